@@ -9,7 +9,13 @@ in HBM, then ONE RCCL gather assembles the image on rank 0.  Total work is fixed
 so the tail of one render's shallow launch overlaps the head of the next; every render is
 still traced, gathered and assembled in full inside the timed region.
 
-    python bench.py --gpus 1 --steps 10 --warmup 2
+A plain run sets up, warms up, times the steps and prints one JSON line.  --full adds, on one GPU, the
+legs the headline does not need: the blocking host call (`host_call`), the other BASELINE configurations
+(`configs`, `configs_brief`) and the CPU baseline (`cpu_baseline`).  --dump-outputs DIR writes the image
+of the last timed step (DIR/image_hit.npy, DIR/image_redshift.npy) so that two builds can be compared
+output for output.
+
+    python bench.py --gpus 1 --steps 10 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -210,7 +216,39 @@ def parse_args():
                          "when the image is sharded")
     ap.add_argument("--emulate-shard", type=str, default=None,
                     help="WORLD:RANK -- time one rank's shard of the image on a single GPU (diagnostic, no gather)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline does not need (N = 1): the blocking host call, the other BASELINE "
+                         "configurations and the CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the image of the last timed step to DIR/image_hit.npy (float32) and DIR/image_redshift.npy "
+                         "(float64), both finite; a fixed sample of them above 64 MB")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.emulate_shard:
+        ap.error("--dump-outputs writes the assembled image: not with --emulate-shard")
+    return args
+
+
+DUMP_CAP_BYTES = 64_000_000      # every file of one dump together, .npy headers included
+
+
+def dump_outputs(outdir, image):
+    """What the timed path hands its caller: the (H, W) redshift image of the last timed step, NaN where no ray hit.  Written
+    as two finite arrays that together hold every pixel: image_hit.npy (float32, 1 = the ray hit the disc, 0 = NaN in the
+    image) and image_redshift.npy (float64, 0 where no ray hit).  Above DUMP_CAP_BYTES a fixed, seeded sample of the
+    flattened image is written instead, with its flat indices (image_sample_index.npy)."""
+    os.makedirs(outdir, exist_ok=True)
+    img = np.asarray(image, dtype=np.float64)
+    hit = np.isfinite(img)
+    out = {"image_hit": hit.astype(np.float32), "image_redshift": np.where(hit, img, 0.0)}
+    if img.size * 12 + 8192 > DUMP_CAP_BYTES:
+        k = (DUMP_CAP_BYTES - 8192) // 20           # per sample: 8 B value, 4 B hit, 8 B index
+        idx = np.sort(np.random.default_rng(0).choice(img.size, size=k, replace=False))
+        out = {name: a.reshape(-1)[idx] for name, a in out.items()}
+        out["image_sample_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def workload(G, size, ens):
@@ -334,8 +372,9 @@ def main():
             return
         pending[slot] = G.gather_image_async(locals_[slot], plan, recv_bufs=recv[slot])
 
-    def drain():
-        for slot in range(2):
+    def drain(first=0):
+        # the older render first: last_image ends as the image of the latest one
+        for slot in (first, 1 - first):
             if pending[slot] is not None:
                 img = pending[slot].result()
                 if img is not None:
@@ -355,7 +394,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(i, i % 2)
-    drain()                   # every render of the timed region is gathered and assembled inside it
+    drain(args.steps % 2)     # every render of the timed region is gathered and assembled inside it
     fence()
     elapsed = time.perf_counter() - t0
     image = last_image[0]
@@ -363,11 +402,14 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    image_host = image.cpu().numpy() if image is not None else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, image_host)
 
     # ---- second leg (N = 1): the blocking host entry point, image copied D2H into a host buffer every step
     #      ("wall time of the blocking ABI call, H2D/D2H included, ctx creation excluded") ----
     host_call = None
-    if world == 1 and not args.no_host_call and not args.emulate_shard:
+    if args.full and world == 1 and not args.no_host_call and not args.emulate_shard:
         import ctypes as C
 
         from gradus_jl_amd import _lib
@@ -431,7 +473,7 @@ def main():
         return
     if rank == 0:
         # sanity: the image is a real render (hits exist, values finite and O(1))
-        img = image.cpu().numpy()
+        img = image_host
         hits = np.isfinite(img)
         assert hits.sum() > 0.05 * total_rays and 0.0 < np.nanmin(img) and np.nanmax(img) < 2.0
 
@@ -554,12 +596,12 @@ def main():
             line["host_call"] = host_call
             line["value_blocking_call_with_d2h"] = host_call["value"]      # SURVEY §8(d)'s definition, named as such
         line["value_device_resident"] = rays_per_s                         # == value (the contract's definition), named as such
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             try:
                 line["configs"] = baseline_configs(G, ens)
             except Exception as e:      # noqa: BLE001 -- a sibling failing must not lose the measured headline
                 line["configs"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.size, args.cpu_seconds)
             except Exception as e:      # noqa: BLE001 -- the checker failing must not lose the measured line
