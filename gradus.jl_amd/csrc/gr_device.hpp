@@ -578,6 +578,10 @@ struct KerrFamily {
     // Kerr-Newman (and every metric below) since round 4: three waves as well, made to fit by parking the stage accelerations
     // in LDS (ParkA: 197 -> 163 registers, no scratch)
     static constexpr int kLaneWavesPerSimd = (CHARGED && GR_PARK_DEFAULT == 0) ? 2 : 3;
+    // Escape radius in units of M (+inf: never cull): beyond it a null geodesic with v^r > 0 escapes with r increasing
+    // monotonically -- the photon region of Kerr ends by 4M for every |a| <= M (the retrograde circular photon orbit of
+    // a = M), and outside it R(r) has no root above an outgoing ray.  Ray::step's escape cull
+    static constexpr double kEscapeRadiusM = CHARGED ? __builtin_inf() : 4.0;
     static constexpr int kParkStages = CHARGED ? GR_PARK_DEFAULT : 0;
     static constexpr bool kColdRare = !CHARGED;                // at the register cap: the event sampling parks in LDS (gr_kernels.hpp)
     real M, a;
@@ -610,6 +614,15 @@ struct KerrFamily {
         g[2] = Sig;
         g[4] = -a * s2 * w;
         g[3] = s2 * (r2 + a2 - a * g[4]);
+    }
+
+    // The escape cull's speed bound (Ray::step): |dr/dλ| at every r' >= r of a null geodesic with E = -v_t, L = v_ϕ.
+    // Σ² (dr/dλ)² = R(r') = [E(r'² + a²) - aL]² - Δ K, with Δ >= 0 outside the horizon, K = Q + (L - aE)² >= 0 and Σ >= r'²,
+    // so |dr/dλ| <= (|E|(r'² + a²) + |aL|) / r'², which falls with r'.  (Kerr only: Kerr-Newman never culls.)
+    GR_DEV real radial_speed_bound(real r, real E, real L) const
+    {
+        const real aE = GR_FABS(E);
+        return aE + GR_FMA(aE, a * a, GR_FABS(a * L)) * rcp_full(r * r);
     }
 
     // hand-differentiated; one reciprocal for everything
@@ -779,6 +792,7 @@ struct JohannsenMetric {
     // one-ray-per-lane kernel: 205 registers and two waves per SIMD left 17 % of the issue slots empty (profiles/r3zz_c4: issue
     // 0.83); with A[1..5] parked in LDS (ParkA, 10 KB per wave) the kernel needs 157 and runs three
     static constexpr int kLaneWavesPerSimd = GR_PARK_DEFAULT > 0 ? 3 : 2;      // (-DGR_PARK_DEFAULT=0: the round-3 shape, for A/B)
+    static constexpr double kEscapeRadiusM = __builtin_inf();                   // never culled (KerrFamily::kEscapeRadiusM)
     static constexpr int kParkStages = GR_PARK_DEFAULT;
     real M, a, a13, a22, a52, e3;
     real ka2, ktM, keM3;                             // a², 2M, ϵ3 M³: uniform, formed once (rhs)
@@ -993,6 +1007,7 @@ struct GenericMetricT {
     static constexpr bool kSlimFused = (ID == GR_METRIC_BUMBLEBEE || ID == GR_METRIC_MORRIS_THORNE);
     static constexpr int kLaneWavesPerSimd = kSlimFused ? GR_FUSED23_LANE_WAVES
                                              : (ID == GR_METRIC_JOHANNSEN_PSALTIS) ? GR_JP_LANE_WAVES : GR_GENERIC_LANE_WAVES;
+    static constexpr double kEscapeRadiusM = __builtin_inf();      // never culled (KerrFamily::kEscapeRadiusM)
     static constexpr bool kColdRare = (ID == GR_METRIC_BUMBLEBEE) && kLaneWavesPerSimd >= 3;
     static constexpr int kParkStages = (!kSlimFused && kLaneWavesPerSimd >= 3) ? GR_PARK_DEFAULT : 0;
     static constexpr bool kHasForce = false;
@@ -1820,6 +1835,7 @@ __device__ __attribute__((noinline)) void tab_rhs_from_global(const double* pc, 
 struct TabulatedMetric {
     static constexpr int kMinWavesPerSimd = GR_TAB_LANE_WAVES < 2 ? GR_TAB_LANE_WAVES : 2;
     static constexpr int kLaneWavesPerSimd = GR_TAB_LANE_WAVES;
+    static constexpr double kEscapeRadiusM = __builtin_inf();      // never culled, a tabulated Kerr included (KerrFamily::kEscapeRadiusM)
     static constexpr int kParkStages = GR_TAB_PARK;      // stage accelerations parked in LDS while a right-hand side runs (ParkA)
     static constexpr bool kHasForce = false;
     static constexpr bool kFusedRhs = false;
@@ -2577,6 +2593,10 @@ struct Params {
                               // runs (POINT_UNITS doubles + one address slot per lane behind the other LDS regions)
     int32_t xcd_spread;       // one-ray-per-lane kernel on rays in CALLER order: 1 = workgroup b traces chunk xcd_chunk(b) of the
     int32_t lds_tab_off;      // rays instead of chunk b (gr_kernels.hpp) | byte offset of the tabulated metric's patch caches in the workgroup's LDS
+    // escape cull (Ray::step): an outgoing ray beyond this radius whose pixel is already decided ends as if it had
+    // reached λ1.  +inf = off (derive_params): what every launch but launch_trace's gated ones (escape_cull_radius) and the host
+    // harnesses see.  (Last, so that the fields before it keep their kernarg offsets.)
+    double r_cull = __builtin_inf();
 };
 
 // the derived fields of Params, from cfg (host side; one place for the library and the two host harnesses)
@@ -2588,6 +2608,7 @@ static inline void derive_params(Params& p)
     p.dtmax = span < 0.0 ? -span : span;
     int64_t mi = p.cfg.maxiters < 0 ? 0 : p.cfg.maxiters;
     p.maxiters32 = (int32_t)(mi > 0x7fffffff ? 0x7fffffff : mi);
+    p.r_cull = __builtin_inf();     // the escape cull is off unless the launcher gates it on (escape_cull_radius)
 }
 
 // Small read-mostly tables staged in LDS by the kernel prologue (null = use the global copy):
@@ -2850,7 +2871,10 @@ struct TabLds : Base {
 // ---------------------------------------------------------------------------------------
 // The per-lane integrator.
 // ---------------------------------------------------------------------------------------
-enum : int32_t { RAY_EVENT = 0x100 };   // bit in Ray::flags while a disc event awaits its root find
+enum : int32_t {
+    RAY_EVENT = 0x100,     // bit in Ray::flags while a disc event awaits its root find
+    RAY_NO_CULL = 0x200    // ... once the escape cull's λ1-first bound has failed for the ray (Ray::step): never tested again
+};
 
 template <class Metric, int DISC>
 struct Ray {
@@ -2889,6 +2913,13 @@ struct Ray {
 
     // a geometry with a ContinuousCallback (distance_to_disc); a mesh is a DiscreteCallback on the step's line element instead
     static constexpr bool kContinuous = (DISC != GR_DISC_NONE && DISC != GR_DISC_MESH);
+    // the escape cull (step()) exists in the fp64 kernels of a single thin disc around a metric with a finite
+    // escape radius; everywhere else it is not compiled at all
+#if defined(GR_REAL_IS_FLOAT) || defined(GR_REAL_IS_TAN2)
+    static constexpr bool kEscapeCull = false;
+#else
+    static constexpr bool kEscapeCull = (DISC == GR_DISC_THIN) && Metric::kEscapeRadiusM < __builtin_inf();
+#endif
 
 #if GR_HAS_MESH
     // ---- MeshAccretionGeometry (geometry/meshes.jl:1-80): after every accepted step the Cartesian line element
@@ -3892,6 +3923,35 @@ struct Ray {
             sth = sn; cth = cn;
             t = tnew;
             dt = GR_FMIN(dtmax, dtnew);
+            // ESCAPE CULL.  Under the host's gating (escape_cull_radius: filter_intersected, a line profile or
+            // (g, ρ) pairs; one thin disc; no hemisphere / chart / winding callback; fp64) finalize() reads nothing of a ray that
+            // does not end IntersectedWithGeometry but its status, and a ray that reaches λ1 keeps NoStatus.  So a ray may stop at
+            // the end of an accepted step whose event check found nothing once no later step can change either:
+            //  1. it escapes: v^r > 0 and r > R_cull >= R_esc (Metric::kEscapeRadiusM) -- an outgoing null geodesic beyond the
+            //     photon region goes out with r increasing monotonically;
+            //  2. no later event: a thin disc's condition is 1 where ρ = r |sin θ| lies outside [r_in, r_out] and r (|cos θ| - gtol)
+            //     inside, so it is <= 0 only where |cos θ| <= gtol and ρ <= r_out, i.e. r <= r_out / sqrt(1 - gtol²) <= R_cull.
+            //     With r > R_cull at every later step end and dense-output sample it stays > 0.  It is > 0 at this step's end
+            //     (cprev, just taken over from cnext) and was at its start: a start < 0 with an end > 0 is an event and has
+            //     returned above (a start of exactly 0, or NaN, has no sign and raises no event at all);
+            //  3. λ1 comes first: |dr/dλ| <= B(r) (Metric::radial_speed_bound, falling with r), so r stays below r + B(r) (λ1 - λ)
+            //     up to λ1; short of r_outer, the full trace reaches λ1 with NoStatus before the chart's outer boundary could make
+            //     it OutOfDomain.  If not, the ray goes on and RAY_NO_CULL keeps it from asking again.
+            // R_cull = (1 + 1e-6) max(R_esc, r_out / sqrt(1 - gtol²)) and the 1e-6 on the bound of 3 cover the rounding of the
+            // conditions and the integrator's drift from the exact geodesic (1e-9 tolerance).  A culled ray takes λ = λ1 and ends
+            // through the test below.  The test sits behind the step's commit, where the fewest values are alive; the common path
+            // pays three compares (the flag word holds nothing but RAY_NO_CULL here: GR_FLAG_* and RAY_EVENT end the ray, winding
+            // counts come with a callback, under which R_cull is +inf); E, L and B are formed once per ray.
+            if constexpr (kEscapeCull) {
+                if (cprev > 0.0 && v[1] > 0.0 && x[1] > (real)p.r_cull && (uint32_t)flags < (uint32_t)RAY_NO_CULL) {
+                    real g[5];
+                    metric_comps(m, x[1], x[2], sth, cth, g);
+                    const real E = -(g[0] * v[0] + g[4] * v[3]), L = g[4] * v[0] + g[3] * v[3];
+                    const real reach = GR_FMA(m.radial_speed_bound(x[1], E, L), tend - t, x[1]);
+                    if (reach * (1.0 + 1e-6) < (real)p.cfg.r_outer) t = tend;
+                    else flags |= RAY_NO_CULL;
+                }
+            }
             return term || !(t < tend);
         } else {
             // step_reject_controller!; a NaN state lands here too (e2 is NaN).  fminf(1/qmin, NaN) returns
@@ -4219,6 +4279,7 @@ struct Ray {
             resolve_event(p);
             flags &= ~RAY_EVENT;
         }
+        if constexpr (kEscapeCull) flags &= ~RAY_NO_CULL;      // a step-loop bit like RAY_EVENT, not an anomaly
         if (flags & GR_FLAG_MASK) status = GR_STATUS_NO_STATUS;
         const Cold& cd = cold_of(p);
         if (cd.tile_cost) {
