@@ -71,29 +71,12 @@ typedef double gr_real_t;
 #define GR_EPS 2.220446049250313e-16
 #endif
 
-#ifndef GR_GENERIC_MIN_WAVES
-#define GR_GENERIC_MIN_WAVES 2
-#endif
-// Stages of the Tsit5 step whose accelerations the one-ray-per-lane kernels of the non-Kerr metrics park in LDS (ParkA below)
-// to run three waves per SIMD instead of two.  MEASURED in round 4 and left OFF: with -DGR_PARK_DEFAULT=5 every such kernel fits
-// 142-168 registers without scratch (205 -> 157 for Johannsen) and 2.4 waves are resident per SIMD instead of 1.7 -- and the
-// issue rate does not move (0.850 against 0.847 per 4 clocks, FP64 pipe 0.77 against 0.75 busy; profiles/r4e_c4_*): Johannsen
-// 1024² 8.44 against 8.07 ms, 2048² 27.8 against 28.5; Bumblebee 2048² 22.9 against 22.4; dilaton-axion 38.5 against 39.2.  The
-// slots two waves leave empty are not waiting for a third wave: 89 % of these kernels' instructions are FP64 (Kerr: 85 %), which
-// the pipe takes at 0.77 per 4 clocks at best.  The fp32 kernels have registers to spare and never park.
-#ifndef GR_PARK_DEFAULT
-#define GR_PARK_DEFAULT 0
-#endif
 // MeshAccretionGeometry (GR_DISC_MESH) exists in the fp64 kernels only (and in the host harness); the fp32 and tangent flavours
 // do not instantiate it and the host unit refuses the combination
 #if defined(GR_REAL_IS_TAN2) || defined(GR_REAL_IS_FLOAT)
 #define GR_HAS_MESH 0
 #else
 #define GR_HAS_MESH 1
-#endif
-// tests due in one wave after a step up to which the wave takes them one by one, all lanes on one test (above: each lane its own)
-#ifndef GR_MESH_WAVE_MAX
-#define GR_MESH_WAVE_MAX 16
 #endif
 
 #ifdef GR_HOST_HARNESS
@@ -148,15 +131,8 @@ typedef creal hreal;
 // issues at the FP64 rate (one per 4 clocks and SIMD, profiles/r5_valu_calib.json).  The weighted sums of a Tsit5 step -- stage
 // arguments, new state, error estimate -- are axpys over the FOUR components of one ray with a common coefficient: components
 // (0, 1) and (2, 3) ride in the two halves of one packed instruction (the coefficient broadcast from one scalar register,
-// op_sel_hi), no second ray, no masks.  -DGR_PK_F32=0 builds the scalar sums (the A/B of profiles/r6_c5f32_packed_ab.log).
-#ifndef GR_PK_F32
+// op_sel_hi), no second ray, no masks (against the scalar sums: profiles/r6_c5f32_packed_ab.log).
 #ifdef GR_REAL_IS_FLOAT
-#define GR_PK_F32 1
-#else
-#define GR_PK_F32 0
-#endif
-#endif
-#if GR_PK_F32
 typedef float gr_f2 __attribute__((ext_vector_type(2)));
 #define GR_PK2(arr, i) (gr_f2{ (arr)[(i)], (arr)[(i) + 1] })
 #define GR_PKFMA(c, a, b) __builtin_elementwise_fma((gr_f2)(c), (a), (b))
@@ -167,7 +143,7 @@ typedef float gr_f2 __attribute__((ext_vector_type(2)));
 // ---------------------------------------------------------------------------------------
 GR_DEV real rcp_full(real x)
 {
-#if defined(GR_REAL_IS_TAN2) && !defined(GR_TAN_OLD_RCP)
+#ifdef GR_REAL_IS_TAN2
     return gr_t_rcp(x);      // value: seed + two Newton steps on the plain double; tangents: -x' / x² (no Newton steps on tangents)
 #else
     // v_rcp_f64 seed (4.6e-8 relative, measured) + two Newton steps: <= 1 ulp for normal, finite x
@@ -180,23 +156,10 @@ GR_DEV real rcp_full(real x)
 #endif
 }
 GR_DEV real rcp_raw(real x) { return GR_RCP_SEED(x); }
-GR_DEV real rcp_fast(real x);
-// The reciprocal inside the fused right-hand sides: 1 = seed + one Newton step (2e-15 relative, the rounding level of the ~85
-// operations it feeds), 2 = two steps (<= 1 ulp).
-#ifndef GR_RHS_RCP_STEPS
-#define GR_RHS_RCP_STEPS 1
-#endif
-GR_DEV real rcp_rhs(real x)
-{
-#if GR_RHS_RCP_STEPS == 1
-    return rcp_fast(x);
-#else
-    return rcp_full(x);
-#endif
-}
+// The reciprocal inside the fused right-hand sides: 2e-15 relative, the rounding level of the ~85 operations it feeds
 GR_DEV real rcp_fast(real x)
 {
-#if defined(GR_REAL_IS_TAN2) && !defined(GR_TAN_OLD_RCP)
+#ifdef GR_REAL_IS_TAN2
     return gr_t_rcp(x);
 #else
     // one Newton step: ~2e-15 relative
@@ -207,7 +170,7 @@ GR_DEV real rcp_fast(real x)
 }
 GR_DEV real sqrt_fast(real x)
 {
-#if defined(GR_REAL_IS_TAN2) && !defined(GR_TAN_OLD_RCP)
+#ifdef GR_REAL_IS_TAN2
     return gr_t_sqrt(x);
 #else
     // x > 0, normal range.  rsq seed + two coupled Newton steps (Goldschmidt): <= 1 ulp
@@ -229,12 +192,9 @@ GR_DEV int sgn(real x) { return (x > 0.0) - (x < 0.0); }
 // are formed by the vector ALU (the scalar unit has no FP64), so the compiler keeps them in VGPRs for the whole step loop;
 // at the 168-register budget it spilled exactly those to scratch and reloaded them in every stage.  Two v_readfirstlane
 // once per kernel put them where uniform values belong.
-#ifndef GR_UNIFORM_TO_SGPR
-#define GR_UNIFORM_TO_SGPR 1
-#endif
 GR_DEV real uni(real x)
 {
-#if defined(GR_HOST_HARNESS) || defined(GR_REAL_IS_TAN2) || !GR_UNIFORM_TO_SGPR
+#if defined(GR_HOST_HARNESS) || defined(GR_REAL_IS_TAN2)
     return x;
 #elif defined(GR_REAL_IS_FLOAT)
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
@@ -342,7 +302,7 @@ GR_DEV void sincos_fast_impl(T x, T& s_out, T& c_out)
     c_out = ((q + 1) & 2) ? -c0 : c0;
 }
 
-#if defined(GR_REAL_IS_TAN2) && !defined(GR_TAN_OLD_SINCOS)
+#ifdef GR_REAL_IS_TAN2
 // the polynomials run on the VALUE; the tangents are cos θ θ' and -sin θ θ'
 GR_DEV void sincos_fast(real x, real& s_out, real& c_out)
 {
@@ -363,39 +323,27 @@ constexpr creal SINCOS_ROT_MAX = 0.03125;
 // The two polynomials each open with an FMA that has TWO constant operands, and a VALU instruction of this ISA reads at
 // most one scalar / literal operand: the other constant has to sit in a vector register.  Left to itself the compiler
 // rebuilds both (v_mov_b32 pairs + a copy) at each of the six stage points of a step -- 36 of the step's ~130 non-FP64
-// vector instructions.  RotK keeps the two addends in registers for the life of the ray (4 VGPRs), made opaque once in
-// Ray::init so that they are not rematerialised.
-#ifndef GR_ROT_MODE
-#define GR_ROT_MODE 3
-#endif
+// vector instructions.  So each such FMA is opened as a product and a sum, one scalar operand each.
+//
+// RotK is what an earlier form left behind: it kept the two addends (1/120, 1/24) in registers for the life of the ray.
+// Nothing reads them now, and the compiler drops them -- but with the member gone from Ray it allocates the registers of
+// k_trace_persistent<TabulatedMetric, GR_DISC_MESH> differently (two v_mov_b32 more) and swaps operands in 87 other kernels.
+// The struct, Ray::rotk and its load() stay so that removing the build switches compiles to the same kernels
+// (profiles/r8_refactor_isa.txt); they can go with the next change that alters the integrator's code anyway.
 struct RotK {
-    real s2, c2;      // 1/120, 1/24 (GR_ROT_MODE 1 only)
+    real s2, c2;
     GR_DEV void load()
     {
         s2 = 8.3333333333333333e-03;
         c2 = 4.1666666666666664e-02;
-#if GR_ROT_MODE == 1 && !defined(GR_HOST_HARNESS) && !defined(GR_REAL_IS_TAN2)
-        asm volatile("" : "+v"(s2), "+v"(c2));
-#endif
     }
 };
 template <class T>
-GR_DEV void sincos_rot_impl(const RotK& k, T th0, T s0, T c0, T th, T& s_out, T& c_out)
+GR_DEV void sincos_rot_impl(T th0, T s0, T c0, T th, T& s_out, T& c_out)
 {
     const T d = th - th0;
     if (GR_FABS(d) <= SINCOS_ROT_MAX) {
         const T z = d * d;
-#if GR_ROT_MODE == 2
-        // every FMA with ONE non-inline constant (the second operand is 1.0 or -0.5, which the ISA encodes inline):
-        //   sin δ = δ + δ z S1 (1 + z (S2/S1) (1 + z S3/S2)),   cos δ - 1 = z (-1/2 + z C2 (1 + z C3/C2))
-        // three multiplications more than Horner's form, six register moves fewer per stage point
-        const T u1 = GR_FMA(z, -2.3809523809523808e-02, 1.0);          // S3/S2 = -1/42
-        const T u3 = GR_FMA(z * u1, -5.0e-02, 1.0);                    // S2/S1 = -1/20
-        const T sd = GR_FMA((d * z) * u3, -1.6666666666666666e-01, d); // sin δ
-        const T t1 = GR_FMA(z, -3.3333333333333333e-02, 1.0);          // C3/C2 = -1/30
-        const T pc = GR_FMA(z * t1, 4.1666666666666664e-02, -0.5);
-#elif GR_ROT_MODE == 3
-        // the two-constant FMA opened as a product and a sum (one scalar operand each)
         T ps, pc;
         {
 #pragma clang fp contract(off)
@@ -407,13 +355,6 @@ GR_DEV void sincos_rot_impl(const RotK& k, T th0, T s0, T c0, T th, T& s_out, T&
         ps = fma_sk(z, ps, -1.6666666666666666e-01);
         const T sd = GR_FMA(d * z, ps, d);                    // sin δ
         pc = GR_FMA(z, pc, -0.5);
-#else
-        T ps = GR_FMA(z, -1.9841269841269841e-04, (T)k.s2);
-        ps = GR_FMA(z, ps, -1.6666666666666666e-01);
-        const T sd = GR_FMA(d * z, ps, d);                    // sin δ
-        T pc = GR_FMA(z, -1.3888888888888889e-03, (T)k.c2);
-        pc = GR_FMA(z, pc, -0.5);
-#endif
         const T cm1 = z * pc;                                        // cos δ - 1
         s_out = GR_FMA(c0, sd, GR_FMA(s0, cm1, s0));
         c_out = GR_FMA(-s0, sd, GR_FMA(c0, cm1, c0));
@@ -423,18 +364,18 @@ GR_DEV void sincos_rot_impl(const RotK& k, T th0, T s0, T c0, T th, T& s_out, T&
     }
 }
 
-#if defined(GR_REAL_IS_TAN2) && !defined(GR_TAN_OLD_SINCOS)
+#ifdef GR_REAL_IS_TAN2
 // rotation on the VALUES (the tangents of sin θ0, cos θ0 are not needed: d sin θ = cos θ θ', d cos θ = -sin θ θ')
-GR_DEV void sincos_rot(const RotK& k, real th0, real s0, real c0, real th, real& s_out, real& c_out)
+GR_DEV void sincos_rot(real th0, real s0, real c0, real th, real& s_out, real& c_out)
 {
     double sv, cv;
-    sincos_rot_impl<double>(k, th0.v, s0.v, c0.v, th.v, sv, cv);
+    sincos_rot_impl<double>(th0.v, s0.v, c0.v, th.v, sv, cv);
     gr_t_sincos_lift(th, sv, cv, s_out, c_out);
 }
 #else
-GR_DEV void sincos_rot(const RotK& k, real th0, real s0, real c0, real th, real& s_out, real& c_out)
+GR_DEV void sincos_rot(real th0, real s0, real c0, real th, real& s_out, real& c_out)
 {
-    sincos_rot_impl<real>(k, th0, s0, c0, th, s_out, c_out);
+    sincos_rot_impl<real>(th0, s0, c0, th, s_out, c_out);
 }
 #endif
 
@@ -445,13 +386,9 @@ GR_DEV void sincos_rot(const RotK& k, real th0, real s0, real c0, real th, real&
 // formed anew from the step's base at the next stage: the error does not accumulate (the base itself, rotated once per
 // accepted step, keeps the three-term form and its resynchronisation), and 1e-12 of an acceleration for one stage of the
 // rare large steps is three orders below the integration tolerance the kernels run at.  Three instructions per stage fewer.
-#ifndef GR_ROT_STAGE_TERMS
-#define GR_ROT_STAGE_TERMS 2
-#endif
 template <class T>
-GR_DEV void sincos_rot_stage_impl(const RotK& k, T th0, T s0, T c0, T th, T& s_out, T& c_out)
+GR_DEV void sincos_rot_stage_impl(T th0, T s0, T c0, T th, T& s_out, T& c_out)
 {
-#if GR_ROT_STAGE_TERMS == 2 && GR_ROT_MODE == 3
     const T d = th - th0;
     if (GR_FABS(d) <= SINCOS_ROT_MAX) {
         const T z = d * d;
@@ -470,22 +407,19 @@ GR_DEV void sincos_rot_stage_impl(const RotK& k, T th0, T s0, T c0, T th, T& s_o
         GR_NO_SPECULATION();
         sincos_fast_impl<T>(th, s_out, c_out);
     }
-#else
-    sincos_rot_impl<T>(k, th0, s0, c0, th, s_out, c_out);
-#endif
 }
 
-#if defined(GR_REAL_IS_TAN2) && !defined(GR_TAN_OLD_SINCOS)
-GR_DEV void sincos_rot_stage(const RotK& k, real th0, real s0, real c0, real th, real& s_out, real& c_out)
+#ifdef GR_REAL_IS_TAN2
+GR_DEV void sincos_rot_stage(real th0, real s0, real c0, real th, real& s_out, real& c_out)
 {
     double sv, cv;
-    sincos_rot_stage_impl<double>(k, th0.v, s0.v, c0.v, th.v, sv, cv);
+    sincos_rot_stage_impl<double>(th0.v, s0.v, c0.v, th.v, sv, cv);
     gr_t_sincos_lift(th, sv, cv, s_out, c_out);
 }
 #else
-GR_DEV void sincos_rot_stage(const RotK& k, real th0, real s0, real c0, real th, real& s_out, real& c_out)
+GR_DEV void sincos_rot_stage(real th0, real s0, real c0, real th, real& s_out, real& c_out)
 {
-    sincos_rot_stage_impl<real>(k, th0, s0, c0, th, s_out, c_out);
+    sincos_rot_stage_impl<real>(th0, s0, c0, th, s_out, c_out);
 }
 #endif
 
@@ -574,15 +508,13 @@ struct KerrFamily {
     static constexpr int kMinWavesPerSimd = CHARGED ? 2 : 1;   // persistent kernel: Kerr fits 2 waves/SIMD on its own
     // one-ray-per-lane kernel: capped at 168 VGPRs = 3 waves/SIMD.  The few spilled values (36-68 B of scratch) live in
     // the rarely executed event-sampling blocks, none on the step's main path; the third wave hides the dependent
-    // FP64 chains that two waves leave exposed: 22.95 -> 21.97 ms on the 2048² image (profiles/r2_ab_variants.txt)
-    // Kerr-Newman (and every metric below) since round 4: three waves as well, made to fit by parking the stage accelerations
-    // in LDS (ParkA: 197 -> 163 registers, no scratch)
-    static constexpr int kLaneWavesPerSimd = (CHARGED && GR_PARK_DEFAULT == 0) ? 2 : 3;
+    // FP64 chains that two waves leave exposed: 22.95 -> 21.97 ms on the 2048² image (profiles/r2_ab_variants.txt).
+    // Kerr-Newman needs 197 registers: two waves
+    static constexpr int kLaneWavesPerSimd = CHARGED ? 2 : 3;
     // Escape radius in units of M (+inf: never cull): beyond it a null geodesic with v^r > 0 escapes with r increasing
     // monotonically -- the photon region of Kerr ends by 4M for every |a| <= M (the retrograde circular photon orbit of
     // a = M), and outside it R(r) has no root above an outgoing ray.  Ray::step's escape cull
     static constexpr double kEscapeRadiusM = CHARGED ? __builtin_inf() : 4.0;
-    static constexpr int kParkStages = CHARGED ? GR_PARK_DEFAULT : 0;
     static constexpr bool kColdRare = !CHARGED;                // at the register cap: the event sampling parks in LDS (gr_kernels.hpp)
     real M, a;
     real Q, Q2, qm;      // CHARGED only: charge, its square, test-particle q (or q/μ)
@@ -697,7 +629,7 @@ struct KerrFamily {
         real Del = GR_FMA(-tM, r, ra2);
         if (CHARGED) Del += Q2;
         const real Ds2 = Del * s2;
-        const real P = rcp_rhs(Sig * Ds2);
+        const real P = rcp_fast(Sig * Ds2);
         const real iSig = P * Ds2;           // 1/Σ
         const real iDs = P * Sig;            // 1/(Δ sin²θ)
         const real iDel = iDs * s2;          // 1/Δ
@@ -789,11 +721,9 @@ struct JohannsenMetric {
     static constexpr bool kHasForce = false;
     static constexpr bool kFusedRhs = true;                    // rhs() below replaces eval() + the generic contraction
     static constexpr int kMinWavesPerSimd = 2;
-    // one-ray-per-lane kernel: 205 registers and two waves per SIMD left 17 % of the issue slots empty (profiles/r3zz_c4: issue
-    // 0.83); with A[1..5] parked in LDS (ParkA, 10 KB per wave) the kernel needs 157 and runs three
-    static constexpr int kLaneWavesPerSimd = GR_PARK_DEFAULT > 0 ? 3 : 2;      // (-DGR_PARK_DEFAULT=0: the round-3 shape, for A/B)
+    // one-ray-per-lane kernel: 205 registers, two waves per SIMD (a third wave did not raise the issue rate: DESIGN.md §5e)
+    static constexpr int kLaneWavesPerSimd = 2;
     static constexpr double kEscapeRadiusM = __builtin_inf();                   // never culled (KerrFamily::kEscapeRadiusM)
-    static constexpr int kParkStages = GR_PARK_DEFAULT;
     real M, a, a13, a22, a52, e3;
     real ka2, ktM, keM3;                             // a², 2M, ϵ3 M³: uniform, formed once (rhs)
     real kA1, kA2, kA5, kA1r, kA2r, kA5r;            // α13 M³, α22 M², α52 M² and -3, -2, -2 times them: A_i = 1 + kA_i / r^n
@@ -893,7 +823,7 @@ struct JohannsenMetric {
         const real a2 = ka2, tM = ktM, eM3 = keM3;
         // A_i = 1 + α (M/r)^n with the powers of M folded into uniform factors: nine instructions for the three functions
         // and their r-derivatives (twelve when (M/r)^n is formed first)
-        const real ir = rcp_rhs(r);
+        const real ir = rcp_fast(r);
         const real ir2 = ir * ir, ir3 = ir2 * ir, ir4 = ir2 * ir2;
         const real A1 = GR_FMA(kA1, ir3, 1.0), A2 = GR_FMA(kA2, ir2, 1.0), A5 = GR_FMA(kA5, ir2, 1.0);
         const real A1r = kA1r * ir4, A2r = kA2r * ir3, A5r = kA5r * ir3;
@@ -913,7 +843,7 @@ struct JohannsenMetric {
         const real DA5_r = GR_FMA(Del, A5r, Del_r * A5);
         // reciprocals
         const real e1 = N * DA5, e2 = Sig * s2;
-        const real R = rcp_rhs(e1 * e2);
+        const real R = rcp_fast(e1 * e2);
         const real ie1 = R * e2, ie2 = R * e1;                      // 1/(N ΔA5), 1/(Σ s²)
         const real iN = ie1 * DA5, iDA5 = ie1 * N, iSig = ie2 * s2;
         const real iDel = A5 * iDA5;
@@ -977,15 +907,6 @@ struct JohannsenMetric {
 // step then carried all nine metric bodies -- a 9 600-instruction step loop (57 KB of code against a 64 KB
 // instruction cache), 180 B of scratch per lane and 1.8x the time of Kerr.  ID < 0 keeps the run-time switch
 // (tests/host_harness.cpp traces every metric through one instantiation).
-#ifndef GR_JP_LANE_WAVES
-#define GR_JP_LANE_WAVES (GR_PARK_DEFAULT > 0 ? 3 : 2)
-#endif
-#ifndef GR_GENERIC_LANE_WAVES
-#define GR_GENERIC_LANE_WAVES (GR_PARK_DEFAULT > 0 ? 3 : 2)
-#endif
-#ifndef GR_FUSED23_LANE_WAVES
-#define GR_FUSED23_LANE_WAVES 3
-#endif
 // The fused dilaton-axion form shares one reciprocal of Σh Δh s² K² between 1/Σh, 1/Δh and the inverse t-ϕ block: in single precision
 // that costs rays near the horizon (the fp32 soak flags 1089 rays instead of 875 with it, profiles/r4z_soak32_2600_fp32_fused_dilaton_axion.txt) -- the fp32
 // kernels keep the dual-number form for this metric, as they keep the inverse components formed first for Kerr -- and for NoZ, whose
@@ -997,24 +918,21 @@ struct JohannsenMetric {
 #endif
 template <int ID>
 struct GenericMetricT {
-    static constexpr int kMinWavesPerSimd = GR_GENERIC_MIN_WAVES;
-    // one-ray-per-lane kernel: three waves per SIMD with the stage accelerations parked in LDS (181-228 registers without,
-    // 142-168 with, no scratch: scripts/kernel_probe.sh "GenericMetricT<id>")
+    static constexpr int kMinWavesPerSimd = 2;     // persistent kernel
+    // one-ray-per-lane kernel: 181-228 registers (scripts/kernel_probe.sh "GenericMetricT<id>"), two waves per SIMD.
     // Bumblebee and Morris-Thorne with their fused right-hand sides need 167 registers (Bumblebee: with the event sampling's
-    // registers parked in LDS like Kerr's, kColdRare): three waves per SIMD (GR_FUSED23_LANE_WAVES=2: the two-wave shape, A/B)
+    // registers parked in LDS like Kerr's, kColdRare): three waves per SIMD
     // (Kerr-dark-matter and Kerr-refractive, fused later in round 4, need 193: at three waves they spill 80-96 bytes and run 6.3 /
     // 8.6 ms against 5.6 / 7.8 at 1024², 19.9 / 26.4 against 20.2 / 26.2 at 2048² -- two waves)
     static constexpr bool kSlimFused = (ID == GR_METRIC_BUMBLEBEE || ID == GR_METRIC_MORRIS_THORNE);
-    static constexpr int kLaneWavesPerSimd = kSlimFused ? GR_FUSED23_LANE_WAVES
-                                             : (ID == GR_METRIC_JOHANNSEN_PSALTIS) ? GR_JP_LANE_WAVES : GR_GENERIC_LANE_WAVES;
+    static constexpr int kLaneWavesPerSimd = kSlimFused ? 3 : 2;
     static constexpr double kEscapeRadiusM = __builtin_inf();      // never culled (KerrFamily::kEscapeRadiusM)
     static constexpr bool kColdRare = (ID == GR_METRIC_BUMBLEBEE) && kLaneWavesPerSimd >= 3;
-    static constexpr int kParkStages = (!kSlimFused && kLaneWavesPerSimd >= 3) ? GR_PARK_DEFAULT : 0;
     static constexpr bool kHasForce = false;
     // rhs() below: hand-derived for Johannsen-Psaltis (round 3), for Bumblebee, Morris-Thorne, Kerr-dark-matter and Kerr-refractive
     // (round 4; the last two as Kerr plus the terms of their r-dependent parameter), flat space, dilaton-axion and NoZ: every metric
     // of the catalogue.  eval() + the generic contraction on typed duals remains as the definition the fused forms are tested
-    // against (tests/test_kernel_logic_host.py), as the fp32 kernels' form for dilaton-axion and NoZ, and under GR_NO_FUSED_RHS
+    // against (tests/test_kernel_logic_host.py), and as the fp32 kernels' form for dilaton-axion and NoZ
     static constexpr bool kFusedRhs = (ID == GR_METRIC_JOHANNSEN_PSALTIS || ID == GR_METRIC_BUMBLEBEE || ID == GR_METRIC_MORRIS_THORNE
                                        || ID == GR_METRIC_KERR_DARK_MATTER || ID == GR_METRIC_KERR_REFRACTIVE || ID == GR_METRIC_SPHERICAL
                                        || (ID == GR_METRIC_DILATON_AXION && GR_DA_FUSED) || (ID == GR_METRIC_NOZ && GR_DA_FUSED));
@@ -1325,7 +1243,7 @@ struct GenericMetricT {
         const real Sig = GR_FMA(-a2, s2, ra2);
         const real Del = GR_FMA(-tM, r, ra2);
         const real Ds2 = Del * s2;
-        const real Pr = rcp_rhs(Sig * Ds2);
+        const real Pr = rcp_fast(Sig * Ds2);
         const real iSig = Pr * Ds2, iDs = Pr * Sig, iDel = iDs * s2;
         const real tr = 2.0 * r;
         const real w = (tM * r) * iSig;
@@ -1370,7 +1288,7 @@ struct GenericMetricT {
         if constexpr (ID == GR_METRIC_MORRIS_THORNE) {
             const real l = r;
             const real w = GR_FMA(l, l, P[0] * P[0]);
-            const real R = rcp_rhs(w * s);                   // 1/(w s)
+            const real R = rcp_fast(w * s);                   // 1/(w s)
             const real iw = R * s, is = R * w;
             const real vp2 = vp * vp;
             const real tl = 2.0 * l;
@@ -1383,7 +1301,7 @@ struct GenericMetricT {
             // flat space in spherical coordinates (minkowski.jl:4-13): g = diag(-1, 1, r², r² s²), so
             //   a^t = 0,  a^r = r (v_θ² + s² v_ϕ²),  a^θ = -2 v_r v_θ / r + s c v_ϕ²,  a^ϕ = -2 (v_r / r + (c/s) v_θ) v_ϕ.
             // One reciprocal, 1/(r s), shared by 1/r and 1/s.
-            const real R = rcp_rhs(r * s);
+            const real R = rcp_fast(r * s);
             const real ir = R * s, is = R * r;
             const real vp2 = vp * vp;
             at = 0.0;
@@ -1407,7 +1325,7 @@ struct GenericMetricT {
             const real a = P[1], b = P[3];
             const real a2 = ka2;
             const real s2 = s * s, S2 = 2.0 * (s * c);
-            const real is2 = rcp_rhs(s2);
+            const real is2 = rcp_fast(s2);
             const real Wm1 = GR_FMA(2.0 * kd_bab, c, kd_N0) * is2;          // W - 1
             const real W = 1.0 + Wm1;
             const real W_h = -(GR_FMA(2.0 * kd_bab, s, Wm1 * S2) * is2);    // ∂_θ W
@@ -1436,7 +1354,7 @@ struct GenericMetricT {
             const real Phi_h = GR_FMA(S2, F, -(s2 * (Dh * G_h)));
             const real K2 = K * K;
             const real DsK = (Dh * s2) * K2;
-            const real R = rcp_rhs(Sh * DsK);
+            const real R = rcp_fast(Sh * DsK);
             const real iSh = R * DsK, J = R * Sh, iDh = J * (s2 * K2);
             const real Pd = GR_FMA(Dh_r, vr, P_h * vh), Qd = GR_FMA(Q_r, vr, Q_h * vh), Phd = GR_FMA(Phi_r, vr, Phi_h * vh);
             const real Shd = GR_FMA(rp, vr, Sh_h * vh);
@@ -1500,7 +1418,7 @@ struct GenericMetricT {
             const real hpp_r = s2 * GR_FMA(tr, big, Se * big_r);
             const real hpp_y = GR_FMA(-2.0 * y, Sb, s2 * GR_FMA(Se_y, big, Se * big_y));
             const real DlS = Del * Se;
-            const real R = rcp_rhs((D * DlS) * s2);
+            const real R = rcp_fast((D * DlS) * s2);
             const real J1 = R * s2;                      // 1/(D Δ Se)
             const real iD = R * (DlS * s2);
             const real is2Se = R * (D * Del);            // 1/(s² Se)
@@ -1583,14 +1501,14 @@ struct GenericMetricT {
         } else if constexpr (ID == GR_METRIC_BUMBLEBEE) {
             const real tM = ktM, K = ktM * P[1];
             const real rm = r - tM;
-            const real Q = rcp_rhs(r * rm);                  // 1/(r (r - 2M))
+            const real Q = rcp_fast(r * rm);                  // 1/(r (r - 2M))
             const real ir = Q * rm, irm = Q * r;
             const real s2 = s * s, S2 = 2.0 * (s * c);
             const real u = tM * ir, ir2 = ir * ir;
             const real Kir = K * ir;                         // -g_tϕ / s²
             const real r2 = r * r;
             const real Dp = GR_FMA(u - 1.0, r2, -((K * Kir) * (s2 * ir)));       // D' = (u - 1) r² - K² s²/r²
-            const real R = rcp_rhs(Dp * s2);                 // 1/(D' s²)
+            const real R = rcp_fast(Dp * s2);                 // 1/(D' s²)
             const real iDp = R * s2, is2Dp = R;
             // metric gradients
             const real gtt_r = -(u * ir);
@@ -1623,7 +1541,7 @@ struct GenericMetricT {
         const real a2S2 = a2 * S2;                         // -Σ_θ
         const real a2s2 = a2 * s2;
         const real Sig = rho2 - a2s2;                      // r² + a² cos²θ (Σ >= r²: no cancellation)
-        const real iSig = rcp_rhs(Sig);
+        const real iSig = rcp_fast(Sig);
         const real Del = GR_FMA(-tM, r, rho2);
         // w, h, η and their gradients
         const real w = (tM * r) * iSig;
@@ -1641,7 +1559,7 @@ struct GenericMetricT {
         const real Dt_h = GR_FMA(a2S2, h, a2s2 * h_h);
         // reciprocals
         const real HD = H * Dt;
-        const real R = rcp_rhs(HD * s2);                  // 1/(H Δ̃ s²)
+        const real R = rcp_fast(HD * s2);                  // 1/(H Δ̃ s²)
         const real iH = R * (Dt * s2), iDt = R * (H * s2), is2Dt = R * H;
         // dots along the ray
         const real hd = GR_FMA(h_r, vr, h_h * vh);
@@ -1729,7 +1647,7 @@ GR_DEV void geodesic_contract(const real j1[5], const real j2[5], const real gi[
 // a 64-byte head; a lane compares its patch number with the tags (read as vectors: one LDS latency per look-up), and reads its
 // coefficients from its slot with ds_read_b128 -- lanes in one slot read one address (a broadcast), lanes in different slots
 // different bank groups (the slot stride is 208 mod 256 bytes), so the cost of an evaluation does not depend on how many patches
-// the wave straddles.  The reads run GR_TAB_LOOKAHEAD coefficients ahead of the arithmetic, pinned there by a data dependence
+// the wave straddles.  The reads run kTabLookahead coefficients ahead of the arithmetic, pinned there by a data dependence
 // (CoefStream).  A patch that is not resident is copied by all active lanes into a slot no lane of this evaluation reads; a wave
 // that straddles more patches than it has slots (the shadow's edge) sends the lanes left over to global memory through one
 // out-of-line copy of the evaluation.  The scalar path that was built first -- s_load the patch of the first unfinished lane,
@@ -1744,38 +1662,23 @@ GR_DEV void geodesic_contract(const real j1[5], const real j2[5], const real gi[
 // 105 coefficients of an evaluation would cost as many FP64-rate instructions as the 210 operations themselves; the components
 // and their Jacobian are rounded to float once and the inverse, the contraction and the whole step run in single precision.
 // ---------------------------------------------------------------------------------------
-#define GR_HAS_TABULATED 1      // (every flavour of the kernels: fp64, fp32, tangents)
-#ifndef GR_TAB_SLOTS
-#define GR_TAB_SLOTS 12
-#endif
-#ifndef GR_TAB_FETCH
-#define GR_TAB_FETCH 1      // missing patches a wave copies into its cache side by side; 2 and 4 measured equal (27.7 / 28.3 ms against
-#endif                      // 27.4 at 1024², profiles/r5q_tab_slots_ab.log): the slow waves are slow in the global-memory evaluation
-
-#ifndef GR_TAB_LANE_WAVES
 #ifdef GR_REAL_IS_TAN2
-#define GR_TAB_LANE_WAVES 1
+constexpr int kTabLaneWaves = 1;        // waves per SIMD of the tabulated metric's kernels
 #else
-#define GR_TAB_LANE_WAVES 2
+constexpr int kTabLaneWaves = 2;
 #endif
-#endif
-#ifndef GR_TAB_PARK
-#define GR_TAB_PARK 0       // stage accelerations parked in LDS (ParkA); measured equal at two waves per SIMD (profiles/r5e_tab_ab.log)
-#endif
-#ifndef GR_TAB_LOOKAHEAD_GLOBAL
-#define GR_TAB_LOOKAHEAD_GLOBAL 32
-#endif
-#ifndef GR_TAB_LOOKAHEAD
-#define GR_TAB_LOOKAHEAD 16     // coefficients the LDS reads of an evaluation run ahead of its arithmetic (LdsCoef)
-#endif
+constexpr int kTabLookahead = 16;       // coefficients the LDS reads of an evaluation run ahead of its arithmetic (LdsCoef)
+constexpr int kTabLookaheadGlobal = 32; // ... and the reads from global memory (GlobalCoef)
 // The wave's patch cache in LDS: [ 16 ints: kTabSlots tags, -1 up to index 14, the round-robin counter at 15 | kTabSlots slots of
 // kTabSlotBytes ].  The tags are read four at a time (ds_read_b128), so a look-up costs one LDS latency whatever the number of slots.
 // The slot stride is 208 mod 256 bytes: slot k starts 208 k bytes (mod 256) into the 64 banks -- distinct 16-byte columns for k < 16,
 // so the lanes of one ds_read group that sit in different slots do not collide.
-constexpr int kTabSlots = GR_TAB_SLOTS;
+constexpr int kTabSlots = 12;
 constexpr int kTabTagVecs = (kTabSlots + 3) / 4;
 constexpr int kTabRR = 15;              // index of the round-robin counter among the 16 ints of the head
-constexpr int kTabFetch = GR_TAB_FETCH;
+// missing patches a wave copies into its cache side by side; 2 and 4 measured equal (27.7 / 28.3 ms against 27.4 at 1024²,
+// profiles/r5q_tab_slots_ab.log): the slow waves are slow in the global-memory evaluation
+constexpr int kTabFetch = 1;
 constexpr int kTabCopyDepth = 8 / kTabFetch;        // loads per patch a lane keeps in flight while it copies (8 in flight in all)
 constexpr int kTabHeadBytes = 64;
 // (the smallest size >= a patch that is 208 mod 256: 1488 at degree 7, 1232 at 6, 976 at 5)
@@ -1833,10 +1736,9 @@ __device__ __attribute__((noinline)) void tab_rhs_from_global(const double* pc, 
                                                              real s, real c, real vt, real vr, real vh, real vp, real* out);
 #endif
 struct TabulatedMetric {
-    static constexpr int kMinWavesPerSimd = GR_TAB_LANE_WAVES < 2 ? GR_TAB_LANE_WAVES : 2;
-    static constexpr int kLaneWavesPerSimd = GR_TAB_LANE_WAVES;
+    static constexpr int kMinWavesPerSimd = kTabLaneWaves;
+    static constexpr int kLaneWavesPerSimd = kTabLaneWaves;
     static constexpr double kEscapeRadiusM = __builtin_inf();      // never culled, a tabulated Kerr included (KerrFamily::kEscapeRadiusM)
-    static constexpr int kParkStages = GR_TAB_PARK;      // stage accelerations parked in LDS while a right-hand side runs (ParkA)
     static constexpr bool kHasForce = false;
     static constexpr bool kFusedRhs = false;
     static constexpr bool kByTheta = true;      // evaluated at (r, θ) -- the integrator hands θ over next to sin θ, cos θ
@@ -1914,7 +1816,7 @@ struct TabulatedMetric {
     // (b) the step loop: the wave's LDS patch cache (above).
 #ifndef GR_HOST_HARNESS
     // The coefficient stream of one evaluation out of an LDS slot: ds_read_b128 of the pairs the recurrences consume in
-    // order.  Reads run GR_TAB_LOOKAHEAD coefficients ahead of the arithmetic: when a row of a component has been folded in,
+    // order.  Reads run kTabLookahead coefficients ahead of the arithmetic: when a row of a component has been folded in,
     // the pairs up to that distance beyond it are requested, so a read's LDS latency lies behind the FMAs of the rows before
     // it and only the look-ahead (2 registers per coefficient) is held in registers.  Left to the scheduler all reads go to
     // the top of the evaluation (360 registers: 1.3 KB of scratch per lane) -- scheduling barriers do not hold the pure
@@ -1998,12 +1900,12 @@ struct TabulatedMetric {
             issue(from, to);
         }
     };
-    typedef CoefStream<const double2_t __attribute__((address_space(3)))*, unsigned, GR_TAB_LOOKAHEAD> LdsCoef;      // out of a cache slot
+    typedef CoefStream<const double2_t __attribute__((address_space(3)))*, unsigned, kTabLookahead> LdsCoef;      // out of a cache slot
     // ... out of the table in global memory (tab_rhs_from_global): memory latency is ten times the LDS's, and the lanes that take
     // this path are few and often alone in their wave -- twice the look-ahead
     // (an address-space-1 pointer: through a generic one the loads are flat_load's, which count on the LDS counter as well and
     // return out of order there -- every wait for one of them then waits for all of them, and the look-ahead is gone)
-    typedef CoefStream<const double2_t __attribute__((address_space(1)))*, unsigned long long, GR_TAB_LOOKAHEAD_GLOBAL> GlobalCoef;
+    typedef CoefStream<const double2_t __attribute__((address_space(1)))*, unsigned long long, kTabLookaheadGlobal> GlobalCoef;
 #endif
     // components and Jacobian from a coefficient source: the polynomials, the chain rule, the axis forms
     // (ax: this lane's row of the axis terms, read in form 2 only)
@@ -2286,9 +2188,7 @@ template <int ID> struct MetricOf { typedef GenericMetricT<ID> type; };
 template <> struct MetricOf<GR_METRIC_KERR> { typedef KerrFamily<false> type; };
 template <> struct MetricOf<GR_METRIC_KERR_NEWMAN> { typedef KerrFamily<true> type; };
 template <> struct MetricOf<GR_METRIC_JOHANNSEN> { typedef JohannsenMetric type; };
-#if GR_HAS_TABULATED
 template <> struct MetricOf<GR_METRIC_TABULATED> { typedef TabulatedMetric type; };
-#endif
 
 // does a metric want (r, θ) instead of (r, sin θ, cos θ)?  (TabulatedMetric)
 template <class Metric, class = void>
@@ -2343,12 +2243,10 @@ template <class Metric>
 GR_DEV void geodesic_rhs_sc(const Metric& m, real r, real s, real c, real vt, real vr, real vh, real vp,
                             real& at, real& ar, real& ah, real& ap)
 {
-#ifndef GR_NO_FUSED_RHS
     if constexpr (Metric::kFusedRhs) {
         m.rhs(r, s, c, vt, vr, vh, vp, at, ar, ah, ap);
         return;
     }
-#endif
     geodesic_rhs_generic(m, r, s, c, vt, vr, vh, vp, at, ar, ah, ap);
 }
 
@@ -2563,10 +2461,7 @@ struct Cold {
 };
 
 // the error norm's scaled residuals in single precision: the fp64 device kernels only (see Ray::step)
-#ifndef GR_NORM_F32
-#define GR_NORM_F32 1
-#endif
-#if GR_NORM_F32 && !defined(GR_REAL_IS_FLOAT) && !defined(GR_REAL_IS_TAN2)
+#if !defined(GR_REAL_IS_FLOAT) && !defined(GR_REAL_IS_TAN2)
 #define GR_NORM_F32_ON 1
 #else
 #define GR_NORM_F32_ON 0
@@ -2792,67 +2687,29 @@ GR_DEV real redshift_pf(const Metric& m, const Params& pp, const Cold& p, const 
 // stage accelerations; the rest of the ray -- t, dt, x^t, x^ϕ, the disc condition at the step's start, the controller's
 // memory and the counters -- is touched before and after it only.  At the register budget of three waves per SIMD
 // (168 VGPRs) the compiler spilled into scratch (56-88 B per lane, HBM-backed: 44-60 MB of write-back per launch).  A
-// lane-private LDS slot costs neither HBM traffic nor a VALU instruction: the cold values are parked at the top of
-// step() and reloaded behind the last right-hand side (9 ds_write_b64 + 9 ds_read_b64 per step on a unit that is
-// otherwise idle; 72 B per lane = 4.6 KB per wave of the CU's 160 KB).  NoColdStore keeps everything in registers
-// (host harness, tangent flavour, k_trace_path).
+// lane-private LDS slot costs neither HBM traffic nor a VALU instruction: the cold values are parked around the event
+// sampling, the rarely taken block that needs a dozen registers of its own (9 ds_write_b64 + 9 ds_read_b64 on a unit that
+// is otherwise idle; 72 B per lane = 4.6 KB per wave of the CU's 160 KB; which kernels: ColdSel, gr_kernels.hpp).
+// NoColdStore keeps everything in registers (host harness, tangent flavour, k_trace_path).
 // ---------------------------------------------------------------------------------------
 constexpr int COLD_SLOTS = 9;      // 8-byte slots per lane
 struct NoColdStore {
     static constexpr bool kOn = false;
-    static constexpr bool kHead = false;
-    static constexpr int kParkA = 0;
     static constexpr bool kTabLds = false;      // (a tabulated metric's patch cache: TabLds below)
 };
-template <bool HEAD>
-struct LdsColdStoreT {
+struct LdsColdStore {
     static constexpr bool kTabLds = false;
     static constexpr bool kOn = true;       // parked around the event sampling (the rarely taken branch)
-    static constexpr bool kHead = HEAD;     // ... and across the whole hot region of every step
-    static constexpr int kParkA = 0;        // (stage accelerations: ParkA below)
     static constexpr int kStride = 64;     // one wave per region: slot k of the wave's lanes is one conflict-free 512-byte row,
                                            // and k * 512 is an immediate offset of the ds instruction (no address arithmetic)
     double* lane;        // this lane's slot 0 inside its wave's region; slot k is lane[k * 64]
     template <class T> GR_DEV void st(int k, T v) const { *reinterpret_cast<T*>(lane + k * kStride) = v; }
     template <class T> GR_DEV T ld(int k) const { return *reinterpret_cast<const T*>(lane + k * kStride); }
-    GR_DEV void st2(int k, int32_t a, int32_t b) const
-    {
-        reinterpret_cast<int32_t*>(lane + k * kStride)[0] = a;
-        reinterpret_cast<int32_t*>(lane + k * kStride)[1] = b;
-    }
-    GR_DEV void ld2(int k, int32_t& a, int32_t& b) const
-    {
-        a = reinterpret_cast<const int32_t*>(lane + k * kStride)[0];
-        b = reinterpret_cast<const int32_t*>(lane + k * kStride)[1];
-    }
     // the compiler may neither forward a parked value to its reload nor move the accesses into the hot region
     static GR_DEV void fence()
     {
 #ifndef GR_HOST_HARNESS
         asm volatile("" ::: "memory");
-#endif
-    }
-};
-typedef LdsColdStoreT<true> LdsColdStore;
-typedef LdsColdStoreT<false> LdsColdStoreRare;
-
-// STAGE ACCELERATIONS PARKED IN LDS (round 4).  A[1..5] are written once per stage and read only by the sums of the later
-// stages, the error estimate and the dense output -- never inside a right-hand side, which is where the register pressure
-// peaks.  With ParkA<Base, N> the accelerations of stages 1..N leave for LDS as soon as they are formed (Ray::step, GR_PARK) and
-// come back, behind a compiler fence, where a sum is about to read them (GR_UNPARK): no value of A[1..N] is alive across a
-// right-hand side.  N x 4 scalars per lane: 32 B per stage for the fp64 kernels (Johannsen: 3 stages = 6 KB per wave, 72 KB per
-// CU at three waves per SIMD), 64 B for the tangent build's (value, ∂) pairs (4 stages = 16 KB per wave, 128 KB at two).
-// Element (q, i) of the wave is 64 consecutive scalars: one conflict-free ds_read / ds_write per element.
-template <class Base, int NPARK>
-struct ParkA : Base {
-    static constexpr int kParkA = NPARK;
-    real* park;          // this lane's element (1, 0); element (q, i) is park[((q - 1) * 4 + i) * 64]
-    GR_DEV void stA(int q, int i, real v) const { park[((q - 1) * 4 + i) * 64] = v; }
-    GR_DEV real ldA(int q, int i) const { return park[((q - 1) * 4 + i) * 64]; }
-    static GR_DEV void park_fence()
-    {
-#ifndef GR_HOST_HARNESS
-        asm volatile("" ::: "memory");      // no forwarding of a parked value to its reload, no reload hoisted above a right-hand side
 #endif
     }
 };
@@ -2885,12 +2742,8 @@ struct Ray {
     hreal dt, h;      // proposed step, last used step
     real cprev;       // disc condition at x
     real sth, cth;    // sin θ, cos θ at x (base of the stage rotations)
-    RotK rotk;        // register-resident constants of the stage rotations
-#ifdef GR_CONTROLLER_F64
-    double lq_old;      // log2(qold)
-#else
+    RotK rotk;        // unread (see RotK)
     float lq_old;       // log2(qold)
-#endif
     int32_t ev_top;     // upper bracket j of Θ = j/7 when an event is pending
     int64_t j;          // local (swizzled) ray index
     int32_t status, flags;      // flags: GR_FLAG_* | RAY_EVENT in bits 0..15, TraceWindings count in bits 16..31
@@ -3461,13 +3314,8 @@ struct Ray {
             const real dm = GR_FMAX(d1, d2);
             // 10^(-(2 + log10 dm)/5) = 10^-0.4 dm^-0.2 ; single-precision hardware log2/exp2 is ample
             // for a starting step size
-#ifdef GR_CONTROLLER_F64
-            const real dt1 = (dm <= 1e-15) ? GR_FMAX(1e-6, dt0 * 1e-3)
-                                             : 0.39810717055349726 * (real)::exp2(-0.2 * ::log2((double)dm));
-#else
             const real dt1 = (dm <= 1e-15) ? GR_FMAX(1e-6, dt0 * 1e-3)
                                              : 0.39810717055349726 * (real)fast_exp2f(-0.2f * fast_log2f((float)dm));
-#endif
             dt = (hreal)GR_FMIN(GR_FMIN(100.0 * dt0, dt1), dtmax);
         }
     }
@@ -3504,33 +3352,8 @@ struct Ray {
         h = hh;
         const hreal h2 = hh * hh;
         const bool resync = (nacc & 63) == 63;      // full sin/cos at the new state (decided while nacc is in a register)
-        if constexpr (Cold_::kHead) {
-            // park what the hot region does not read (see LdsColdStore)
-            cs.template st<real>(0, t);
-            cs.template st<real>(1, dt);
-            cs.template st<real>(2, x[0]);
-            cs.template st<real>(3, x[3]);
-            cs.template st<real>(4, cprev);
-            cs.st2(5, status, flags);
-            cs.st2(6, nacc, nrej);
-            cs.st2(7, ev_top, __builtin_bit_cast(int32_t, (float)lq_old));
-            cs.template st<int64_t>(8, j);
-            Cold_::fence();
-        }
 
         real s, c;
-        // stage accelerations parked in LDS (ParkA): store A[S] behind its right-hand side, reload A[1..UPTO] where sums read them
-#define GR_PARK(S)                                                                             \
-    if constexpr (Cold_::kParkA >= (S)) {                                                      \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) cs.stA((S), i_, A[(S)][i_]);          \
-        Cold_::park_fence();                                                                   \
-    }
-#define GR_UNPARK(UPTO)                                                                        \
-    if constexpr (Cold_::kParkA > 0) {                                                         \
-        Cold_::park_fence();                                                                   \
-        _Pragma("unroll") for (int q_ = 1; q_ <= ((UPTO) < Cold_::kParkA ? (UPTO) : Cold_::kParkA); ++q_)   \
-            _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) A[q_][i_] = cs.ldA(q_, i_);       \
-    }
 #ifdef GR_REAL_IS_TAN2
 #define GR_PIN4(a) { gr_t_pin((a)[0]); gr_t_pin((a)[1]); gr_t_pin((a)[2]); gr_t_pin((a)[3]); }     // see gr_t_pin
 #else
@@ -3538,7 +3361,7 @@ struct Ray {
 #endif
         // stages 2..6: arguments need r, θ and the four velocities only (the RHS does not
         // depend on t or ϕ)
-#if GR_PK_F32
+#ifdef GR_REAL_IS_FLOAT
 #define GR_STAGE_VSUM(S)                                                                              \
         _Pragma("unroll") for (int i = 0; i < 4; i += 2)                                              \
         {                                                                                             \
@@ -3558,7 +3381,6 @@ struct Ray {
 #endif
 #define GR_STAGE(S)                                                                                   \
     {                                                                                                 \
-        GR_UNPARK((S) - 1)                                                                            \
         real vs[4];                                                                                 \
         const hreal ha = Ts::A[S][0] * hh;                                                          \
         GR_STAGE_VSUM(S)                                                                              \
@@ -3575,7 +3397,7 @@ struct Ray {
             rs = GR_FMA(h2a, ar, rs);                                                          \
             ts = GR_FMA(h2a, at, ts);                                                          \
         }                                                                                             \
-        sincos_rot_stage(rotk, x[2], sth, cth, ts, s, c);                                             \
+        sincos_rot_stage(x[2], sth, cth, ts, s, c);                                                   \
         GR_DBG_BIT((GR_FABS(ts - x[2]) <= SINCOS_ROT_MAX) ? 0 : (1 << S));                                    \
         GR_DBG_DMAX(GR_FABS(ts - x[2]));                                                              \
         if constexpr (ByThetaOf<Metric>::value)                                                       \
@@ -3583,7 +3405,6 @@ struct Ray {
         else                                                                                          \
         geodesic_rhs_sc(m, rs, s, c, vs[0], vs[1], vs[2], vs[3], A[S][0], A[S][1], A[S][2], A[S][3]); \
         GR_PIN4(A[S]);                                                                                \
-        GR_PARK(S)                                                                                    \
     }
         GR_STAGE(1)
         GR_STAGE(2)
@@ -3593,13 +3414,11 @@ struct Ray {
 #undef GR_STAGE
 #undef GR_STAGE_VSUM
         // stage 7 argument = the new state.  Its right-hand side reads r, θ and the velocities; t and ϕ of the new state are
-        // formed behind it (their old values are parked when the cold store is on)
+        // formed behind it
         real xn[4], vn[4];
-        GR_UNPARK(5)
         const hreal ha6 = Ts::A[6][0] * hh, hc6 = TsD::X.C[6] * hh, h2a6 = TsD::X.AX[6][0] * h2;
-#if GR_PK_F32
+#ifdef GR_REAL_IS_FLOAT
         // (all four positions here, in pairs: t and ϕ of the new state then live across the last right-hand side -- two registers)
-        static_assert(Cold_::kParkA == 0 && !Cold_::kHead, "the packed sums keep the whole state in registers");
 #pragma unroll
         for (int i = 0; i < 4; i += 2) {
             gr_f2 acc = GR_PK2(A[0], i), ax = GR_PK2(A[0], i);
@@ -3629,45 +3448,20 @@ struct Ray {
     }
         GR_NEW_POSITION(1)
         GR_NEW_POSITION(2)
-        if constexpr (Cold_::kParkA > 0) {      // t and ϕ of the new state while the parked accelerations are here
-            GR_NEW_POSITION(0)
-            GR_NEW_POSITION(3)
-        }
 #endif
         // sin/cos at the new state by rotating the step's base as well (the RHS at the new state is stage 7 and the
         // base of the next step).  Rotation errors random-walk by ~1 ulp per step, so the base is re-synchronised
         // with a full evaluation every 64 accepted steps (and whenever the rotation falls back to it anyway).
         real sn, cn;
-#ifndef GR_NO_ROT_FINAL
         GR_DBG_DMAX(GR_FABS(xn[2] - x[2]));
         if (resync) sincos_fast(xn[2], sn, cn);
-        else sincos_rot(rotk, x[2], sth, cth, xn[2], sn, cn);
+        else sincos_rot(x[2], sth, cth, xn[2], sn, cn);
         if constexpr (ByThetaOf<Metric>::value) geodesic_rhs_th(m, cs, xn[1], xn[2], sn, cn, vn[0], vn[1], vn[2], vn[3], A[6][0], A[6][1], A[6][2], A[6][3]);
         else geodesic_rhs_sc(m, xn[1], sn, cn, vn[0], vn[1], vn[2], vn[3], A[6][0], A[6][1], A[6][2], A[6][3]);
         GR_PIN4(A[6]);
-#else
-        accel(m, xn[1], xn[2], vn, A[6], sn, cn);
-#endif
-        if constexpr (Cold_::kHead) {
-            Cold_::fence();
-            t = cs.template ld<real>(0);
-            dt = cs.template ld<real>(1);
-            x[0] = cs.template ld<real>(2);
-            x[3] = cs.template ld<real>(3);
-            cprev = cs.template ld<real>(4);
-            cs.ld2(5, status, flags);
-            cs.ld2(6, nacc, nrej);
-            int32_t lqb;
-            cs.ld2(7, ev_top, lqb);
-            lq_old = __builtin_bit_cast(float, lqb);
-            j = cs.template ld<int64_t>(8);
-        }
-        if constexpr (Cold_::kParkA == 0) {
-            GR_NEW_POSITION(0)
-            GR_NEW_POSITION(3)
-        }
+        GR_NEW_POSITION(0)
+        GR_NEW_POSITION(3)
 #undef GR_NEW_POSITION
-        GR_UNPARK(5)          // the error estimate reads every stage
 
         // error estimate, squared RMS norm over all eight components: ũ_v = h Σ b̃_q A_q, ũ_x = h (Σb̃ · v + h Σ b̄_i A_i);
         // the common factor h² and the 1/8 of the mean are applied once to the sum.
@@ -3687,7 +3481,7 @@ struct Ray {
         double e2n = 0.0;
 #endif
         const hreal hbx = TsD::X.BTX[0] * hh;
-#if GR_PK_F32
+#ifdef GR_REAL_IS_FLOAT
         real ev4[4], ex4[4];
 #pragma unroll
         for (int i = 0; i < 4; i += 2) {
@@ -3700,8 +3494,6 @@ struct Ray {
             ev4[i] = ev2.x; ev4[i + 1] = ev2.y;
             ex4[i] = ex2.x; ex4[i + 1] = ex2.y;
         }
-#endif
-#if GR_PK_F32
         // ... and the scaled residuals of the pairs: scale = reltol max(|u0|, |u1|) + abstol, residual / scale, squares summed -- packed
         // FMA / MUL around two scalar reciprocals
         {
@@ -3722,9 +3514,6 @@ struct Ray {
 #else
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-#if GR_PK_F32
-            const real ev = ev4[i], ex = ex4[i];
-#else
             real ev = A[0][i];               // ũ_v / (h b̃_0)
 #pragma unroll
             for (int q = 1; q < 7; ++q) ev = GR_FMA(TsD::X.BTR[q], A[q][i], ev);
@@ -3732,7 +3521,6 @@ struct Ray {
 #pragma unroll
             for (int q = 1; q < 6; ++q) ex = GR_FMA(TsD::X.BTXR[q], A[q][i], ex);
             ex = GR_FMA(hbx, ex, TsD::X.SBT * v[i]);
-#endif
 #ifdef GR_REAL_IS_TAN2
             if (p.tangent_norm) {
                 // The reference integrates Dual state through OrdinaryDiffEq (precision-solvers.jl:73-131,401-451) and
@@ -3753,7 +3541,7 @@ struct Ray {
             }
 #endif
 #if GR_NORM_F32_ON
-            // The scaled residuals in SINGLE precision (round 4; -DGR_NORM_F32=0 restores the FP64 form): one v_cvt_f32_f64 per
+            // The scaled residuals in SINGLE precision (round 4; the tangent build keeps the FP64 form below): one v_cvt_f32_f64 per
             // operand, then v_fma_f32 / v_rcp_f32 / v_mul_f32 instead of 2 FMA + 2 quarter-rate v_rcp_f64 + 2 MUL + 2 FMA in FP64
             // per component -- 809 -> 776 FP64 instructions per step, 18.20 -> 17.93 ms interleaved on one box
             // (profiles/r4h_ab_normf32.txt).  The quotient feeds a controller that works in single precision anyway (and whose
@@ -3794,30 +3582,15 @@ struct Ray {
         // PI controller in log2 space: q = EEst^β1 / qold^β2 / γ.  The step factor is formed with
         // single-precision hardware log2/exp2 (relative error ~1e-6 in dt, far below anything the
         // 1e-9 tolerance can see; the reference's DiffEqBase.fastpow is itself Float32-based).
-        // GR_CONTROLLER_F64 builds the same controller on double-precision log2/exp2 (A/B of the disc-rim
-        // classification against the oracle, scripts/controller_ab.py).
-#ifdef GR_CONTROLLER_F64
-        typedef double ctl_t;
-#define GR_CTL_LOG2(x) ::log2((double)(x))
-#define GR_CTL_EXP2(x) ::exp2((double)(x))
-#define GR_CTL_MIN(a, b) ::fmin((double)(a), (double)(b))
-#define GR_CTL_MAX(a, b) ::fmax((double)(a), (double)(b))
-#else
-        typedef float ctl_t;
-#define GR_CTL_LOG2(x) fast_log2f((float)(x))
-#define GR_CTL_EXP2(x) fast_exp2f((float)(x))
-#define GR_CTL_MIN(a, b) ::fminf((float)(a), (float)(b))
-#define GR_CTL_MAX(a, b) ::fmaxf((float)(a), (float)(b))
-#endif
-        const ctl_t lE = (ctl_t)0.5 * GR_CTL_LOG2(e2);       // log2(EEst); -inf when e2 underflows
+        const float lE = 0.5f * fast_log2f((float)(e2));       // log2(EEst); -inf when e2 underflows
         if (e2 <= 1.0) {
             // dt_next = dt / q with q = clamp(EEst^β1 / qold^β2 / γ, 1/qmax, 1/qmin): formed directly as the growth factor
             // 1/q = clamp(γ 2^(β2 log2 qold - β1 log2 EEst), qmin, qmax), so the accepted step needs no reciprocal
             // (round 2 clamped q and then divided: one v_rcp_f64, four Newton FMAs and a conversion more per step)
-            ctl_t gf = GR_CTL_EXP2((ctl_t)PI_BETA2 * (ctl_t)lq_old - (ctl_t)PI_BETA1 * lE) * (ctl_t)PI_GAMMA;
-            gf = GR_CTL_MIN((ctl_t)PI_QMAX, GR_CTL_MAX((ctl_t)PI_QMIN, gf));   // e2 == 0 -> lE = -inf -> qmax
+            float gf = fast_exp2f((float)PI_BETA2 * lq_old - (float)PI_BETA1 * lE) * (float)PI_GAMMA;
+            gf = ::fminf((float)PI_QMAX, ::fmaxf((float)PI_QMIN, gf));   // e2 == 0 -> lE = -inf -> qmax
             nacc++;
-            lq_old = GR_CTL_MAX(lE, (ctl_t)LOG2_QOLDINIT);
+            lq_old = ::fmaxf(lE, (float)LOG2_QOLDINIT);
             hreal dtnew = hh * (hreal)gf;
             real tnew = t + hh;
             if (GR_FABS(tnew - tend) < 100.0 * GR_EPS * GR_FMAX(GR_FABS(tnew), GR_FABS(tend))) tnew = tend;
@@ -3836,10 +3609,7 @@ struct Ray {
                 }
                 int top = 0;
                 int32_t mask = 0;
-                if (__builtin_popcount((unsigned)mask_end) != K) {
-                    GR_UNPARK(5)
-                    top = sample_event_composite(p, hh, mask);
-                }
+                if (__builtin_popcount((unsigned)mask_end) != K) top = sample_event_composite(p, hh, mask);
                 if (!top && mask_end) { top = 7; mask = mask_end; }
                 if (top) {
                     flags |= RAY_EVENT;
@@ -3875,7 +3645,6 @@ struct Ray {
                             cs.template st<real>(8, t);
                             Cold_::fence();
                         }
-                        GR_UNPARK(5)          // the dense output reads the member array
                         top = sample_event(p, pos ? 1 : -1, hh);
                         if constexpr (Cold_::kOn) {
                             Cold_::fence();
@@ -3974,16 +3743,10 @@ struct Ray {
                 return true;
 #endif
             }
-            const ctl_t q11 = GR_CTL_EXP2((ctl_t)PI_BETA1 * lE);
-            dt = hh / (hreal)GR_CTL_MIN((ctl_t)(1.0 / PI_QMIN), q11 * (ctl_t)(1.0 / PI_GAMMA));
+            const float q11 = fast_exp2f((float)PI_BETA1 * lE);
+            dt = hh / (hreal)::fminf((float)(1.0 / PI_QMIN), q11 * (float)(1.0 / PI_GAMMA));
             return false;
         }
-#undef GR_CTL_LOG2
-#undef GR_CTL_EXP2
-#undef GR_CTL_MIN
-#undef GR_CTL_MAX
-#undef GR_PARK
-#undef GR_UNPARK
     }
 
 #if GR_HAS_MESH && !defined(GR_HOST_HARNESS)
@@ -4001,7 +3764,8 @@ struct Ray {
             // the other ~q (c / 64 + a few) rounds.  Measured on a ring slab of 960 / 3840 triangles at 1024², by wave up to
             // q = 0 / 2 / 8 / 16 / 32 / 64: 11.4 / 10.1 / 9.4 / 9.1 / 10.7 / 17.7 ms and 25.0 / 22.4 / 18.2 / 15.7 / 14.4 / 24.7 ms
             // (a rule that also counts the candidates first costs more than it finds: 9.9 and 16.7-18.0 ms)
-            const bool by_wave = __popcll(due) <= GR_MESH_WAVE_MAX;
+            constexpr int kMeshWaveMax = 16;      // tests due in one wave up to which the wave takes them one by one
+            const bool by_wave = __popcll(due) <= kMeshWaveMax;
             if (!by_wave) {
                 if (need) hit = mesh_lane_query(p, qprev, qnew);
             } else {
@@ -4262,20 +4026,9 @@ struct Ray {
     }
 
     // unpack_solution + apply_to_image!
-    GR_DEV void finalize(const Metric& m, const Params& p, const LdsView& lds) { finalize(m, p, lds, NoColdStore{}); }
-
-    template <class Cold_>
-    GR_DEV void finalize(const Metric& m, const Params& p, const LdsView& lds, const Cold_& cs)
+    GR_DEV void finalize(const Metric& m, const Params& p, const LdsView& lds)
     {
         if (kContinuous && (flags & RAY_EVENT)) {
-            if constexpr (Cold_::kParkA > 0) {
-                // the event step's accelerations of stages 1..kParkA are still where step() parked them
-                Cold_::park_fence();
-#pragma unroll
-                for (int q_ = 1; q_ <= Cold_::kParkA; ++q_)
-#pragma unroll
-                    for (int i_ = 0; i_ < 4; ++i_) A[q_][i_] = cs.ldA(q_, i_);
-            }
             resolve_event(p);
             flags &= ~RAY_EVENT;
         }

@@ -41,80 +41,41 @@ struct LaneStats {
 #ifndef GR_HOST_HARNESS
 extern __shared__ double gr_lds[];
 
-// Cold lane storage (gr_device.hpp, LdsColdStoreT): LDS as the place for what a block of the step does not read.
-//   GR_COLD_LDS = 3 (default): around the EVENT SAMPLING only (taken in ~2 % of the wave-steps), for the metrics that run at
-//                 the 168-register cap (Metric::kColdRare: Kerr).  The sampling block needs a dozen registers of its own; left to
-//                 the compiler they are made by spilling to scratch, whose write-back was 113 of the 147 MB the bench kernel
-//                 sent to HBM per launch.  Parked in LDS instead: 50.7 MB written (1.5 x the 33.6 MB image), same time
-//                 (19.22 vs 19.19 ms, profiles/r3h_*).
-//   GR_COLD_LDS = 2: the same for every metric;  1: additionally across the hot region of EVERY step (the round-3 instrument
-//                 that attributed the write excess: no scratch at all, +1.3 % time, 1.7 % on Johannsen);  0: off.
-// The tangent scalar and the fp64-controller build do not fit the 8-byte slots: off there.
-#ifndef GR_COLD_LDS
-#if defined(GR_REAL_IS_TAN2) || defined(GR_CONTROLLER_F64)
-#define GR_COLD_LDS 0
-#else
-#define GR_COLD_LDS 3
-#endif
-#endif
-#if GR_COLD_LDS && (defined(GR_REAL_IS_TAN2) || defined(GR_CONTROLLER_F64))
-#error "the cold lane storage is written for the fp64 / fp32 scalars and the fp32 controller"
-#endif
+// Cold lane storage (gr_device.hpp, LdsColdStore): LDS as the place for what the EVENT SAMPLING (taken in ~2 % of the
+// wave-steps) does not read, for the metrics that run at the 168-register cap (Metric::kColdRare: Kerr).  The sampling block
+// needs a dozen registers of its own; left to the compiler they are made by spilling to scratch, whose write-back was 113 of
+// the 147 MB the bench kernel sent to HBM per launch.  Parked in LDS instead: 50.7 MB written (1.5 x the 33.6 MB image), same
+// time (19.22 vs 19.19 ms, profiles/r3h_*).  The tangent scalar does not fit the 8-byte slots: off there.
 template <class Metric, class = void>
 struct ColdRareOf { static constexpr bool value = false; };
 template <class Metric>
 struct ColdRareOf<Metric, decltype((void)Metric::kColdRare)> { static constexpr bool value = Metric::kColdRare; };
 
-// How many stage accelerations the one-ray-per-lane kernel of a metric parks in LDS (ParkA, gr_device.hpp): Metric::kParkStages,
-// GR_PARK_STAGES overrides it for every metric of a build (the tangent objects: 4)
-template <class Metric, class = void>
-struct ParkStagesOf { static constexpr int value = 0; };
-template <class Metric>
-struct ParkStagesOf<Metric, decltype((void)Metric::kParkStages)> { static constexpr int value = Metric::kParkStages; };
-
 template <class Metric, bool LANE_KERNEL = true>      // the persistent kernel runs below the register cap: nothing to park
 struct ColdSel {
-#if GR_COLD_LDS == 1
-    typedef LdsColdStore base;
-#elif GR_COLD_LDS == 2
-    typedef LdsColdStoreRare base;
-#elif GR_COLD_LDS == 3
-    typedef typename std::conditional<LANE_KERNEL && ColdRareOf<Metric>::value, LdsColdStoreRare, NoColdStore>::type base;
-#else
+#ifdef GR_REAL_IS_TAN2
     typedef NoColdStore base;
-#endif
-#ifdef GR_PARK_STAGES
-    static constexpr int kPark = LANE_KERNEL ? GR_PARK_STAGES : 0;
 #else
-    static constexpr int kPark = LANE_KERNEL ? ParkStagesOf<Metric>::value : 0;
+    typedef typename std::conditional<LANE_KERNEL && ColdRareOf<Metric>::value, LdsColdStore, NoColdStore>::type base;
 #endif
-    typedef typename std::conditional<(kPark > 0), ParkA<base, kPark>, base>::type type0;
     // a tabulated metric's patch cache (TabLds): kTabLdsBytesPerWave bytes per wave behind every other LDS region
-    static constexpr bool kTab = ByThetaOf<Metric>::value && GR_HAS_TABULATED;
-    typedef typename std::conditional<kTab, TabLds<type0>, type0>::type type;
-    static constexpr size_t kColdBytes = base::kOn ? sizeof(double) * COLD_SLOTS : 0;
-    static constexpr size_t kParkBytes = sizeof(real) * 4 * (size_t)kPark;
-    static constexpr size_t kBytesPerThread = kColdBytes + kParkBytes;
-#if GR_HAS_TABULATED
+    static constexpr bool kTab = ByThetaOf<Metric>::value;
+    typedef typename std::conditional<kTab, TabLds<base>, base>::type type;
+    static constexpr size_t kBytesPerThread = base::kOn ? sizeof(double) * COLD_SLOTS : 0;
     static constexpr size_t kTabBytesPerWave = kTab ? kTabLdsBytesPerWave : 0;
-#else
-    static constexpr size_t kTabBytesPerWave = 0;
-#endif
 };
 // wave w of the workgroup owns bytes [w * 64 * kBytesPerThread, (w + 1) * 64 * kBytesPerThread) of the region behind the
-// histogram and the plunging table: its cold slots first (64 lanes x COLD_SLOTS doubles), then its parked accelerations
+// histogram and the plunging table: 64 lanes x COLD_SLOTS doubles
 template <class Sel>
 __device__ __forceinline__ typename Sel::type cold_store_of(const Params& p)
 {
     typedef typename Sel::type Store;
     Store st{};
-    if constexpr (Store::kOn || Store::kParkA > 0) {
+    if constexpr (Store::kOn) {
         const unsigned w = threadIdx.x >> 6, l = threadIdx.x & 63;
         char* region = reinterpret_cast<char*>(gr_lds + p.lds_bins + 4 * p.lds_plunge_rows) + (size_t)w * (64 * Sel::kBytesPerThread);
-        if constexpr (Store::kOn) st.lane = reinterpret_cast<double*>(region) + l;
-        if constexpr (Store::kParkA > 0) st.park = reinterpret_cast<real*>(region + 64 * Sel::kColdBytes) + l;
+        st.lane = reinterpret_cast<double*>(region) + l;
     }
-#if GR_HAS_TABULATED
     if constexpr (Store::kTabLds) {
         // the patch cache of wave w: p.lds_tab_off bytes into the workgroup's LDS (launch_tmpl), empty to begin with
         typedef char __attribute__((address_space(3))) lds_char;
@@ -137,7 +98,6 @@ __device__ __forceinline__ typename Sel::type cold_store_of(const Params& p)
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
-#endif
     return st;
 }
 
@@ -297,7 +257,7 @@ __global__ void __launch_bounds__(256, GR_LANE_MIN_WAVES) k_trace_lane(const Par
         __builtin_amdgcn_wave_barrier();
         if (gid < p.n) {
             GR_PARAMS_AFTER_LOOP(p, pl, zoff)
-            ray.finalize(m, pl, lds, cs);
+            ray.finalize(m, pl, lds);
             ls.add(ray);
 #ifdef GR_WAVE_TIMELINE
             tl_steps = ray.nacc + ray.nrej;
@@ -318,7 +278,7 @@ __global__ void __launch_bounds__(256, GR_LANE_MIN_WAVES) k_trace_lane(const Par
         // per-lane exit block.  It emits no instruction.
         __builtin_amdgcn_wave_barrier();
         GR_PARAMS_AFTER_LOOP(p, pl, zoff)
-        ray.finalize(m, pl, lds, cs);
+        ray.finalize(m, pl, lds);
         if constexpr (ColdSel<Metric>::kTab && LANES_PER_RAY_LOG2 == 0) {
             // A tabulated metric: what a tile costs is how long its wave lived, not how many steps its rays took -- a wave at
             // the shadow's edge, its lanes in a dozen different patches, spends 4x the time per step of one inside a single patch
@@ -494,10 +454,8 @@ hipError_t launch_tmpl(const LaunchKnobs& k, Params& p, hipStream_t stream)
 {
     const int block = k.block;
     if (k.kernel != 0) p.lds_points = 0;     // the persistent kernel refills lanes one by one: no wave-wide moment to send records
-    // a kernel that parks its stage accelerations in LDS (10 KB per wave) leaves the plunging table in L2: twelve one-wave
-    // workgroups per CU cannot each hold a copy as well (staged and L2-served look-ups measured equal, gradus_mi355x.hip)
-    if (k.kernel == 0 && ColdSel<Metric, true>::kPark > 0) p.lds_plunge_rows = 0;
-    // (so does a tabulated metric: its LDS is the patch cache, 18 KB per wave)
+    // a tabulated metric leaves the plunging table in L2: its LDS is the patch cache, 18 KB per wave (staged and L2-served
+    // look-ups measured equal, gradus_mi355x.hip)
     if (ColdSel<Metric, true>::kTab) p.lds_plunge_rows = 0;
     const size_t cold_b = (k.kernel == 0 ? ColdSel<Metric, true>::kBytesPerThread : ColdSel<Metric, false>::kBytesPerThread) * (size_t)block;
     const size_t point_b = p.lds_points ? kPointLdsBytesPerThread * (size_t)block : 0;

@@ -29,8 +29,8 @@
 //               with it against 1.55 s -- and 24.5 ms against 20.9 for the 1024² launch, where the value part computed
 //               twice costs more than the shorter chain saves.
 // The host unit picks per launch (gr_ctx_set "tangent_pairs": launches that cannot fill the SIMDs anyway take the pairs).
-// A 256-register variant of the pair shape (two waves per SIMD, stage accelerations parked in LDS: -DGR_TAN_MIN_WAVES=2
-// -DGR_PARK_STAGES=4) was measured and lost to both (24.5 ms; 1.31 s).
+// A 256-register variant of the pair shape (two waves per SIMD, stage accelerations parked in LDS) was measured and lost
+// to both (24.5 ms; 1.31 s).
 #define GR_REAL_IS_TAN2 1
 #if defined(GR_TU_TAN1)
 #define GR_TAN_W 1
@@ -42,13 +42,7 @@
 #define GR_TU_PREFIX grt
 #endif
 #define GR_LANE_ONLY 1
-#ifndef GR_TAN_MIN_WAVES
-#define GR_TAN_MIN_WAVES 1  // waves per SIMD the tangent kernels are compiled for
-#endif
-#define GR_LANE_MIN_WAVES GR_TAN_MIN_WAVES
-#ifndef GR_PARK_STAGES
-#define GR_PARK_STAGES 0    // stage accelerations parked in LDS while a right-hand side runs (ParkA, gr_device.hpp)
-#endif
+#define GR_LANE_MIN_WAVES 1  // waves per SIMD the tangent kernels are compiled for
 #elif defined(GR_TU_F32)
 #define GR_REAL_IS_FLOAT 1
 #define GR_NS gr32

@@ -12,9 +12,6 @@ cat > /tmp/probe/probe_tan.hip <<EOT
 #define GR_NS grt
 #define GR_LANE_ONLY 1
 #define GR_LANE_MIN_WAVES $MW
-#ifndef GR_PARK_STAGES
-#define GR_PARK_STAGES 0
-#endif
 #define GR_NO_LAUNCHER 1
 #include "$ROOT/gradus.jl_amd/csrc/gr_kernels.hpp"
 using namespace grt;

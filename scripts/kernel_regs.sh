@@ -4,7 +4,7 @@
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TMP=$(mktemp -d)
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -disable-machine-licm --cuda-device-only -DGR_TU_METRIC=${1:-0} \
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -disable-machine-licm -ffp-contract=on --cuda-device-only -DGR_TU_METRIC=${1:-0} \
       -c "$ROOT/gradus.jl_amd/csrc/kernels_tu.hip" -o $TMP/dev.co
 /opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --input=$TMP/dev.co \
       --targets=hip-amdgcn-amd-amdhsa--gfx950 --output=$TMP/dev.elf
