@@ -557,6 +557,29 @@ struct KerrFamily {
         return aE + GR_FMA(aE, a * a, GR_FABS(a * L)) * rcp_full(r * r);
     }
 
+    // Carter's constant of a null geodesic from its state (the start and polar-rate culls, Ray::init / Ray::step):
+    // Q = p_θ² + cos²θ (L²/sin²θ - a²E²), p_θ = Σ v^θ.  On the axis (sin θ = 0) it is inf or NaN: every test on it then fails.
+    GR_DEV real carter_constant(real pth, real s, real c, real E, real L) const
+    {
+        return GR_FMA(c * c, GR_FMA(L * L, rcp_full(s * s), -(a * a) * (E * E)), pth * pth);
+    }
+    // ... and the radial potential with its first two derivatives.  In Mino time dτ = dλ/Σ a null geodesic has (dr/dτ)² = R(r),
+    // (dμ/dτ)² = Θ(μ) for μ = cos θ, with K = Q + (L - aE)² and
+    //   R(r) = [E(r² + a²) - aL]² - Δ K = E² r⁴ + c2 r² + c1 r + c0,   c2 = a²E² - L² - Q,  c1 = 2MK,  c0 = -a²Q,
+    //   Θ(μ) = Q + c2 μ² - a²E² μ⁴.
+    // Returns c2 (the polar bound reads it as well).  (Kerr only: Kerr-Newman never culls.)
+    GR_DEV real radial_potential(real r, real E, real L, real Q, real& R, real& R1, real& R2) const
+    {
+        const real e2 = E * E, lae = L - a * E;
+        const real c2 = GR_FMA(a * a, e2, -GR_FMA(L, L, Q));
+        const real c1 = 2.0 * M * GR_FMA(lae, lae, Q), c0 = -(a * a) * Q;
+        const real e2r2 = e2 * (r * r);
+        R = GR_FMA(r, GR_FMA(r, e2r2 + c2, c1), c0);
+        R1 = GR_FMA(r, GR_FMA(4.0, e2r2, 2.0 * c2), c1);
+        R2 = GR_FMA(12.0, e2r2, 2.0 * c2);
+        return c2;
+    }
+
     // hand-differentiated; one reciprocal for everything
     GR_DEV void eval(real r, real s, real c, real g[5], real gr[5], real gt[5], real gi[5]) const
     {
@@ -2489,9 +2512,13 @@ struct Params {
     int32_t xcd_spread;       // one-ray-per-lane kernel on rays in CALLER order: 1 = workgroup b traces chunk xcd_chunk(b) of the
     int32_t lds_tab_off;      // rays instead of chunk b (gr_kernels.hpp) | byte offset of the tabulated metric's patch caches in the workgroup's LDS
     // escape cull (Ray::step): an outgoing ray beyond this radius whose pixel is already decided ends as if it had
-    // reached λ1.  +inf = off (derive_params): what every launch but launch_trace's gated ones (escape_cull_radius) and the host
-    // harnesses see.  (Last, so that the fields before it keep their kernarg offsets.)
+    // reached λ1, and so does one inside it that provably leaves before it can reach the disc (the polar-rate test).  +inf = off
+    // (derive_params): what every launch but launch_trace's gated ones (escape_cull_radius) and the host harnesses see.  (Last,
+    // so that the fields before it keep their kernarg offsets.)
     double r_cull = __builtin_inf();
+    // start cull (Ray::init): the same radius for the test at the start of a ray -- a ray whose radial turning
+    // point lies outside it is decided before its first step.  A switch of its own: +inf = off, whatever r_cull holds.
+    double r_cull_start = __builtin_inf();
 };
 
 // the derived fields of Params, from cfg (host side; one place for the library and the two host harnesses)
@@ -2504,6 +2531,23 @@ static inline void derive_params(Params& p)
     int64_t mi = p.cfg.maxiters < 0 ? 0 : p.cfg.maxiters;
     p.maxiters32 = (int32_t)(mi > 0x7fffffff ? 0x7fffffff : mi);
     p.r_cull = __builtin_inf();     // the escape cull is off unless the launcher gates it on (escape_cull_radius)
+    p.r_cull_start = __builtin_inf();     // ... and so is the start cull
+}
+
+// The culls' gating radius as far as the configuration decides it (host side; one place for the launcher, escape_cull_radius in
+// gradus_mi355x.hip, which adds the conditions on output and precision, and for the host harness of the culls): one GR_DISC_THIN
+// disc with a finite outer radius and gtol < 1, no hemisphere / chart / winding callback, null rays traced forward, a metric
+// with a finite escape radius (Metric::kEscapeRadiusM, in units of M = params[0]) and |a| <= M.
+// (1 + 1e-6) max(R_esc, r_out / sqrt(1 - gtol²)): outside r_out / sqrt(1 - gtol²) the thin disc's condition is > 0.  +inf = gated off.
+static inline double cull_gate_radius(const gr_config& c, double escape_radius_M)
+{
+    const double off = __builtin_inf();
+    if (c.disc_id != GR_DISC_THIN || c.upper_hemisphere != 0 || c.mu != 0.0 || !(c.lambda1 > c.lambda0)) return off;
+    const double r_esc = escape_radius_M * c.params[0];
+    if (!(r_esc < off) || !(c.params[0] > 0.0) || !(::fabs(c.params[1]) <= c.params[0])) return off;
+    if (!(c.gtol >= 0.0 && c.gtol < 1.0) || !(c.disc_r_out < off)) return off;
+    const double r_disc = c.disc_r_out / ::sqrt(1.0 - c.gtol * c.gtol);
+    return (1.0 + 1e-6) * (r_esc > r_disc ? r_esc : r_disc);
 }
 
 // Small read-mostly tables staged in LDS by the kernel prologue (null = use the global copy):
@@ -3243,8 +3287,37 @@ struct Ray {
         geodesic_rhs(m, r, th, vv[0], vv[1], vv[2], vv[3], a[0], a[1], a[2], a[3], s, c);
     }
 
-    // reinit! + auto_dt_reset! (tracing.jl:234-243; App. A.4)
-    GR_DEV void init(const Metric& m, const Params& p, int64_t jl)
+    // START CULL.  Under the escape cull's gating (step(): a miss leaves nothing behind but NoStatus) a ray is
+    // decided before its first step when its radial turning point lies outside R_cull = Params::r_cull_start:
+    //  1. it starts outside: r0 > R_cull;
+    //  2. R(R_cull) < 0 for the ray's E, L, Q (Metric::radial_potential).  (dr/dτ)² = R(r) >= 0 along the geodesic, so the ray is
+    //     confined to the connected piece of {R >= 0} that holds r0, and R_cull is not in it: r > R_cull for ever, whatever the
+    //     sign of v^r.  The thin disc's condition is <= 0 only at r <= r_out / sqrt(1 - gtol²) <= R_cull (step(), 2), so it stays
+    //     > 0 at every step end and dense-output sample, and the chart's inner boundary is never met;
+    //  3. λ1 comes first: |dr/dλ| <= B(R_cull) at every r >= R_cull (Metric::radial_speed_bound, falling with r), so r stays
+    //     below r0 + B(R_cull)(λ1 - λ0); short of r_outer the full trace ends at λ1 with NoStatus.  If not, the ray is traced.
+    // Margins: R(R_cull) < -1e-6 E² R_cull⁴ -- 1e-6 of the quartic's leading term, which bounds the size of every term of R where
+    // R <= 0.  With R' <= 4 E² r³ there, the turning point then lies at least 2.5e-7 R_cull beyond R_cull, which itself is 1e-6
+    // beyond the disc's reach: the room for the rounding of E, L, Q and R and for the integrator's drift from the exact geodesic
+    // (1e-9 tolerance), as in step().  The bound of 3 carries the same 1e-6 as there.  NaN or inf constants fail the compares.
+    GR_DEV bool start_decided(const Metric& m, const Params& p) const
+    {
+        real s, c, g[5];
+        sincos_fast(x[2], s, c);
+        metric_comps(m, x[1], x[2], s, c, g);
+        const real E = -(g[0] * v[0] + g[4] * v[3]), L = g[4] * v[0] + g[3] * v[3];
+        const real Q = m.carter_constant(g[2] * v[2], s, c, E, L);
+        const real rc = (real)p.r_cull_start, rc2 = rc * rc;
+        real R, R1, R2;
+        m.radial_potential(rc, E, L, Q, R, R1, R2);
+        if (!(R < -1e-6 * ((E * E) * (rc2 * rc2)))) return false;
+        const real reach = GR_FMA(m.radial_speed_bound(rc, E, L), (real)p.cfg.lambda1 - (real)p.cfg.lambda0, x[1]);
+        return reach * (1.0 + 1e-6) < (real)p.cfg.r_outer;
+    }
+
+    // reinit! + auto_dt_reset! (tracing.jl:234-243; App. A.4).  Returns true when the ray is decided without a step (the start
+    // cull: λ = λ1, NoStatus, no steps; finalize() reads nothing else of it under the cull's gating)
+    GR_DEV bool init(const Metric& m, const Params& p, int64_t jl)
     {
         j = jl;
         status = GR_STATUS_NO_STATUS;
@@ -3254,6 +3327,12 @@ struct Ray {
         t = p.cfg.lambda0;
         h = 0.0;
         lq_old = (float)LOG2_QOLDINIT;
+        if constexpr (kEscapeCull) {
+            if (x[1] > (real)p.r_cull_start && start_decided(m, p)) {
+                t = p.cfg.lambda1;
+                return true;
+            }
+        }
         real s, c;
         accel(m, x[1], x[2], v, A[0], s, c);
         sth = s; cth = c;
@@ -3318,6 +3397,7 @@ struct Ray {
                                              : 0.39810717055349726 * (real)fast_exp2f(-0.2f * fast_log2f((float)dm));
             dt = (hreal)GR_FMIN(GR_FMIN(100.0 * dt0, dt1), dtmax);
         }
+        return false;
     }
 
 #ifdef GR_HOST_HARNESS
@@ -3687,6 +3767,9 @@ struct Ray {
             const bool cb_term = discrete_cb(p, xn[1], xn[2], cn, status, flags);
             term |= cb_term;
             if constexpr (DISC == GR_DISC_MESH) mesh_cb_term = cb_term ? 1 : 0;
+            // (the polar-rate cull below: cos θ kept its sign over this step -- compares only, taken before the commit)
+            bool same_side = false;
+            if constexpr (kEscapeCull) same_side = cn > 0.0 ? cth > 0.0 : cth < 0.0;
 #pragma unroll
             for (int i = 0; i < 4; ++i) { x[i] = xn[i]; v[i] = vn[i]; A[0][i] = A[6][i]; }
             sth = sn; cth = cn;
@@ -3711,14 +3794,51 @@ struct Ray {
             // through the test below.  The test sits behind the step's commit, where the fewest values are alive; the common path
             // pays three compares (the flag word holds nothing but RAY_NO_CULL here: GR_FLAG_* and RAY_EVENT end the ray, winding
             // counts come with a callback, under which R_cull is +inf); E, L and B are formed once per ray.
+            //
+            // POLAR-RATE CULL: the same end for an outgoing ray still INSIDE R_cull that provably passes R_cull before it can reach
+            // the disc's wedge |cos θ| <= gtol -- from there on 1-3 above hold.  Asked at every such step (a failure may pass later:
+            // it does not set RAY_NO_CULL) with v^r > 0, R_esc (1 + 1e-6) < r <= R_cull, the disc condition > 0 at both ends of the
+            // step (as in 2) and μ = cos θ of one sign at both ends with |μ| > gtol.  With E, L, Q from the current state, in Mino
+            // time dτ = dλ/Σ, (dr/dτ)² = R(r) and (dμ/dτ)² = Θ(μ) (Metric::radial_potential):
+            //  a. no turning point: R(r) > 0, R'(r) >= 0, R''(r) >= 0.  R'' = 12E²r² + 2c2 rises with r, so R is convex and rising
+            //     on [r, ∞): the ray goes out monotonically and R(r') >= R + R'(r' - r);
+            //  b. it reaches R_cull, d = R_cull - r away, within τ_r = ∫ dr'/sqrt(R(r')) <= ∫ dr'/sqrt(R + R'(r' - r))
+            //     = (2/R')(sqrt(R + R'd) - sqrt(R)) = 2d / (sqrt(R + R'd) + sqrt(R));
+            //  c. it needs at least τ_θ = (|μ| - gtol)/sqrt(T), T = Q + max(0, c2) μ², to reach the wedge: on the way there it
+            //     crosses every |μ'| between gtol and |μ|, where Θ(μ') = Q + c2 μ'² - a²E² μ'⁴ <= T, whichever way θ moves first
+            //     (T <= 0: it never gets there);
+            //  d. so if τ_r (1 + 1e-6) < τ_θ, the condition stays > 0 up to R_cull, the ray is beyond R_cull with v^r > 0, and 1-3
+            //     take over (B of 3 is formed at the smaller r here, where it is larger).  Written without a division:
+            //     2d (1 + 1e-6) sqrt(T) < (|μ| - gtol)(sqrt(R + R'd) + sqrt(R)).
+            // The 1e-6 covers the rounding (sqrt_fast: 1 ulp) and the integrator's drift, as above.  Both bounds are loose by
+            // construction.  A NaN anywhere (the axis: Q = inf) fails a compare.  Nothing is carried from step to step.
             if constexpr (kEscapeCull) {
-                if (cprev > 0.0 && v[1] > 0.0 && x[1] > (real)p.r_cull && (uint32_t)flags < (uint32_t)RAY_NO_CULL) {
-                    real g[5];
-                    metric_comps(m, x[1], x[2], sth, cth, g);
-                    const real E = -(g[0] * v[0] + g[4] * v[3]), L = g[4] * v[0] + g[3] * v[3];
-                    const real reach = GR_FMA(m.radial_speed_bound(x[1], E, L), tend - t, x[1]);
-                    if (reach * (1.0 + 1e-6) < (real)p.cfg.r_outer) t = tend;
-                    else flags |= RAY_NO_CULL;
+                if (cprev > 0.0 && v[1] > 0.0 && (uint32_t)flags < (uint32_t)RAY_NO_CULL) {
+                    const real rc = (real)p.r_cull;
+                    bool out = x[1] > rc;
+                    const bool ask = same_side && rc < (real)__builtin_inf() && x[1] > (real)(Metric::kEscapeRadiusM * (1.0 + 1e-6)) * m.M;
+                    if (out || ask) {
+                        real g[5];
+                        metric_comps(m, x[1], x[2], sth, cth, g);
+                        const real E = -(g[0] * v[0] + g[4] * v[3]), L = g[4] * v[0] + g[3] * v[3];
+                        const real mu = GR_FABS(cth) - (real)p.cfg.gtol;
+                        if (!out && mu > 0.0) {
+                            const real Q = m.carter_constant(g[2] * v[2], sth, cth, E, L);
+                            real R, R1, R2;
+                            const real c2 = m.radial_potential(x[1], E, L, Q, R, R1, R2);
+                            if (R > 0.0 && R1 >= 0.0 && R2 >= 0.0) {
+                                const real d = rc - x[1];
+                                const real T = GR_FMA(GR_FMAX(c2, 0.0), cth * cth, Q);
+                                const real sT = !(T <= 0.0) ? sqrt_fast(T) : 0.0;
+                                out = 2.0 * (1.0 + 1e-6) * d * sT < mu * (sqrt_fast(GR_FMA(R1, d, R)) + sqrt_fast(R));
+                            }
+                        }
+                        if (out) {
+                            const real reach = GR_FMA(m.radial_speed_bound(x[1], E, L), tend - t, x[1]);
+                            if (reach * (1.0 + 1e-6) < (real)p.cfg.r_outer) t = tend;
+                            else flags |= RAY_NO_CULL;
+                        }
+                    }
                 }
             }
             return term || !(t < tend);

@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(256, GR_LANE_MIN_WAVES) k_trace_lane(const Par
         const typename ColdSel<Metric>::type cs = cold_store_of<ColdSel<Metric>>(p);
         bool live = gid < p.n;
         if (live) {
-            ray.init(m, p, tile_swizzle(cold_of(p), gid));
+            ray.init(m, p, tile_swizzle(cold_of(p), gid));      // never decided at the start: no cull is compiled for a mesh (Ray::kEscapeCull)
             ray.mesh_coop = 1;
         }
         while (__any(live)) {
@@ -270,8 +270,9 @@ __global__ void __launch_bounds__(256, GR_LANE_MIN_WAVES) k_trace_lane(const Par
         const typename ColdSel<Metric>::type cs = cold_store_of<ColdSel<Metric>>(p);
         unsigned long long tab_t0 = 0;
         if constexpr (ColdSel<Metric>::kTab) tab_t0 = wall_clock64();
-        ray.init(m, p, tile_swizzle(cold_of(p), gid));
-        while (!ray.step(m, p, cs)) {}
+        // (a ray the start cull decides takes no step at all: Ray::init)
+        if (!ray.init(m, p, tile_swizzle(cold_of(p), gid)))
+            while (!ray.step(m, p, cs)) {}
         // In a one-wave workgroup finalize() lays the end-point record down in the LDS bytes other lanes of this wave use as
         // cold storage inside step() (lds_prologue): every lane must have LEFT the loop before any lane stores.  The
         // structured loop exit guarantees that today; the barrier states it, so that no later pass may sink finalize() into a
@@ -347,18 +348,26 @@ __global__ void __launch_bounds__(256, GR_PERSISTENT_MIN_WAVES) k_trace_persiste
                     pending = false;
                 }
             }
-            if (!queue_empty) {
+            // (a lane whose new ray the start cull decides, Ray::init, is done with it here and draws again at once)
+            bool redraw = !queue_empty;
+            while (redraw) {
                 const unsigned long long idle = __ballot(!active);
                 const int n = __popcll(idle);
                 unsigned long long base = 0;
                 if (lane == 0) base = atomicAdd(p.queue, (unsigned long long)n);
                 base = __shfl(base, 0, 64);
                 const int64_t mine = (int64_t)base + __popcll(idle & ((1ull << lane) - 1ull));
+                bool decided = false;
                 if (!active && mine < p.n) {
-                    ray.init(m, p, tile_swizzle(cold_of(p), mine));
-                    active = true;
+                    decided = ray.init(m, p, tile_swizzle(cold_of(p), mine));
+                    if (decided) {
+                        ray.finalize(m, p, lds);
+                        ls.add(ray);
+                    } else
+                        active = true;
                 }
                 if ((int64_t)base + n >= p.n) queue_empty = true;
+                redraw = !queue_empty && __ballot(decided) != 0ull;
             }
             if (__ballot(active) == 0ull) break;
         }
@@ -383,7 +392,7 @@ __global__ void __launch_bounds__(64) k_trace_path(const Params p, double* path,
     Metric m;
     m.load(p.cfg);
     Ray<Metric, DISC> ray;
-    ray.init(m, p, j);
+    ray.init(m, p, j);      // never decided at the start: a path launch leaves Params::r_cull_start at +inf (derive_params)
     double* const mine = path + 9 * cap * j;
     int64_t n = 0;
     auto save = [&]() {

@@ -714,8 +714,9 @@ static int32_t sky_prepare(gr_ctx* ctx, Params& p, Cold& cold, hipStream_t strea
     return GR_OK;
 }
 
-// The escape cull's radius for one launch (Params::r_cull, Ray::step); +inf leaves every ray to run to its end.
-// Finite only where each condition of the proof in Ray::step holds:
+// The culls' gating radius for one launch (Params::r_cull for Ray::step's escape and polar-rate culls, Params::r_cull_start for
+// Ray::init's start cull); +inf leaves every ray to run to its end.
+// Finite only where each condition of the proofs in Ray::step and Ray::init holds:
 //   output:    finalize reads nothing but the status of a ray that misses -- a fused point function behind filter_intersected
 //              (out_mode 0), BinningMethod (2: only rays that hit are binned) or (g, ρ) pairs (3: NaN pairs).  Never for end points
 //              (1), ray summaries (4, 5), filter_early_term or an unfiltered point function;
@@ -724,22 +725,21 @@ static int32_t sky_prepare(gr_ctx* ctx, Params& p, Cold& cold, hipStream_t strea
 //              (μ = 0) traced forward (λ1 > λ0);
 //   callbacks: no hemisphere, PoloidalShapeChart or winding callback (any of them can set a status after the cull point);
 //   precision: the fp64 kernels (lane and persistent); not fp32, not the tangent kernels.
-// GRADUS_MI355X_ESCAPE_CULL=0 in the environment, read at every launch, switches it off (A/B of one build).
+// Two switches in the environment, read at every launch (A/B of one build), each on its own mechanism (launch_trace):
+// GRADUS_MI355X_ESCAPE_CULL=0 -- no ray ends early inside the step loop; GRADUS_MI355X_START_CULL=0 -- no ray is decided at its start.
+static bool cull_switched_off(const char* name)
+{
+    const char* sw = std::getenv(name);
+    return sw && std::strcmp(sw, "0") == 0;
+}
 static double escape_cull_radius(const gr_ctx* ctx, const Params& p, const Cold& cold, bool tangent)
 {
     const double off = HUGE_VAL;
-    const char* sw = std::getenv("GRADUS_MI355X_ESCAPE_CULL");
-    if (sw && std::strcmp(sw, "0") == 0) return off;
     if (tangent || ctx->precision == 32) return off;
     const bool misses_ignored = (cold.out_mode == 0 && cold.pf.filter_id == GR_FILTER_INTERSECTED) || cold.out_mode == 2 || cold.out_mode == 3;
     const gr_config& c = p.cfg;
-    if (!misses_ignored || c.disc_id != GR_DISC_THIN || c.upper_hemisphere != 0 || c.mu != 0.0 || !(c.lambda1 > c.lambda0)) return off;
-    if (c.metric_id < 0 || c.metric_id > GR_METRIC_TABULATED) return off;
-    const double r_esc = kEscapeRadiusM[c.metric_id] * c.params[0];
-    if (!(r_esc < off) || !(c.params[0] > 0.0) || !(std::fabs(c.params[1]) <= c.params[0])) return off;
-    if (!(c.gtol >= 0.0 && c.gtol < 1.0) || !(c.disc_r_out < off)) return off;
-    const double r_disc = c.disc_r_out / std::sqrt(1.0 - c.gtol * c.gtol);      // outside it the thin disc's condition is > 0
-    return (1.0 + 1e-6) * std::max(r_esc, r_disc);
+    if (!misses_ignored || c.metric_id < 0 || c.metric_id > GR_METRIC_TABULATED) return off;
+    return cull_gate_radius(c, kEscapeRadiusM[c.metric_id]);      // the conditions on the configuration: gr_device.hpp
 }
 
 int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t stream)
@@ -802,7 +802,11 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
     // image planes are tiled and their tile order already mixes (gr_ctx_set "xcd_spread" 0 switches it off)
     p.xcd_spread = (ctx->xcd_spread && kern_sel == 0 && cold.src_mode != 0) ? 1 : 0;
     derive_params(p);
-    p.r_cull = escape_cull_radius(ctx, p, cold, tangent);
+    {
+        const double r_gate = escape_cull_radius(ctx, p, cold, tangent);
+        p.r_cull = cull_switched_off("GRADUS_MI355X_ESCAPE_CULL") ? HUGE_VAL : r_gate;
+        p.r_cull_start = cull_switched_off("GRADUS_MI355X_START_CULL") ? HUGE_VAL : r_gate;
+    }
     LaunchKnobs knobs{ kern_sel, block_sel, ctx->n_cu, (int)ctx->waves_per_simd,
                        ctx->d_queue + ctx->queue_next };
     ctx->queue_next = (ctx->queue_next + 1) % ctx->queue_slots;

@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""CPU census of the start cull and the step loop's culls (Ray::init, Ray::step) on the bench plane.
+
+Random whole 8 x 8 tiles of the 2048² bench image (Kerr a = 0.998, observer r = 1000, θ = 75°, ThinDisc(isco, 50), λ1 = 2000),
+lanes as the one-ray-per-lane kernel lays them out, are stepped through the KERNEL's own logic compiled for the host
+(tests/host_harness_cull.cpp) four times: both mechanisms off, the start cull alone, the step loop's culls alone, both.  Printed:
+steps per arm, the sum over tiles of the longest lane's steps (the cost of one wave per tile), how many rays each arm ended early
+and how many of those the full trace says hit the disc (must be 0), whether pixels and statuses are the same bytes in all arms,
+and the ratio of accepted steps that GRADUS_MI355X_ESCAPE_CULL unset / =0 shows on this build.  The step loop's arm here holds the
+escape cull (r > R_cull) and the polar-rate cull together, as the switch does.  CPU only.
+
+    python scripts/cull_census.py [--tiles 1000] [--seed 1]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+SIZE, ALIMS, BLIMS = 2048, (-60.0, 60.0), (-35.0, 35.0)
+X_OBS = np.array([0.0, 1000.0, math.radians(75.0), 0.0])
+
+
+def bench_scene(G, size=SIZE, x=X_OBS, r_out=50.0, **kw):
+    m = G.KerrMetric(1.0, 0.998)
+    cfg = G.render_configuration(m, x, G.ThinDisc(m.isco(), r_out), 2000.0, image_width=size, image_height=size,
+                                 alpha_lims=ALIMS, beta_lims=BLIMS, **kw)
+    pf = G.ConstPointFunctions.redshift(m, x) @ G.ConstPointFunctions.filter_intersected()
+    return cfg, pf
+
+
+def census(tiles=1000, seed=1):
+    import gradus_jl_amd as G
+    import harness_cull as Hc
+
+    cfg, pf = bench_scene(G)
+    nt = SIZE // 8
+    picks = np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
+    res, _ = Hc.census(G, cfg, pf, picks)
+    res["seed"] = int(seed)
+    res["r_cull"] = Hc.gate_radius(cfg)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tiles", type=int, default=1000)
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    print(json.dumps(census(a.tiles, a.seed), indent=1))
+
+
+if __name__ == "__main__":
+    main()
