@@ -78,12 +78,16 @@ typedef double gr_real_t;
 #else
 #define GR_HAS_MESH 1
 #endif
+// The pass cull (KerrFamily::pass_cull_bounds, Ray::start_decided) is written for plain doubles (asin): the fp64 kernels and the
+// host harnesses.  The fp32 and tangent flavours are never gated on (escape_cull_radius) and do not compile it.
+#define GR_HAS_PASS_CULL GR_HAS_MESH
 
 #ifdef GR_HOST_HARNESS
 // tests/host_harness.cpp compiles this header with g++ to trace single rays on the CPU next to
 // the oracle.  Test infrastructure only: the shipped library never defines GR_HOST_HARNESS.
 #include <cmath>
 #define GR_DEV inline
+#define GR_DEV_COLD inline
 #ifdef GR_REAL_IS_TAN2
 #define GR_RCP_SEED(x) gr_t_rcp(x)
 #define GR_RSQ_SEED(x) gr_t_rsq(x)
@@ -97,6 +101,7 @@ typedef double gr_real_t;
 #else
 #include <hip/hip_runtime.h>
 #define GR_DEV __device__ __forceinline__
+#define GR_DEV_COLD __device__ __attribute__((noinline))      // once-per-ray code kept out of the kernels' register allocation
 #if defined(GR_REAL_IS_TAN2)
 #define GR_RCP_SEED(x) gr_t_rcp(x)
 #define GR_RSQ_SEED(x) gr_t_rsq(x)
@@ -579,6 +584,108 @@ struct KerrFamily {
         R2 = GR_FMA(12.0, e2r2, 2.0 * c2);
         return c2;
     }
+
+#if GR_HAS_PASS_CULL
+    // PASS CULL (Ray::start_decided): the closed forms.  An ingoing ray that starts outside R_cull = 1/uc, turns
+    // at r_t >= R_pass = 1/up and leaves again is a miss if every visit of the disc's wedge |μ| <= gtol falls before it first
+    // reaches R_cull or after it has left R_cull again.  In u = 1/r and Mino time, with ω² = L² + Q - a²E² = -c2:
+    //   (du/dτ)² = U(u) = E² - u² W(u),  W(u) = ω² - c1 u + a²Q u²;   (dμ/dτ)² = Θ(μ) = Q - ω² μ² - a²E² μ⁴.
+    // Preconditions (the caller adds r0 > R_cull and v^r < 0): E > 0, Q > 0, ω² > 0, |μ0| > gtol (1 + 1e-6).
+    // Radial side.
+    //  1. Turning point.  U'' = -2ω² + 6 c1 u - 12 a²Q u² < 0 on [0, u] once 3 c1 u < ω²: U is concave there, and with
+    //     U(0) = E² > 0, U'(0) = 0 it falls.  U(uc) > 0 is asked (else the start cull's own test is the one that applies).
+    //     Newton from uc lands beyond the root (the tangent of a concave function lies above it) at u1, the largest u used:
+    //     concavity is asked there.  From u1 on Newton descends to the root from above; four more rounds leave a relative
+    //     error far below 1e-6 (from r_t = 0.7 R_cull: 6e-2, 2e-3, 2e-6, 4e-12).  The bracket is u (1 -+ 1e-6), and both
+    //     signs are verified by evaluation: U(u_lo) > 0 (so U > 0 on [0, u_lo], concave and positive at both ends: u_t is the
+    //     FIRST root) and U(u_hi) < 0.  Asked of it: uc < u_lo, u_hi <= up, and 1/u_hi beyond (1 + 1e-6) kEscapeRadiusM M.
+    //  2. Harmonic bounds with the true turning point u_t, W_t = W(u_t) = E²/u_t².  If c1 >= 2 a²Q u_t, W falls on [0, u_t] and
+    //       (W_t - c1 u_t / 2)(u_t² - u²) <= U(u) <= W_t (u_t² - u²)   for 0 <= u <= u_t:
+    //     above by W(u) >= W_t; below by W(u) - W_t <= c1 (u_t - u) and u² <= u_t (u_t + u) / 2.  W_t - c1 u_t / 2 > 0 is asked.
+    //  3. Times, S(x) = π/2 - asin(x / u_t):  T_a^lo = (asin(uc/u_t) - asin(u0/u_t)) / sqrt(W_t) is at most the Mino time at
+    //     which r first reaches R_cull;  T_b^hi = (S(u0) + S(uc)) / sqrt(W_t - c1 u_t / 2) is at least the Mino time at which the
+    //     ray is back at R_cull on its way out.  Both are monotone in u_t; each is formed at both ends of the bracket and the
+    //     weaker value kept.
+    // Polar side.  μ+² = 2Q / (ω² + sqrt(ω⁴ + 4 a²E² Q)) is the turning value (also for a = 0), and
+    // Θ = a²E² (μ+² - μ²)(μ² + m²) with a²E² m² = Q/μ+².  With μ = μ+ sin ψ the phase rises at ψ'² = Q/μ+² + a²E² μ², between
+    // Ω_lo² = Q/μ+² = (ω² + sqrt(..))/2 and Ω_hi² = Ω_lo² + a²E² μ+².  Asked: |μ0| < μ+, g = gtol/μ+ < 1 - 1e-6.  δ = asin g;
+    // ψ0 = asin(μ0/μ+) if dμ/dτ >= 0 at the start (the sign of -v^θ), else π - asin(μ0/μ+).  The wedge is ψ within δ of nπ; its
+    // n-th visit (nπ - δ > ψ0) lies inside the Mino-time window [(nπ - δ - ψ0)/Ω_hi, (nπ + δ - ψ0)/Ω_lo], both ends rising with n.
+    // Decision.  n* = the first visit ahead whose window end (1 + 1e-6) is not below T_a^lo; the ray is decided if the window
+    // start of n* times (1 - 1e-6) exceeds T_b^hi.  Visits before n* happen at r > R_cull going in, n* and all later ones at
+    // r > R_cull going out, where the disc's condition is > 0 (Ray::step, 2) and the escape cull's 1-3 hold from there on.
+    // Margins: the 1e-6 on the bracket, on gtol, on g and on the two window ends each exceed by ten orders the rounding of
+    // asin, sqrt_fast and rcp_full (<= 1 ulp), and by three the integrator's drift from the exact geodesic at tolerance 1e-9,
+    // which moves E, L, Q and so u_t, the two times and the phase by relative 1e-9; R_cull itself carries the 1e-6 it has over
+    // the disc's reach (cull_gate_radius).  Every condition is a comparison that a NaN or inf fails: such a ray is traced.
+    struct PassBounds {
+        real u_lo, u_hi;        // bracket of the turning point u_t = 1/r_t
+        real Ta_lo, Tb_hi;      // Mino time: first at R_cull not before Ta_lo, back at R_cull not after Tb_hi
+        real Om_lo, Om_hi;      // bounds of dψ/dτ
+        real psi0;              // the polar phase at the start
+    };
+    static GR_DEV real pass_U(real u, real e2, real w2, real c1, real q4) { return GR_FMA(-(u * u), GR_FMA(u, GR_FMA(u, q4, -c1), w2), e2); }
+    static GR_DEV bool pass_cull_bounds(real M, real a, real E, real L, real Q, real u0, real uc, real up, real mu0, bool mu_rising, real gtol,
+                                        PassBounds& b)
+    {
+        constexpr real kPi = 3.141592653589793;
+        const real e2 = E * E, A = (a * a) * e2, lae = L - a * E;
+        const real w2 = GR_FMA(L, L, Q) - A, c1 = 2.0 * M * GR_FMA(lae, lae, Q), q4 = (a * a) * Q;
+        b = PassBounds{ 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+        if (!(E > 0.0 && Q > 0.0 && w2 > 0.0) || !(GR_FABS(mu0) > gtol * (1.0 + 1e-6))) return false;
+        // 1. the turning point: Newton on the concave U from uc
+        real f = pass_U(uc, e2, w2, c1, q4);
+        if (!(f > 0.0)) return false;
+        real u = uc;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const real d = -u * GR_FMA(u, GR_FMA(u, 4.0 * q4, -3.0 * c1), 2.0 * w2);       // U'(u)
+            u = GR_FMA(-f, rcp_full(d), u);
+            if (k == 0 && (!(u > uc) || !(3.0 * c1 * u < w2))) return false;            // concave on [0, u1]
+            f = pass_U(u, e2, w2, c1, q4);
+        }
+        const real u_lo = u * (1.0 - 1e-6), u_hi = u * (1.0 + 1e-6);
+        b.u_lo = u_lo; b.u_hi = u_hi;
+        if (!(pass_U(u_lo, e2, w2, c1, q4) > 0.0) || !(pass_U(u_hi, e2, w2, c1, q4) < 0.0)) return false;
+        if (!(uc < u_lo) || !(u0 < uc) || !(u_hi <= up) || !(u_hi * ((1.0 + 1e-6) * kEscapeRadiusM * M) < 1.0)) return false;
+        // 2, 3. the two times, at both ends of the bracket
+        if (!(c1 >= 2.0 * q4 * u_hi)) return false;
+        real Ta = __builtin_inf(), Tb = 0.0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const real ut = k ? u_hi : u_lo, iu = rcp_full(ut);
+            const real Wt = e2 * (iu * iu), Wl = GR_FMA(-0.5 * c1, ut, Wt);
+            if (!(Wl > 0.0)) return false;
+            const real as0 = ::asin(u0 * iu), asc = ::asin(uc * iu);
+            Ta = GR_FMIN(Ta, (asc - as0) * rcp_full(sqrt_fast(Wt)));
+            Tb = GR_FMAX(Tb, (kPi - as0 - asc) * rcp_full(sqrt_fast(Wl)));
+        }
+        b.Ta_lo = Ta; b.Tb_hi = Tb;
+        // the polar phase and its rates
+        const real ol2 = 0.5 * (w2 + sqrt_fast(GR_FMA(w2, w2, 4.0 * A * Q)));      // Q/μ+²
+        const real mp2 = Q * rcp_full(ol2), imp = rcp_full(sqrt_fast(mp2));
+        const real g = gtol * imp, s0 = mu0 * imp;
+        if (!(GR_FABS(s0) < 1.0) || !(g < 1.0 - 1e-6)) return false;
+        const real delta = ::asin(g), as_mu = ::asin(s0);
+        const real psi0 = mu_rising ? as_mu : kPi - as_mu;
+        const real om_lo = sqrt_fast(ol2), om_hi = sqrt_fast(GR_FMA(A, mp2, ol2));
+        b.Om_lo = om_lo; b.Om_hi = om_hi; b.psi0 = psi0;
+        // the first visit ahead, then the first whose window does not end before Ta
+        const real n1 = psi0 < -delta ? 0.0 : (psi0 < kPi - delta ? 1.0 : 2.0);
+        const real nx = GR_FMAX(n1, __builtin_ceil((Ta * om_lo * (1.0 / (1.0 + 1e-6)) - delta + psi0) * (1.0 / kPi)));
+        const real start = (GR_FMA(nx, kPi, -delta) - psi0) * rcp_full(om_hi);
+        return start * (1.0 - 1e-6) > Tb;
+    }
+    // ... as ONE out-of-line function of plain values for the kernels: it runs once per ray, before the step loop, and inlined
+    // it disturbs the register allocation of both kernels (one ray per lane: 12 B more scratch; persistent: 226 -> 238 VGPRs and
+    // 20 B of scratch where there was none; profiles/r10_static_counts.txt).  Returns the lower end of r_t's bracket, the
+    // smallest r of the path (the bound on r_outer is formed there), or 0 if the ray is not decided.
+    static GR_DEV_COLD real pass_cull_rmin(real M, real a, real E, real L, real Q, real u0, real uc, real up, real mu0, real vth, real gtol)
+    {
+        PassBounds b;
+        return pass_cull_bounds(M, a, E, L, Q, u0, uc, up, mu0, vth <= 0.0, gtol, b) ? rcp_full(b.u_hi) : 0.0;
+    }
+#endif
 
     // hand-differentiated; one reciprocal for everything
     GR_DEV void eval(real r, real s, real c, real g[5], real gr[5], real gt[5], real gi[5]) const
@@ -2519,6 +2626,9 @@ struct Params {
     // start cull (Ray::init): the same radius for the test at the start of a ray -- a ray whose radial turning
     // point lies outside it is decided before its first step.  A switch of its own: +inf = off, whatever r_cull holds.
     double r_cull_start = __builtin_inf();
+    // pass cull (Ray::start_decided): the start cull's second test decides ingoing rays that turn outside this
+    // radius, pass_cull_radius(r_cull_start) < r_cull_start.  +inf = off; asked only where r_cull_start is finite.
+    double r_pass = __builtin_inf();
 };
 
 // the derived fields of Params, from cfg (host side; one place for the library and the two host harnesses)
@@ -2532,6 +2642,7 @@ static inline void derive_params(Params& p)
     p.maxiters32 = (int32_t)(mi > 0x7fffffff ? 0x7fffffff : mi);
     p.r_cull = __builtin_inf();     // the escape cull is off unless the launcher gates it on (escape_cull_radius)
     p.r_cull_start = __builtin_inf();     // ... and so is the start cull
+    p.r_pass = __builtin_inf();           // ... and its second test, the pass cull
 }
 
 // The culls' gating radius as far as the configuration decides it (host side; one place for the launcher, escape_cull_radius in
@@ -2549,6 +2660,13 @@ static inline double cull_gate_radius(const gr_config& c, double escape_radius_M
     const double r_disc = c.disc_r_out / ::sqrt(1.0 - c.gtol * c.gtol);
     return (1.0 + 1e-6) * (r_esc > r_disc ? r_esc : r_disc);
 }
+
+// The pass cull's radius R_pass = ζ R_cull (Ray::start_decided): rays that turn between R_pass and R_cull are the weak-field part
+// of the misses that dip inside R_cull.  ζ is as small as the bracket (0.62, 0.73) on the accepted-step ratio of
+// GRADUS_MI355X_ESCAPE_CULL unset over =0 allows (tests/test_gpu_escape_cull.py, tests/test_cull_host.py): a decision at the start
+// takes more from the ratio's denominator than from its numerator.  Census behind the value: DESIGN.md §5a.
+constexpr double kPassCullZeta = 0.75;
+static inline double pass_cull_radius(double r_gate) { return r_gate < __builtin_inf() ? kPassCullZeta * r_gate : __builtin_inf(); }
 
 // Small read-mostly tables staged in LDS by the kernel prologue (null = use the global copy):
 // the PlungingInterpolation table of the non-Kerr redshift and the per-workgroup private copy of
@@ -3300,6 +3418,10 @@ struct Ray {
     // R <= 0.  With R' <= 4 E² r³ there, the turning point then lies at least 2.5e-7 R_cull beyond R_cull, which itself is 1e-6
     // beyond the disc's reach: the room for the rounding of E, L, Q and R and for the integrator's drift from the exact geodesic
     // (1e-9 tolerance), as in step().  The bound of 3 carries the same 1e-6 as there.  NaN or inf constants fail the compares.
+    // PASS CULL: asked only where 2 fails.  An ingoing ray (v^r < 0) that turns at r_t >= R_pass = Params::r_pass and meets the
+    // wedge |μ| <= gtol only outside R_cull, by two-sided bounds on its radial and polar Mino times, is decided the same way
+    // (Metric::pass_cull_bounds holds the statement, the closed forms and the margins).  The bound of 3 is then formed at the
+    // smallest r of the path, the lower end of r_t's bracket, where B is largest.  A switch of its own: r_pass = +inf is off.
     GR_DEV bool start_decided(const Metric& m, const Params& p) const
     {
         real s, c, g[5];
@@ -3310,8 +3432,17 @@ struct Ray {
         const real rc = (real)p.r_cull_start, rc2 = rc * rc;
         real R, R1, R2;
         m.radial_potential(rc, E, L, Q, R, R1, R2);
-        if (!(R < -1e-6 * ((E * E) * (rc2 * rc2)))) return false;
-        const real reach = GR_FMA(m.radial_speed_bound(rc, E, L), (real)p.cfg.lambda1 - (real)p.cfg.lambda0, x[1]);
+        real r_min = rc;      // the smallest r of the path, for the bound of 3
+        if (!(R < -1e-6 * ((E * E) * (rc2 * rc2)))) {
+#if GR_HAS_PASS_CULL
+            if (!((real)p.r_pass < (real)__builtin_inf()) || !(v[1] < 0.0)) return false;
+            r_min = Metric::pass_cull_rmin(m.M, m.a, E, L, Q, rcp_full(x[1]), rcp_full(rc), rcp_full((real)p.r_pass), c, v[2], (real)p.cfg.gtol);
+            if (!(r_min > 0.0)) return false;
+#else
+            return false;
+#endif
+        }
+        const real reach = GR_FMA(m.radial_speed_bound(r_min, E, L), (real)p.cfg.lambda1 - (real)p.cfg.lambda0, x[1]);
         return reach * (1.0 + 1e-6) < (real)p.cfg.r_outer;
     }
 

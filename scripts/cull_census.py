@@ -9,7 +9,12 @@ and how many of those the full trace says hit the disc (must be 0), whether pixe
 and the ratio of accepted steps that GRADUS_MI355X_ESCAPE_CULL unset / =0 shows on this build.  The step loop's arm here holds the
 escape cull (r > R_cull) and the polar-rate cull together, as the switch does.  CPU only.
 
-    python scripts/cull_census.py [--tiles 1000] [--seed 1]
+With --pass-cull the same tiles go through tests/host_harness_pass_cull.cpp as well, the pass cull (Ray::start_decided) on
+against off under the start cull alone and under all culls, and the result gains a "pass_cull" entry: steps and wave-steps of
+the four arms, how many rays the pass cull decided (and how many of those hit the disc: must be 0), the ratio of wave-steps it
+leaves, and the GRADUS_MI355X_ESCAPE_CULL switch ratio with it on.  --zeta tries another R_pass = ζ R_cull than the library's.
+
+    python scripts/cull_census.py [--tiles 1000] [--seed 1] [--pass-cull [--zeta 0.72] [--pass-only]]
 """
 from __future__ import annotations
 
@@ -50,12 +55,34 @@ def census(tiles=1000, seed=1):
     return res
 
 
+def pass_census(tiles=1000, seed=1, zeta=-1.0):
+    """The pass cull's arms on the tiles census() draws for the same arguments (zeta < 0: the library's)."""
+    import gradus_jl_amd as G
+    import harness_pass_cull as Hp
+
+    cfg, pf = bench_scene(G)
+    nt = SIZE // 8
+    picks = np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
+    res, _ = Hp.census(G, cfg, pf, picks, zeta)
+    res["seed"] = int(seed)
+    res["zeta"] = Hp.zeta() if zeta < 0 else float(zeta)
+    res["r_cull"] = Hp.gate_radius(cfg)
+    res["r_pass"] = res["zeta"] * res["r_cull"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--pass-cull", action="store_true", help="add the pass cull's arms")
+    ap.add_argument("--zeta", type=float, default=-1.0, help="R_pass / R_cull (default: the library's constant)")
+    ap.add_argument("--pass-only", action="store_true", help="with --pass-cull: skip the four arms of the older culls")
     a = ap.parse_args()
-    print(json.dumps(census(a.tiles, a.seed), indent=1))
+    res = {} if (a.pass_cull and a.pass_only) else census(a.tiles, a.seed)
+    if a.pass_cull:
+        res["pass_cull"] = pass_census(a.tiles, a.seed, a.zeta)
+    print(json.dumps(res, indent=1))
 
 
 if __name__ == "__main__":
