@@ -618,6 +618,20 @@ struct KerrFamily {
     // asin, sqrt_fast and rcp_full (<= 1 ulp), and by three the integrator's drift from the exact geodesic at tolerance 1e-9,
     // which moves E, L, Q and so u_t, the two times and the phase by relative 1e-9; R_cull itself carries the 1e-6 it has over
     // the disc's reach (cull_gate_radius).  Every condition is a comparison that a NaN or inf fails: such a ray is traced.
+    // ENTRY CULL (Ray::step): the same question for an ingoing ray already INSIDE R_cull, u0 >= uc, with E, L, Q, μ0 and the sign
+    // of dμ/dτ taken from its current state and τ counted from there.  What carries over, and what is asked instead:
+    //  - 1 does not read u0: the bracket is that of the first root of U beyond uc, and U > 0 on [0, u_lo].  u0 < u_lo is asked (in
+    //    place of u0 < uc, which the start's caller has by r0 > R_cull and which uc < u_lo makes the stronger condition there):
+    //    the ray is on the ingoing branch short of the turning point, reaches it and comes back, as from outside.
+    //  - 2 holds on all of [0, u_t], so  ∫ du/sqrt(U) from u0 to u_t  <= S(u0)/sqrt(W_t - c1 u_t / 2) for any u0 <= u_t and
+    //    T_b^hi = (S(u0) + S(uc))/sqrt(W_t - c1 u_t / 2) is still at least the Mino time at which the ray is back at R_cull.
+    //  - T_a^lo = (asin(uc/u_t) - asin(u0/u_t))/sqrt(W_t) <= 0: the ray is at or inside R_cull now, so no visit ahead falls
+    //    before R_cull is first reached and n* must be the first visit ahead, n1.  The formula gives that: with T_a^lo <= 0 the
+    //    ceil's argument is at most (ψ0 - δ)/π < (ψ0 + δ)/π < n1, so the max keeps n1 (the 1/(1 + 1e-6) on a negative T_a^lo is
+    //    then without effect).  |μ0| > gtol (1 + 1e-6) keeps ψ0 itself out of every window.
+    //  - from the window start of n1 beyond T_b^hi on, the ray is outside R_cull going out with the disc's condition > 0, as
+    //    after a start decision; until then it is inside R_cull and outside the wedge, where the condition is > 0 as well.
+    // The depth limit up is the caller's (R_dip = kEntryCullZeta R_cull there); every other precondition is the one above.
     struct PassBounds {
         real u_lo, u_hi;        // bracket of the turning point u_t = 1/r_t
         real Ta_lo, Tb_hi;      // Mino time: first at R_cull not before Ta_lo, back at R_cull not after Tb_hi
@@ -647,7 +661,7 @@ struct KerrFamily {
         const real u_lo = u * (1.0 - 1e-6), u_hi = u * (1.0 + 1e-6);
         b.u_lo = u_lo; b.u_hi = u_hi;
         if (!(pass_U(u_lo, e2, w2, c1, q4) > 0.0) || !(pass_U(u_hi, e2, w2, c1, q4) < 0.0)) return false;
-        if (!(uc < u_lo) || !(u0 < uc) || !(u_hi <= up) || !(u_hi * ((1.0 + 1e-6) * kEscapeRadiusM * M) < 1.0)) return false;
+        if (!(uc < u_lo) || !(u0 < u_lo) || !(u_hi <= up) || !(u_hi * ((1.0 + 1e-6) * kEscapeRadiusM * M) < 1.0)) return false;
         // 2, 3. the two times, at both ends of the bracket
         if (!(c1 >= 2.0 * q4 * u_hi)) return false;
         real Ta = __builtin_inf(), Tb = 0.0;
@@ -676,14 +690,23 @@ struct KerrFamily {
         const real start = (GR_FMA(nx, kPi, -delta) - psi0) * rcp_full(om_hi);
         return start * (1.0 - 1e-6) > Tb;
     }
-    // ... as ONE out-of-line function of plain values for the kernels: it runs once per ray, before the step loop, and inlined
-    // it disturbs the register allocation of both kernels (one ray per lane: 12 B more scratch; persistent: 226 -> 238 VGPRs and
-    // 20 B of scratch where there was none; profiles/r10_static_counts.txt).  Returns the lower end of r_t's bracket, the
-    // smallest r of the path (the bound on r_outer is formed there), or 0 if the ray is not decided.
-    static GR_DEV_COLD real pass_cull_rmin(real M, real a, real E, real L, real Q, real u0, real uc, real up, real mu0, real vth, real gtol)
+    // The decision as one value: the lower end of r_t's bracket, the smallest r of the path (the bound on r_outer is formed there),
+    // or 0 if the ray is not decided.  Inline, for the entry cull's block in Ray::step ...
+    static GR_DEV real pass_cull_rmin_inline(real M, real a, real E, real L, real Q, real u0, real uc, real up, real mu0, real vth, real gtol)
     {
         PassBounds b;
         return pass_cull_bounds(M, a, E, L, Q, u0, uc, up, mu0, vth <= 0.0, gtol, b) ? rcp_full(b.u_hi) : 0.0;
+    }
+    // ... and as ONE out-of-line function of plain values for Ray::start_decided: it runs once per ray, before the step loop, and
+    // inlined there it disturbs the register allocation of both kernels (one ray per lane: 12 B more scratch; persistent: 226 -> 238
+    // VGPRs and 20 B of scratch where there was none; profiles/r10_static_counts.txt).  Inside the step loop it is the other way
+    // round: a call there leaves the caller the callee-saved half of the registers for the whole ray state and the loop's
+    // invariants, and the allocator answers by keeping invariants in scratch that the five stages reload at every step (160 B, a
+    // scratch load in the head, three stage blocks and the commit block); inlined, the block is one more rarely taken branch
+    // like the event sampling and the parked values are stored and reloaded inside it (profiles/r11_static_counts.txt).
+    static GR_DEV_COLD real pass_cull_rmin(real M, real a, real E, real L, real Q, real u0, real uc, real up, real mu0, real vth, real gtol)
+    {
+        return pass_cull_rmin_inline(M, a, E, L, Q, u0, uc, up, mu0, vth, gtol);
     }
 #endif
 
@@ -2629,6 +2652,10 @@ struct Params {
     // pass cull (Ray::start_decided): the start cull's second test decides ingoing rays that turn outside this
     // radius, pass_cull_radius(r_cull_start) < r_cull_start.  +inf = off; asked only where r_cull_start is finite.
     double r_pass = __builtin_inf();
+    // entry cull (Ray::step): an ingoing ray the start left undecided is asked the pass cull's question once more
+    // at the step that takes it inside r_cull, down to kEntryCullZeta r_cull.  It needs r_cull, r_cull_start and r_pass finite
+    // (each of their switches turns it off); 0 here turns it off alone.  1 = on is what derive_params leaves.
+    int32_t entry_cull = 1;
 };
 
 // the derived fields of Params, from cfg (host side; one place for the library and the two host harnesses)
@@ -2643,6 +2670,7 @@ static inline void derive_params(Params& p)
     p.r_cull = __builtin_inf();     // the escape cull is off unless the launcher gates it on (escape_cull_radius)
     p.r_cull_start = __builtin_inf();     // ... and so is the start cull
     p.r_pass = __builtin_inf();           // ... and its second test, the pass cull
+    p.entry_cull = 1;                     // the entry cull is on wherever r_cull and r_pass both are (GRADUS_MI355X_ENTRY_CULL=0: launch_trace)
 }
 
 // The culls' gating radius as far as the configuration decides it (host side; one place for the launcher, escape_cull_radius in
@@ -2664,9 +2692,16 @@ static inline double cull_gate_radius(const gr_config& c, double escape_radius_M
 // The pass cull's radius R_pass = ζ R_cull (Ray::start_decided): rays that turn between R_pass and R_cull are the weak-field part
 // of the misses that dip inside R_cull.  ζ is as small as the bracket (0.62, 0.73) on the accepted-step ratio of
 // GRADUS_MI355X_ESCAPE_CULL unset over =0 allows (tests/test_gpu_escape_cull.py, tests/test_cull_host.py): a decision at the start
-// takes more from the ratio's denominator than from its numerator.  Census behind the value: DESIGN.md §5a.
-constexpr double kPassCullZeta = 0.75;
+// takes more from the ratio's denominator than from its numerator, a decision of the entry cull (Ray::step) is under that switch
+// and takes from the numerator alone.  With the entry cull the smallest ζ on a 0.01 grid that leaves the ratio at or under 0.70
+// (0.03 inside the bracket, for sampling) is 0.55: 0.687 on 1500 tiles, 0.667 on the 400 of the host tests; 0.54 gives 0.701.
+// Census behind the value: DESIGN.md §5a.
+constexpr double kPassCullZeta = 0.55;
 static inline double pass_cull_radius(double r_gate) { return r_gate < __builtin_inf() ? kPassCullZeta * r_gate : __builtin_inf(); }
+// The entry cull's depth limit R_dip = ζ_dip R_cull (Ray::step): the rays the start leaves undecided are asked again on entering
+// R_cull, with the same closed forms, if they turn outside R_dip.  Below 0.2 the census decides nothing more: deeper
+// rays fail the concavity condition or the harmonic bounds grow too loose.
+constexpr double kEntryCullZeta = 0.2;
 
 // Small read-mostly tables staged in LDS by the kernel prologue (null = use the global copy):
 // the PlungingInterpolation table of the non-Kerr redshift and the per-workgroup private copy of
@@ -2891,6 +2926,8 @@ struct TabLds : Base {
 // The per-lane integrator.
 // ---------------------------------------------------------------------------------------
 enum : int32_t {
+    RAY_ENTRY_ARMED = 0x80,      // bit in Ray::flags of an ingoing ray that started outside R_cull undecided, until the entry cull has
+                                 // been asked for it (Ray::init, Ray::step); below RAY_NO_CULL, whose test is one unsigned compare
     RAY_EVENT = 0x100,     // bit in Ray::flags while a disc event awaits its root find
     RAY_NO_CULL = 0x200    // ... once the escape cull's λ1-first bound has failed for the ray (Ray::step): never tested again
 };
@@ -3459,9 +3496,16 @@ struct Ray {
         h = 0.0;
         lq_old = (float)LOG2_QOLDINIT;
         if constexpr (kEscapeCull) {
-            if (x[1] > (real)p.r_cull_start && start_decided(m, p)) {
-                t = p.cfg.lambda1;
-                return true;
+            if (x[1] > (real)p.r_cull_start) {
+                if (start_decided(m, p)) {
+                    t = p.cfg.lambda1;
+                    return true;
+                }
+#if GR_HAS_PASS_CULL
+                // the entry cull is armed (step()): the start test was asked and left the ray undecided, it goes in, the pass
+                // cull is on.  A ray that starts inside R_cull is never armed.
+                if (v[1] < 0.0 && (real)p.r_pass < (real)__builtin_inf() && p.entry_cull != 0) flags = RAY_ENTRY_ARMED;
+#endif
             }
         }
         real s, c;
@@ -3943,7 +3987,39 @@ struct Ray {
             //     2d (1 + 1e-6) sqrt(T) < (|μ| - gtol)(sqrt(R + R'd) + sqrt(R)).
             // The 1e-6 covers the rounding (sqrt_fast: 1 ulp) and the integrator's drift, as above.  Both bounds are loose by
             // construction.  A NaN anywhere (the axis: Q = inf) fails a compare.  Nothing is carried from step to step.
+            //
+            // ENTRY CULL: the same end for an INGOING ray at the step that takes it inside R_cull, if it provably turns outside
+            // R_dip = kEntryCullZeta R_cull and is back outside R_cull, going out, before its polar phase can reach the wedge -- the
+            // pass cull's question (Metric::pass_cull_bounds, "ENTRY CULL" there) asked of the current state, for the rays that
+            // turn deeper than the start decides.  Asked at most once per ray: Ray::init arms it (RAY_ENTRY_ARMED: started outside
+            // R_cull, undecided, v^r < 0, pass cull on), the first accepted step that ends with r <= R_cull clears the bit whatever
+            // comes of it.  Asked there with R_cull finite, v^r < 0 still, the disc condition > 0 at both ends of the step (as in 2)
+            // and the λ1-first bound not failed before; |μ| > gtol (1 + 1e-6) and the rest are the closed forms' own conditions.
+            // E, L, Q come from the current state; the bound of 3 is formed at the lower end of the turning point's bracket, the
+            // smallest r of the path, with the current λ, and a failure sets RAY_NO_CULL.  The common path pays the bit test; the
+            // closed forms are inlined into this block (why: Metric::pass_cull_rmin).
             if constexpr (kEscapeCull) {
+#if GR_HAS_PASS_CULL
+                if (flags & RAY_ENTRY_ARMED) {
+                    const real rc = (real)p.r_cull;
+                    if (x[1] <= rc) {
+                        flags &= ~RAY_ENTRY_ARMED;
+                        if (rc < (real)__builtin_inf() && cprev > 0.0 && v[1] < 0.0 && (uint32_t)flags < (uint32_t)RAY_NO_CULL) {
+                            real g[5];
+                            metric_comps(m, x[1], x[2], sth, cth, g);
+                            const real E = -(g[0] * v[0] + g[4] * v[3]), L = g[4] * v[0] + g[3] * v[3];
+                            const real Q = m.carter_constant(g[2] * v[2], sth, cth, E, L);
+                            const real r_min = Metric::pass_cull_rmin_inline(m.M, m.a, E, L, Q, rcp_full(x[1]), rcp_full(rc),
+                                                                             rcp_full((real)kEntryCullZeta * rc), cth, v[2], (real)p.cfg.gtol);
+                            if (r_min > 0.0) {
+                                const real reach = GR_FMA(m.radial_speed_bound(r_min, E, L), tend - t, x[1]);
+                                if (reach * (1.0 + 1e-6) < (real)p.cfg.r_outer) t = tend;
+                                else flags |= RAY_NO_CULL;
+                            }
+                        }
+                    }
+                }
+#endif
                 if (cprev > 0.0 && v[1] > 0.0 && (uint32_t)flags < (uint32_t)RAY_NO_CULL) {
                     const real rc = (real)p.r_cull;
                     bool out = x[1] > rc;
@@ -4283,7 +4359,7 @@ struct Ray {
             resolve_event(p);
             flags &= ~RAY_EVENT;
         }
-        if constexpr (kEscapeCull) flags &= ~RAY_NO_CULL;      // a step-loop bit like RAY_EVENT, not an anomaly
+        if constexpr (kEscapeCull) flags &= ~(RAY_NO_CULL | RAY_ENTRY_ARMED);      // step-loop bits like RAY_EVENT, not anomalies
         if (flags & GR_FLAG_MASK) status = GR_STATUS_NO_STATUS;
         const Cold& cd = cold_of(p);
         if (cd.tile_cost) {

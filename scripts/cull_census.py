@@ -14,7 +14,14 @@ against off under the start cull alone and under all culls, and the result gains
 the four arms, how many rays the pass cull decided (and how many of those hit the disc: must be 0), the ratio of wave-steps it
 leaves, and the GRADUS_MI355X_ESCAPE_CULL switch ratio with it on.  --zeta tries another R_pass = ζ R_cull than the library's.
 
+With --entry-cull the same tiles go through tests/host_harness_entry_cull.cpp: the library as shipped ("all"), the entry cull
+(Ray::step) off alone ("no-entry") and the step loop's culls off ("start"), at the library's ζ or at --zeta.  The result gains an
+"entry_cull" entry: steps and wave-steps of the arms, how many rays ended on entry, at which steps, and how many of those hit
+the disc (must be 0), the ratios the entry cull leaves and the GRADUS_MI355X_ESCAPE_CULL switch ratio.  --ref-zeta Z adds the
+wave-steps and accepted steps relative to a library with R_pass = Z R_cull and no entry cull (0.75: the one before the entry cull).
+
     python scripts/cull_census.py [--tiles 1000] [--seed 1] [--pass-cull [--zeta 0.72] [--pass-only]]
+    python scripts/cull_census.py --tiles 1500 --seed 3 --entry-cull --pass-only [--zeta 0.60] [--ref-zeta 0.75]
 """
 from __future__ import annotations
 
@@ -71,17 +78,44 @@ def pass_census(tiles=1000, seed=1, zeta=-1.0):
     return res
 
 
+def entry_census(tiles=1000, seed=1, zeta=-1.0, ref_zeta=None):
+    """The entry cull's arms on the tiles census() draws for the same arguments (zeta < 0: the library's)."""
+    import gradus_jl_amd as G
+    import harness_entry_cull as He
+
+    cfg, pf = bench_scene(G)
+    nt = SIZE // 8
+    picks = np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
+    res, _ = He.census(G, cfg, pf, picks, zeta)
+    res["seed"] = int(seed)
+    res["zeta"] = He.zeta() if zeta < 0 else float(zeta)
+    res["zeta_dip"] = He.zeta_dip()
+    res["r_cull"] = He.gate_radius(cfg)
+    if ref_zeta is not None:
+        ref = He.render_tiles(G, cfg, pf, picks, 1, 1, 0, ref_zeta)
+        att = ref["nacc"].astype(np.int64) + ref["nrej"]
+        res["ref_zeta"] = float(ref_zeta)
+        res["wave_steps_vs_ref"] = res["arms"]["all"]["wave_steps"] / int(att.max(axis=1).sum())
+        res["accepted_steps_vs_ref"] = res["arms"]["all"]["accepted_steps"] / int(ref["nacc"].sum())
+        res["no_entry_wave_steps_vs_ref"] = res["arms"]["no-entry"]["wave_steps"] / int(att.max(axis=1).sum())
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--pass-cull", action="store_true", help="add the pass cull's arms")
     ap.add_argument("--zeta", type=float, default=-1.0, help="R_pass / R_cull (default: the library's constant)")
-    ap.add_argument("--pass-only", action="store_true", help="with --pass-cull: skip the four arms of the older culls")
+    ap.add_argument("--pass-only", action="store_true", help="with --pass-cull or --entry-cull: skip the four arms of the older culls")
+    ap.add_argument("--entry-cull", action="store_true", help="add the entry cull's arms")
+    ap.add_argument("--ref-zeta", type=float, default=None, help="with --entry-cull: compare with R_pass / R_cull = this and no entry cull")
     a = ap.parse_args()
-    res = {} if (a.pass_cull and a.pass_only) else census(a.tiles, a.seed)
+    res = {} if ((a.pass_cull or a.entry_cull) and a.pass_only) else census(a.tiles, a.seed)
     if a.pass_cull:
         res["pass_cull"] = pass_census(a.tiles, a.seed, a.zeta)
+    if a.entry_cull:
+        res["entry_cull"] = entry_census(a.tiles, a.seed, a.zeta, a.ref_zeta)
     print(json.dumps(res, indent=1))
 
 
