@@ -67,6 +67,11 @@ tf, dt = timed(lambda: G.lagtransfer(m, x, d, model, plane=plane, n_samples=100_
 t0 = G.continuum_time(m, x, model, ensemble=ens)
 t, E, f = G.binflux(tf, N_E=1500, N_t=1500, t0=t0, ensemble=ens)
 print(f"lagtransfer: 3.24e6 + 1e5 rays in {dt:.2f} s; continuum time {t0:.2f}; response from t = {t[np.nanargmax(np.nansum(f, axis=0) > 0)]:.1f}")
+# ... the same product with the observer's half kept on the device: no end-point records come back, binflux returns the matrix
+tfd, dt = timed(lambda: G.lagtransfer_device(m, x, d, model, plane=plane, n_samples=100_000, ensemble=ens,
+                                             sampler=G.EvenSampler(G.BothHemispheres(), G.RandomGenerator(seed=1))))
+td, Ed, fd = G.binflux(tfd, N_E=1500, N_t=1500, t0=t0)
+print(f"lagtransfer_device: the same rays in {dt:.2f} s, {tfd.n_hits} hits; sum of the matrix {np.nansum(fd):.6g} (host route {np.nansum(f):.6g})")
 # ... and the semi-analytic route
 d = G.ThinDisc(0.0, float("inf"))
 radii = G.InverseGrid()(m.isco(), 1000.0, 100)

@@ -36,9 +36,9 @@ from .transfer_functions import (CunninghamTransferData, CunninghamTransferGrid,
                                 cunningham_transfer_function, cunningham_transfer_functions, integrate_lagtransfer,
                                 integrate_lineprofile,
                                 interpolate_branches, splitbranches, transferfunctions)
-from .reverberation import (AnalyticRadialDiscProfile, LagTransferFunction, bin_transfer_function, binflux, continuum_time,
-                            lag_frequency,
-                            lagtransfer, observer_to_disc)
+from .reverberation import (AnalyticRadialDiscProfile, DeviceLagTransfer, LagTransferFunction, bin_transfer_function, binflux,
+                            continuum_time, lag_frequency,
+                            lagtransfer, lagtransfer_device, observer_to_disc)
 from .orbit_solving import (measure_stability, solve_equatorial_circular_orbit, trace_equatorial_circular_orbit,
                             trace_single_orbit)
 from .precision_solvers import (find_offset_for_radius, impact_parameters_for_radius, impact_parameters_for_radius_obscured,

@@ -26,7 +26,7 @@ def kernel_source_sha16() -> str:
     h = hashlib.sha256()
     root = os.path.dirname(_HERE)
     for rel in ("gradus.jl_amd/csrc/gr_device.hpp", "gradus.jl_amd/csrc/gr_kernels.hpp", "gradus.jl_amd/csrc/gr_tangent.hpp",
-                "gradus.jl_amd/csrc/gr_tabmetric.hpp", "gradus.jl_amd/csrc/metric_table.hip",
+                "gradus.jl_amd/csrc/gr_tabmetric.hpp", "gradus.jl_amd/csrc/gr_lagbin.hpp", "gradus.jl_amd/csrc/metric_table.hip",
                 "gradus.jl_amd/csrc/kernels_tu.hip",
                 "gradus.jl_amd/csrc/gradus_mi355x.hip",
                 "include/gradus_mi355x.h"):
@@ -230,6 +230,22 @@ class gr_binning(C.Structure):
     ]
 
 
+class gr_lagprofile(C.Structure):
+    """What turns a row (g, ρ, t, area) of gr_lagtransfer_trace into (E, t, f): the line's energy, ε(ρ) as gr_binning has it and
+    the coordtime_at table."""
+
+    _fields_ = [
+        ("E0", C.c_double),
+        ("emissivity_index", C.c_double),
+        ("eps_r", C.c_void_p),
+        ("eps_v", C.c_void_p),
+        ("eps_n", C.c_int64),
+        ("time_r", C.c_void_p),
+        ("time_v", C.c_void_p),
+        ("time_n", C.c_int64),
+    ]
+
+
 class gr_stats(C.Structure):
     _fields_ = [
         ("rays", C.c_int64),
@@ -307,6 +323,10 @@ EXPORTS = [
     "gr_corona_bin",
     "gr_corona_trace_multi",
     "gr_corona_bin_multi",
+    "gr_lagtransfer_trace",
+    "gr_lagtransfer_extrema",
+    "gr_lagtransfer_bin",
+    "gr_lagtransfer_rows",
     "gr_render_endpoints_multi",
     "gr_trace_endpoints_multi",
     "gr_rayset_endpoints_multi",
@@ -373,6 +393,11 @@ def load():
     L.gr_corona_bin.argtypes = [vp, vp, i64, vp]
     L.gr_corona_trace_multi.argtypes = [vp, i32, cfgp, rsp, pfp, vp, C.POINTER(C.c_int64), stp]
     L.gr_corona_bin_multi.argtypes = [vp, i32, vp, i64, vp]
+    lpp = C.POINTER(gr_lagprofile)
+    L.gr_lagtransfer_trace.argtypes = [vp, cfgp, rsp, pfp, C.POINTER(C.c_int64), stp]
+    L.gr_lagtransfer_extrema.argtypes = [vp, lpp, vp, vp]
+    L.gr_lagtransfer_bin.argtypes = [vp, lpp, vp, i64, vp, i64, vp]
+    L.gr_lagtransfer_rows.argtypes = [vp, vp]
     ctxa = C.POINTER(vp)
     L.gr_render_endpoints_multi.argtypes = [ctxa, i32, cfgp, plp, i64, vp, vp]
     L.gr_trace_endpoints_multi.argtypes = [ctxa, i32, cfgp, vp, i64, vp, i64, vp, vp]

@@ -27,6 +27,7 @@
 #define GR_NS gr
 #include "gr_device.hpp"
 #include "gr_mesh_grid.hpp"
+#include "gr_lagbin.hpp"
 
 using namespace gr;
 
@@ -131,6 +132,9 @@ struct gr_ctx {
     size_t corona_bytes = 0;
     int64_t corona_n = -1, corona_hits = 0;
     double corona_gmax = 0.0, corona_tmax = 0.0;
+    double* d_lag = nullptr;               // gr_lagtransfer_trace: (g, ρ, t, area) per ray of the observer's plane, kept for gr_lagtransfer_bin
+    size_t lag_bytes = 0;
+    int64_t lag_n = -1, lag_hits = 0;
     double* d_metric_table = nullptr;      // GR_METRIC_TABULATED: device copy of the caller's table, kept while its build id stays
     size_t metric_table_bytes = 0;
     double metric_table_id = 0.0;
@@ -994,6 +998,7 @@ int32_t gr_ctx_destroy(gr_ctx* c)
     if (c->d_chart_table) (void)hipFree(c->d_chart_table);
     if (c->d_metric_table) (void)hipFree(c->d_metric_table);
     if (c->d_corona) (void)hipFree(c->d_corona);
+    if (c->d_lag) (void)hipFree(c->d_lag);
     if (c->d_sky) (void)hipFree(c->d_sky);
     if (c->d_sky_table) (void)hipFree(c->d_sky_table);
     if (c->d_tile_cost) (void)hipFree(c->d_tile_cost);
@@ -2336,18 +2341,12 @@ __global__ void __launch_bounds__(256) k_corona_minmax(const double* __restrict_
     }
 }
 
-// A double as two integers of a fixed-point grid whose step is a power of two chosen from the largest magnitude and the number
-// of values (CoronaScale): hi = round(v / step), lo = round((v / step - hi) 2^K).  Integer sums do not depend on the order of
-// the additions, so the per-bin sums -- and with them the whole profile -- are the same bits on every run and for every launch
-// shape, which floating-point atomics are not; the grid resolves step 2^-K, below one ulp of any value within 2^10 of the
-// largest, so the sums are also as accurate as a sorted pairwise fp64 sum.
-struct CoronaScale { double inv_step, two_k; };
-__device__ __forceinline__ void corona_split(double v, const CoronaScale& sc, long long& hi, long long& lo)
-{
-    const double s = v * sc.inv_step;             // exact: a power of two
-    hi = __double2ll_rn(s);
-    lo = __double2ll_rn((s - (double)hi) * sc.two_k);
-}
+// The fixed-point grid of the sums (CoronaScale, corona_split, CoronaGrid, corona_grid) lives in gr_lagbin.hpp, which the lag-energy
+// bins below share with their host harness: integer sums do not depend on the order of the additions.
+using gr_lag::CoronaGrid;
+using gr_lag::CoronaScale;
+using gr_lag::corona_grid;
+using gr_lag::corona_split;
 
 // bucket(Simple(), ρ, ...) per hit: the last edge <= ρ, clamped to the first / last bin (the rule the reference's golden emissivity
 // vector pins, test/unit/emissivity.jl:27-48); per bin the count and the fixed-point sums of g and t.  acc: 5 x nb integers
@@ -2389,23 +2388,129 @@ __global__ void __launch_bounds__(256) k_corona_bin(const double* __restrict__ r
     }
 }
 
-// step = 2^(e + en - 62) with vmax < 2^e and n <= 2^en: Σ |hi| < 2^62, every hi below 2^(62 - en) <= 2^52 (exact in a double),
-// K = 62 - en: Σ |lo| < 2^61.
-struct CoronaGrid { CoronaScale sc; double step, lo_unit; };
-CoronaGrid corona_grid(double vmax, int64_t n)
+// ---- observer -> disc: the reduction and the bins of binflux (transfer-functions-2d.jl:98-121,211-241) on the rows
+// gr_lagtransfer_trace keeps; the arithmetic per row is gr_lagbin.hpp ----
+
+// Row preparation: the ray's area into the status column, so that a row is (g, ρ, t, area) and needs nothing of the staged ray
+// set any more (g is already NaN unless the ray met the geometry); counts the hits.  The area is area[j], r_i² of a separable
+// plane (gr_lag::sep_row) or 1.
+using gr_lag::LagSep;
+__global__ void __launch_bounds__(256) k_lag_prepare(double* __restrict__ rows, int64_t n, const double* __restrict__ area, LagSep sep,
+                                                     unsigned long long* hits)
 {
-    int en = 10;
-    while (en < 40 && ((int64_t)1 << en) < n) ++en;
-    int e = 0;
-    if (vmax > 0.0 && std::isfinite(vmax)) (void)std::frexp(vmax, &e);      // vmax = f 2^e, f in [0.5, 1)
-    const int k = 62 - en;
-    CoronaGrid g;
-    g.step = std::ldexp(1.0, e + en - 62);
-    g.sc.inv_step = std::ldexp(1.0, -(e + en - 62));
-    g.sc.two_k = std::ldexp(1.0, k);
-    g.lo_unit = std::ldexp(1.0, -k);
-    return g;
+    unsigned long long cnt = 0ull;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        double a = 1.0;
+        if (sep.r) {
+            const double rr = sep.r[gr_lag::sep_row(sep, i)];
+            a = rr * rr;
+        } else if (area) {
+            a = area[i];
+        }
+        const double g = rows[4 * i];
+        rows[4 * i + 3] = a;
+        cnt += (g == g) ? 1ull : 0ull;
+    }
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+    __shared__ unsigned long long part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt = part[0] + part[1] + part[2] + part[3];
+        if (cnt) atomicAdd(hits, cnt);
+    }
 }
+
+// Over the hits: min / max of E and of t (as ordered bit patterns, gr_lag::ordered_bits), their number and max |f| (the bits of a
+// non-negative double).  red[0] = min E, [1] = max E, [2] = min t, [3] = max t, [4] = count, [5] = max |f|.  Per-wave reduction,
+// then one set of atomics per workgroup (k_corona_minmax).
+__global__ void __launch_bounds__(256) k_lag_extrema(const double* __restrict__ rows, int64_t n, gr_lag::Profile prof, unsigned long long* red)
+{
+    unsigned long long v[6] = { ~0ull, 0ull, ~0ull, 0ull, 0ull, 0ull };
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        gr_lag::Hit h;
+        if (gr_lag::hit_of(prof, rows + 4 * i, h)) {
+            const unsigned long long be = gr_lag::ordered_bits(h.E), bt = gr_lag::ordered_bits(h.t);
+            const double af = fabs(h.f);
+            const unsigned long long bf = af < INFINITY ? (unsigned long long)__double_as_longlong(af) : 0ull;      // (a NaN or infinite f adds nothing)
+            v[0] = be < v[0] ? be : v[0];
+            v[1] = be > v[1] ? be : v[1];
+            v[2] = bt < v[2] ? bt : v[2];
+            v[3] = bt > v[3] ? bt : v[3];
+            v[4] += 1ull;
+            v[5] = bf > v[5] ? bf : v[5];
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        unsigned long long o[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o[k] = __shfl_down(v[k], off, 64);
+        v[0] = o[0] < v[0] ? o[0] : v[0];
+        v[1] = o[1] > v[1] ? o[1] : v[1];
+        v[2] = o[2] < v[2] ? o[2] : v[2];
+        v[3] = o[3] > v[3] ? o[3] : v[3];
+        v[4] += o[4];
+        v[5] = o[5] > v[5] ? o[5] : v[5];
+    }
+    __shared__ unsigned long long part[4][6];
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) part[w][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            v[0] = part[k][0] < v[0] ? part[k][0] : v[0];
+            v[1] = part[k][1] > v[1] ? part[k][1] : v[1];
+            v[2] = part[k][2] < v[2] ? part[k][2] : v[2];
+            v[3] = part[k][3] > v[3] ? part[k][3] : v[3];
+            v[4] += part[k][4];
+            v[5] = part[k][5] > v[5] ? part[k][5] : v[5];
+        }
+        if (v[4]) {
+            atomicMin(red, v[0]);
+            atomicMax(red + 1, v[1]);
+            atomicMin(red + 2, v[2]);
+            atomicMax(red + 3, v[3]);
+            atomicAdd(red + 4, v[4]);
+            atomicMax(red + 5, v[5]);
+        }
+    }
+}
+
+// Σ f per (E, t) cell as two integers on the fixed-point grid `sf`: acc[cell] = Σ hi, acc[cells + cell] = Σ lo with
+// cell = i_E n_t + i_t.  LDS = 1: the histogram is private to the workgroup in LDS (2 x 8 x cells bytes, at most 40 KB) and leaves
+// as one global atomic per non-empty entry; LDS = 0 (the default 300 x 300 matrix): global atomics.
+template <int LDS>
+__global__ void __launch_bounds__(256) k_lag_bin(const double* __restrict__ rows, int64_t n, gr_lag::Profile prof,
+                                                 const double* __restrict__ e_edges, int n_e, const double* __restrict__ t_edges, int n_t,
+                                                 CoronaScale sf, unsigned long long* acc)
+{
+    extern __shared__ unsigned long long lag_hist[];
+    const int cells = n_e * n_t;
+    unsigned long long* h = LDS ? lag_hist : acc;
+    if (LDS) {
+        for (int i = threadIdx.x; i < 2 * cells; i += blockDim.x) lag_hist[i] = 0ull;
+        __syncthreads();
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        gr_lag::Hit hit;
+        if (gr_lag::hit_of(prof, rows + 4 * i, hit) && fabs(hit.f) < INFINITY) {
+            const int cell = gr_lag::bucket(e_edges, n_e, hit.E) * n_t + gr_lag::bucket(t_edges, n_t, hit.t);
+            long long fh, fl;
+            corona_split(hit.f, sf, fh, fl);
+            atomicAdd(h + cell, (unsigned long long)fh);
+            atomicAdd(h + cells + cell, (unsigned long long)fl);
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * cells; i += blockDim.x)
+            if (lag_hist[i] != 0ull) atomicAdd(acc + i, lag_hist[i]);
+    }
+}
+
 int32_t rayset_share(const gr_rayset* rays, int32_t n, int k, gr_rayset& out, int64_t* off_out);      // (below, with the other *_multi helpers)
 }  // namespace
 }  // extern "C++"
@@ -2598,6 +2703,205 @@ int32_t gr_corona_bin_multi(gr_ctx* const* ctxs, int32_t n, const double* edges,
     for (int k = 1; k < n; ++k)
         for (size_t i = 0; i < 5 * nb; ++i) acc[i] += acc[5 * nb * (size_t)k + i];
     corona_bins_out(acc.data(), nb, ctxs[0]->corona_gmax, ctxs[0]->corona_tmax, ctxs[0]->corona_hits, out);
+    return GR_OK;
+}
+
+// ---- observer -> disc on the device: lagtransfer's second half and binflux (transfer-functions-2d.jl:141-242) ----
+// the checks of gr_lagtransfer_extrema / _bin that need no device come first, so that a bad argument is reported as such
+static int32_t lag_profile_args(const gr_lagprofile* p)
+{
+    if (!p) return fail(GR_ERR_INVALID_ARGUMENT, "profile is null");
+    if (p->time_n < 2 || !p->time_r || !p->time_v)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_lagprofile: the coordtime table needs time_n >= 2 radii and times");
+    if (p->eps_n != 0 && (p->eps_n < 2 || !p->eps_r || !p->eps_v))
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_lagprofile: a tabulated emissivity needs eps_n >= 2 radii and values");
+    for (int64_t i = 1; i < p->time_n; ++i)
+        if (!(p->time_r[i] >= p->time_r[i - 1])) return fail(GR_ERR_INVALID_ARGUMENT, "gr_lagprofile: the radii of the coordtime table must ascend");
+    for (int64_t i = 1; i < p->eps_n; ++i)
+        if (!(p->eps_r[i] >= p->eps_r[i - 1])) return fail(GR_ERR_INVALID_ARGUMENT, "gr_lagprofile: the radii of the emissivity table must ascend");
+    return GR_OK;
+}
+static int32_t lag_edge_args(const double* edges, int64_t n, const char* axis)
+{
+    if (!edges) return fail(GR_ERR_INVALID_ARGUMENT, std::string(axis) + " edges are null");
+    if (n < 2) return fail(GR_ERR_INVALID_ARGUMENT, std::string(axis) + " axis: at least two edges");
+    if (n > ((int64_t)1 << 22)) return fail(GR_ERR_INVALID_ARGUMENT, "at most 2^22 cells (n_E * n_t)");
+    for (int64_t i = 1; i < n; ++i)
+        if (!(edges[i] >= edges[i - 1])) return fail(GR_ERR_INVALID_ARGUMENT, std::string(axis) + " edges must ascend");
+    return GR_OK;
+}
+static int32_t lag_have_trace(const gr_ctx* ctx, const char* who)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (ctx->lag_n < 0)
+        return fail(GR_ERR_INVALID_ARGUMENT, std::string(who) + " bins the rays of the context's last gr_lagtransfer_trace: there is none");
+    return GR_OK;
+}
+
+// the profile's tables into ctx->d_in, followed by `extra` doubles for the caller (edges, accumulators, reductions)
+static int32_t lag_stage(gr_ctx* ctx, const gr_lagprofile* p, size_t extra, gr_lag::Profile& dev, double** d_extra)
+{
+    int32_t rc;
+    const size_t nt = (size_t)p->time_n, ne = p->eps_n >= 2 ? (size_t)p->eps_n : 0;
+    if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, sizeof(double) * (2 * nt + 2 * ne + extra) + 64)) != GR_OK) return rc;
+    double* b = (double*)ctx->d_in;
+    GR_HIP(hipMemcpyAsync(b, p->time_r, sizeof(double) * nt, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemcpyAsync(b + nt, p->time_v, sizeof(double) * nt, hipMemcpyHostToDevice, ctx->stream));
+    if (ne) {
+        GR_HIP(hipMemcpyAsync(b + 2 * nt, p->eps_r, sizeof(double) * ne, hipMemcpyHostToDevice, ctx->stream));
+        GR_HIP(hipMemcpyAsync(b + 2 * nt + ne, p->eps_v, sizeof(double) * ne, hipMemcpyHostToDevice, ctx->stream));
+    }
+    dev.E0 = p->E0;
+    dev.q = p->emissivity_index;
+    dev.time_r = b; dev.time_v = b + nt; dev.time_n = p->time_n;
+    dev.eps_r = ne ? b + 2 * nt : nullptr; dev.eps_v = ne ? b + 2 * nt + ne : nullptr; dev.eps_n = (int64_t)ne;
+    *d_extra = b + 2 * nt + 2 * ne;
+    return GR_OK;
+}
+
+// k_lag_extrema over the context's rows; waits for it: v = (E_min, E_max, t_min, t_max, max |f|)
+static int32_t lag_extrema(gr_ctx* ctx, const gr_lag::Profile& dev, unsigned long long* d_red /* 6 */, double v[5])
+{
+    static const unsigned long long init[6] = { ~0ull, 0ull, ~0ull, 0ull, 0ull, 0ull };
+    unsigned long long h[6];
+    GR_HIP(hipMemcpyAsync(d_red, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+    int64_t blocks = (ctx->lag_n + 255) / 256;
+    blocks = blocks > 512 ? 512 : blocks;
+    hipLaunchKernelGGL(k_lag_extrema, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->d_lag, ctx->lag_n, dev, d_red);
+    GR_HIP(hipGetLastError());
+    GR_HIP(hipMemcpyAsync(h, d_red, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 4; ++k) v[k] = gr_lag::ordered_value(h[k]);
+    std::memcpy(&v[4], &h[5], sizeof(double));
+    return GR_OK;
+}
+
+// k_lag_bin over the context's rows into `acc` (host, 2 x cells integers); waits for it
+static int32_t lag_bin(gr_ctx* ctx, const gr_lag::Profile& dev, const double* d_e, int64_t n_e, const double* d_t, int64_t n_t,
+                       const CoronaGrid& gf, unsigned long long* d_acc, long long* acc)
+{
+    const size_t cells = (size_t)(n_e * n_t);
+    GR_HIP(hipMemsetAsync(d_acc, 0, sizeof(unsigned long long) * 2 * cells, ctx->stream));
+    int64_t blocks = (ctx->lag_n + 255) / 256;
+    blocks = blocks > 1024 ? 1024 : blocks;
+    const size_t lds = sizeof(unsigned long long) * 2 * cells;
+    if (lds <= 40 * 1024) {
+        hipLaunchKernelGGL(k_lag_bin<1>, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, ctx->d_lag, ctx->lag_n, dev, d_e, (int)n_e,
+                           d_t, (int)n_t, gf.sc, d_acc);
+    } else {
+        hipLaunchKernelGGL(k_lag_bin<0>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->d_lag, ctx->lag_n, dev, d_e, (int)n_e,
+                           d_t, (int)n_t, gf.sc, d_acc);
+    }
+    GR_HIP(hipGetLastError());
+    GR_HIP(hipMemcpyAsync(acc, d_acc, sizeof(long long) * 2 * cells, hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
+    return GR_OK;
+}
+
+int32_t gr_lagtransfer_trace(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf, int64_t* n_hits,
+                             gr_stats* stats)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    ctx->lag_n = -1;      // (a refused trace leaves none)
+    if (!rays || !n_hits) return fail(GR_ERR_INVALID_ARGUMENT, "rayset / n_hits is null");
+    if (rays->sky_sampler) return fail(GR_ERR_INVALID_ARGUMENT, "gr_lagtransfer_trace traces an observer's plane, not a sky source (gr_rayset.sky_sampler = 0)");
+    if (cfg && cfg->disc_id == GR_DISC_NONE) return fail(GR_ERR_INVALID_ARGUMENT, "a lag transfer function needs accretion geometry: none given");
+    int32_t rc;
+    GR_HIP(hipSetDevice(ctx->device));
+    gr_rayset dev;
+    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
+    if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
+    const size_t n = (size_t)rays->n;
+    if ((rc = ensure((void**)&ctx->d_lag, &ctx->lag_bytes, sizeof(double) * 4 * n + 64)) != GR_OK) return rc;
+    unsigned long long* d_hits = (unsigned long long*)(ctx->d_lag + 4 * n);
+    GR_HIP(hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), ctx->stream));
+    if ((rc = gr_ray_summary_device(ctx, cfg, &dev, pf, ctx->d_lag, stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream)) != GR_OK) return rc;
+    if (n > 0) {
+        LagSep sep{};
+        if (dev.sep_r) {
+            const bool tiled = dev.sep_tiled && dev.sep_nr >= 8 && dev.sep_nt >= 8;      // (as rays_params lays the rays out)
+            sep.r = dev.sep_r; sep.nr = dev.sep_nr;
+            sep.core_rows = tiled ? (dev.sep_nr / 8) * 8 : 0;
+            sep.core_cols = tiled ? (dev.sep_nt / 8) * 8 : 0;
+            sep.first = dev.sep_first; sep.block = dev.sep_block; sep.stride = dev.sep_stride;
+        }
+        int64_t blocks = ((int64_t)n + 255) / 256;
+        blocks = blocks > 1024 ? 1024 : blocks;
+        hipLaunchKernelGGL(k_lag_prepare, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->d_lag, (int64_t)n, dev.area, sep, d_hits);
+        GR_HIP(hipGetLastError());
+    }
+    unsigned long long h = 0ull;
+    GR_HIP(hipMemcpyAsync(&h, d_hits, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = end_host_call(ctx, stats)) != GR_OK) return rc;      // (synchronises the stream)
+    ctx->lag_hits = (int64_t)h;
+    ctx->lag_n = rays->n;
+    *n_hits = (int64_t)h;
+    return GR_OK;
+}
+
+int32_t gr_lagtransfer_extrema(gr_ctx* ctx, const gr_lagprofile* profile, double* lims, double* flux_sum)
+{
+    int32_t rc;
+    if ((rc = lag_profile_args(profile)) != GR_OK) return rc;
+    if (!lims || !flux_sum) return fail(GR_ERR_INVALID_ARGUMENT, "lims / flux_sum is null");
+    if ((rc = lag_have_trace(ctx, "gr_lagtransfer_extrema")) != GR_OK) return rc;
+    if (ctx->lag_hits == 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_lagtransfer_extrema: no ray of the context's last gr_lagtransfer_trace met the geometry");
+    GR_HIP(hipSetDevice(ctx->device));
+    gr_lag::Profile dev;
+    double* x;
+    if ((rc = lag_stage(ctx, profile, 2 + 2 + 6, dev, &x)) != GR_OK) return rc;
+    double v[5];
+    if ((rc = lag_extrema(ctx, dev, (unsigned long long*)(x + 4), v)) != GR_OK) return rc;
+    for (int k = 0; k < 4; ++k) lims[k] = v[k];
+    // Σ f: every hit into the one cell of a 1 x 1 matrix (whatever its edge holds, the cell is clamped to it)
+    GR_HIP(hipMemsetAsync(x, 0, sizeof(double) * 2, ctx->stream));
+    const CoronaGrid gf = corona_grid(v[4], ctx->lag_hits);
+    long long acc[2];
+    if ((rc = lag_bin(ctx, dev, x, 1, x + 1, 1, gf, (unsigned long long*)(x + 2), acc)) != GR_OK) return rc;
+    *flux_sum = gr_lag::corona_sum(acc[0], acc[1], gf);
+    return GR_OK;
+}
+
+int32_t gr_lagtransfer_bin(gr_ctx* ctx, const gr_lagprofile* profile, const double* E_edges, int64_t n_E, const double* t_edges,
+                           int64_t n_t, double* out)
+{
+    int32_t rc;
+    if ((rc = lag_profile_args(profile)) != GR_OK) return rc;
+    if ((rc = lag_edge_args(E_edges, n_E, "energy")) != GR_OK) return rc;
+    if ((rc = lag_edge_args(t_edges, n_t, "time")) != GR_OK) return rc;
+    if (n_E * n_t > ((int64_t)1 << 22)) return fail(GR_ERR_INVALID_ARGUMENT, "at most 2^22 cells (n_E * n_t)");
+    if (!out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
+    if ((rc = lag_have_trace(ctx, "gr_lagtransfer_bin")) != GR_OK) return rc;
+    const size_t cells = (size_t)(n_E * n_t);
+    if (ctx->lag_hits == 0) {
+        std::fill(out, out + cells, 0.0);
+        return GR_OK;
+    }
+    GR_HIP(hipSetDevice(ctx->device));
+    gr_lag::Profile dev;
+    double* x;
+    if ((rc = lag_stage(ctx, profile, (size_t)(n_E + n_t) + 2 * cells + 6, dev, &x)) != GR_OK) return rc;
+    double *d_e = x, *d_t = x + n_E;
+    unsigned long long* d_acc = (unsigned long long*)(x + n_E + n_t);
+    GR_HIP(hipMemcpyAsync(d_e, E_edges, sizeof(double) * (size_t)n_E, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemcpyAsync(d_t, t_edges, sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice, ctx->stream));
+    double v[5];
+    if ((rc = lag_extrema(ctx, dev, d_acc + 2 * cells, v)) != GR_OK) return rc;      // (max |f| of THIS profile: the grid of the sums)
+    const CoronaGrid gf = corona_grid(v[4], ctx->lag_hits);
+    std::vector<long long> acc(2 * cells);
+    if ((rc = lag_bin(ctx, dev, d_e, n_E, d_t, n_t, gf, d_acc, acc.data())) != GR_OK) return rc;
+    for (size_t c = 0; c < cells; ++c) out[c] = gr_lag::corona_sum(acc[c], acc[cells + c], gf);
+    return GR_OK;
+}
+
+int32_t gr_lagtransfer_rows(gr_ctx* ctx, double* out)
+{
+    int32_t rc;
+    if ((rc = lag_have_trace(ctx, "gr_lagtransfer_rows")) != GR_OK) return rc;
+    if (ctx->lag_n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
+    GR_HIP(hipSetDevice(ctx->device));
+    if (ctx->lag_n > 0) GR_HIP(hipMemcpyAsync(out, ctx->d_lag, sizeof(double) * 4 * (size_t)ctx->lag_n, hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
     return GR_OK;
 }
 

@@ -575,6 +575,39 @@ int32_t gr_corona_trace_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* c
                               double* rho_min_max /* 2 */, int64_t* n_hits, gr_stats* stats);
 int32_t gr_corona_bin_multi(gr_ctx* const* ctxs, int32_t n, const double* edges, int64_t n_edges, double* out /* 3 x n_edges */);
 
+/* ---- observer -> disc on the device (added within ABI 8, nothing else changes): the second half of lagtransfer and binflux
+ * (src/transfer-functions/transfer-functions-2d.jl:141-242) without the 152-byte end points.  Calls on ONE context:
+ *   gr_lagtransfer_trace    traces an observer's plane (impact parameters or a separable set, not a sky source) against the disc
+ *                           and keeps (g, ρ, t, area) per ray ON THE DEVICE, in a buffer of its own: the corona calls above and
+ *                           these do not disturb each other.  g = NaN unless the ray met the geometry; area = rays->area, r_i² of
+ *                           a separable plane, or 1.  Returns the number of hits.  A refused trace leaves no rows.
+ *   gr_lagtransfer_extrema  over the hits, with E = g E0, t = coordtime(ρ) + t and f = g³ ε(ρ) area: min / max of E and of t (the
+ *                           limits bin_transfer_function takes when none are given) and Σ f (the normalisation of binflux).
+ *                           An error if the trace had no hit.
+ *   gr_lagtransfer_bin      Σ f per cell of the caller's edges (per axis: last edge <= value, clamped to the first / last bin),
+ *                           NOT normalised.  n_E, n_t >= 2, ascending, n_E * n_t <= 2^22.  The sums are integers on a fixed-point
+ *                           grid like those of gr_corona_bin: the same rows give the same bits for every launch shape.
+ *   gr_lagtransfer_rows     the kept rows, n x 4 doubles (for tests and debugging).
+ * ε and coordtime are gr_binning's: ρ clamped to the table, then the NaNLinearInterpolator; eps_n = 0: ε(ρ) = ρ^-emissivity_index.
+ * Tables and edges are host pointers, staged per call.  Without a trace on the context: GR_ERR_INVALID_ARGUMENT. */
+typedef struct gr_lagprofile {
+    double E0;                /* energy of the line: E = g E0                               */
+    double emissivity_index;  /* ε(ρ) = ρ^-q                                                */
+    const double* eps_r;      /* eps_n radii, ascending (eps_n >= 2: tabulated ε)           */
+    const double* eps_v;      /* eps_n emissivities                                         */
+    int64_t eps_n;
+    const double* time_r;     /* time_n >= 2 radii, ascending: the coordtime_at table       */
+    const double* time_v;     /* time_n source -> disc coordinate times                     */
+    int64_t time_n;
+} gr_lagprofile;
+int32_t gr_lagtransfer_trace(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                             int64_t* n_hits, gr_stats* stats);
+int32_t gr_lagtransfer_extrema(gr_ctx* ctx, const gr_lagprofile* profile, double* lims /* E_min, E_max, t_min, t_max */,
+                               double* flux_sum);
+int32_t gr_lagtransfer_bin(gr_ctx* ctx, const gr_lagprofile* profile, const double* E_edges, int64_t n_E,
+                           const double* t_edges, int64_t n_t, double* out /* host, n_E x n_t, row-major [E][t], raw Σf */);
+int32_t gr_lagtransfer_rows(gr_ctx* ctx, double* out /* host, n x 4 */);
+
 /* ---- tabulated metrics (ABI 7; segments, axis terms: ABI 8; GR_METRIC_TABULATED): the AbstractMetric plugin interface on the device ----
  * Host-only functions (no context, no device): plan a grid, learn its nodes, fit, check.
  *
