@@ -4065,6 +4065,19 @@ struct Ray {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) state_nan |= !(xn[i] == xn[i]) || !(vn[i] == vn[i]) || !(A[6][i] == A[6][i]);
                 if (state_nan) { flags |= GR_FLAG_NAN; return true; }
+#elif defined(GR_REAL_IS_FLOAT)
+                // Single precision: the NaN norm is, as a rule, a trial step that OVERFLOWED.  At tolerance 1e-3 .. 1e-4 the
+                // controller proposes h ≈ r to an ingoing ray at r ≈ 25; the stage points of that step lie inside the hole, the
+                // right-hand side there passes 3.4e38, and (x_new, v_new, A_7) hold inf and inf - inf.  The fp64 kernels and the
+                // oracle see EEst² ~ 1e22 .. 1e160 for the same step and reject it; flagging it instead ended rays in mid-flight
+                // (13 of 2304 NoZ rays at 1e-3: tests/test_f32_logic_host.py).  So: a step to reject (by the largest factor, as
+                // above) unless the step's BASE holds the NaN.  An accepted step leaves a finite base behind (its norm was <= 1),
+                // so that is a ray that started from a NaN; one that sits on a singular point (Bumblebee's horizon) runs down to
+                // dt < dtmin within a dozen rejections, as the oracle's does.
+                bool base_nan = false;      // (a NaN step size never gets here: the test at the top)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) base_nan |= !(x[i] == x[i]) || !(v[i] == v[i]) || !(A[0][i] == A[0][i]);
+                if (base_nan) { flags |= GR_FLAG_NAN; return true; }
 #else
                 flags |= GR_FLAG_NAN;
                 return true;
