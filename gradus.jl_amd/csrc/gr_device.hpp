@@ -704,9 +704,15 @@ struct KerrFamily {
     // invariants, and the allocator answers by keeping invariants in scratch that the five stages reload at every step (160 B, a
     // scratch load in the head, three stage blocks and the commit block); inlined, the block is one more rarely taken branch
     // like the event sampling and the parked values are stored and reloaded inside it (profiles/r11_static_counts.txt).
-    static GR_DEV_COLD real pass_cull_rmin(real M, real a, real E, real L, real Q, real u0, real uc, real up, real mu0, real vth, real gtol)
+    // It answers for two depth limits at once, up <= ud (DEFER CULL, Ray::start_decided): the closed forms run once with the deeper
+    // limit ud, and the value is positive where the turning point's bracket also clears up (u_hi <= up, the comparison the single
+    // limit made), negative where it lies between the two.  ud = up leaves the single limit.
+    static GR_DEV_COLD real pass_cull_rmin(real M, real a, real E, real L, real Q, real u0, real uc, real up, real ud, real mu0, real vth, real gtol)
     {
-        return pass_cull_rmin_inline(M, a, E, L, Q, u0, uc, up, mu0, vth, gtol);
+        PassBounds b;
+        if (!pass_cull_bounds(M, a, E, L, Q, u0, uc, ud, mu0, vth <= 0.0, gtol, b)) return 0.0;
+        const real r_min = rcp_full(b.u_hi);
+        return b.u_hi <= up ? r_min : -r_min;
     }
 #endif
 
@@ -2656,6 +2662,10 @@ struct Params {
     // at the step that takes it inside r_cull, down to kEntryCullZeta r_cull.  It needs r_cull, r_cull_start and r_pass finite
     // (each of their switches turns it off); 0 here turns it off alone.  1 = on is what derive_params leaves.
     int32_t entry_cull = 1;
+    // defer cull (Ray::start_decided, Ray::step): a ray the start's closed forms decide with a turning point between
+    // kDeferCullZeta r_cull and r_pass is traced for one accepted step and ends there.  It needs r_cull, r_cull_start and r_pass
+    // finite (each of their switches turns it off); 0 here turns it off alone.  1 = on is what derive_params leaves.
+    int32_t defer_cull = 1;
 };
 
 // the derived fields of Params, from cfg (host side; one place for the library and the two host harnesses)
@@ -2671,6 +2681,7 @@ static inline void derive_params(Params& p)
     p.r_cull_start = __builtin_inf();     // ... and so is the start cull
     p.r_pass = __builtin_inf();           // ... and its second test, the pass cull
     p.entry_cull = 1;                     // the entry cull is on wherever r_cull and r_pass both are (GRADUS_MI355X_ENTRY_CULL=0: launch_trace)
+    p.defer_cull = 1;                     // ... and so is the defer cull (GRADUS_MI355X_DEFER_CULL=0: launch_trace)
 }
 
 // The culls' gating radius as far as the configuration decides it (host side; one place for the launcher, escape_cull_radius in
@@ -2692,16 +2703,27 @@ static inline double cull_gate_radius(const gr_config& c, double escape_radius_M
 // The pass cull's radius R_pass = ζ R_cull (Ray::start_decided): rays that turn between R_pass and R_cull are the weak-field part
 // of the misses that dip inside R_cull.  ζ is as small as the bracket (0.62, 0.73) on the accepted-step ratio of
 // GRADUS_MI355X_ESCAPE_CULL unset over =0 allows (tests/test_gpu_escape_cull.py, tests/test_cull_host.py): a decision at the start
-// takes more from the ratio's denominator than from its numerator, a decision of the entry cull (Ray::step) is under that switch
-// and takes from the numerator alone.  With the entry cull the smallest ζ on a 0.01 grid that leaves the ratio at or under 0.70
-// (0.03 inside the bracket, for sampling) is 0.55: 0.687 on 1500 tiles, 0.667 on the 400 of the host tests; 0.54 gives 0.701.
-// Census behind the value: DESIGN.md §5a.
-constexpr double kPassCullZeta = 0.55;
+// takes more from the ratio's denominator than from its numerator, a decision of the entry cull or an end of the defer cull
+// (Ray::step) is under that switch and takes from the numerator alone.  With the entry cull and the defer cull (ζ_defer = 0.25) the
+// smallest ζ on a 0.01 grid that leaves the ratio at or under 0.70 (0.03 inside the bracket, for sampling) is 0.51: 0.679 on 1500
+// tiles, 0.644 on the 400 of the host tests; 0.50 gives 0.706.  Census behind the value: DESIGN.md §5a.
+constexpr double kPassCullZeta = 0.51;
 static inline double pass_cull_radius(double r_gate) { return r_gate < __builtin_inf() ? kPassCullZeta * r_gate : __builtin_inf(); }
 // The entry cull's depth limit R_dip = ζ_dip R_cull (Ray::step): the rays the start leaves undecided are asked again on entering
 // R_cull, with the same closed forms, if they turn outside R_dip.  Below 0.2 the census decides nothing more: deeper
 // rays fail the concavity condition or the harmonic bounds grow too loose.
 constexpr double kEntryCullZeta = 0.2;
+// The defer cull's depth limit R_defer = ζ_defer R_cull (Ray::start_decided): a ray the start's closed forms decide with a turning
+// point in [R_defer, R_pass) keeps its inbound leg's decision but is charged one accepted step (Ray::step), so that it counts on
+// both sides of the GRADUS_MI355X_ESCAPE_CULL switch.  ζ_dip < ζ_defer < ζ: the entry cull keeps the band [ζ_dip, ζ_defer) R_cull
+// of its own, which the host tests of the entry cull ask to be populated: 0.25 is the smallest value on a 0.05 grid above ζ_dip, and
+// it leaves the entry cull 153 rays on the 400 bench tiles of those tests and 17 or more in each of their 64² scenes that had ten
+// without the defer cull.  Census behind the value: DESIGN.md §5a.  (The macro is for that census alone: scripts/cull_census.py
+// --defer-zeta builds the host harness at other values.)
+#ifndef GR_DEFER_CULL_ZETA
+#define GR_DEFER_CULL_ZETA 0.25
+#endif
+constexpr double kDeferCullZeta = GR_DEFER_CULL_ZETA;
 
 // Small read-mostly tables staged in LDS by the kernel prologue (null = use the global copy):
 // the PlungingInterpolation table of the non-Kerr redshift and the per-workgroup private copy of
@@ -2926,6 +2948,8 @@ struct TabLds : Base {
 // The per-lane integrator.
 // ---------------------------------------------------------------------------------------
 enum : int32_t {
+    RAY_DEFER_DECIDED = 0x40,    // bit in Ray::flags of a ray the start decided with a turning point deeper than R_pass: it ends at its
+                                 // first accepted step (Ray::start_decided, Ray::step)
     RAY_ENTRY_ARMED = 0x80,      // bit in Ray::flags of an ingoing ray that started outside R_cull undecided, until the entry cull has
                                  // been asked for it (Ray::init, Ray::step); below RAY_NO_CULL, whose test is one unsigned compare
     RAY_EVENT = 0x100,     // bit in Ray::flags while a disc event awaits its root find
@@ -3459,7 +3483,12 @@ struct Ray {
     // wedge |μ| <= gtol only outside R_cull, by two-sided bounds on its radial and polar Mino times, is decided the same way
     // (Metric::pass_cull_bounds holds the statement, the closed forms and the margins).  The bound of 3 is then formed at the
     // smallest r of the path, the lower end of r_t's bracket, where B is largest.  A switch of its own: r_pass = +inf is off.
-    GR_DEV bool start_decided(const Metric& m, const Params& p) const
+    // DEFER CULL: the same single evaluation also answers for the deeper limit R_defer = kDeferCullZeta R_cull.  A ray it decides
+    // with R_defer <= r_t < R_pass (every precondition and the bound of 3 verified as for the others) is not ended here: it is
+    // traced, and step() ends it at its first accepted step (RAY_DEFER_DECIDED).  Asked only with Params::defer_cull != 0 and
+    // r_cull finite; without them the limit is R_pass alone, as before.
+    // Returns 0: traced; 1: decided; 2: decided, to end at the first accepted step.
+    GR_DEV int start_decided(const Metric& m, const Params& p) const
     {
         real s, c, g[5];
         sincos_fast(x[2], s, c);
@@ -3470,17 +3499,22 @@ struct Ray {
         real R, R1, R2;
         m.radial_potential(rc, E, L, Q, R, R1, R2);
         real r_min = rc;      // the smallest r of the path, for the bound of 3
+        int decided = 1;
         if (!(R < -1e-6 * ((E * E) * (rc2 * rc2)))) {
 #if GR_HAS_PASS_CULL
-            if (!((real)p.r_pass < (real)__builtin_inf()) || !(v[1] < 0.0)) return false;
-            r_min = Metric::pass_cull_rmin(m.M, m.a, E, L, Q, rcp_full(x[1]), rcp_full(rc), rcp_full((real)p.r_pass), c, v[2], (real)p.cfg.gtol);
-            if (!(r_min > 0.0)) return false;
+            if (!((real)p.r_pass < (real)__builtin_inf()) || !(v[1] < 0.0)) return 0;
+            const real up = rcp_full((real)p.r_pass);
+            const bool defer = p.defer_cull != 0 && (real)p.r_cull < (real)__builtin_inf();
+            const real ud = defer ? rcp_full((real)kDeferCullZeta * rc) : up;
+            r_min = Metric::pass_cull_rmin(m.M, m.a, E, L, Q, rcp_full(x[1]), rcp_full(rc), up, ud, c, v[2], (real)p.cfg.gtol);
+            if (r_min < 0.0) { r_min = -r_min; decided = 2; }
+            if (!(r_min > 0.0)) return 0;
 #else
-            return false;
+            return 0;
 #endif
         }
         const real reach = GR_FMA(m.radial_speed_bound(r_min, E, L), (real)p.cfg.lambda1 - (real)p.cfg.lambda0, x[1]);
-        return reach * (1.0 + 1e-6) < (real)p.cfg.r_outer;
+        return reach * (1.0 + 1e-6) < (real)p.cfg.r_outer ? decided : 0;
     }
 
     // reinit! + auto_dt_reset! (tracing.jl:234-243; App. A.4).  Returns true when the ray is decided without a step (the start
@@ -3497,14 +3531,17 @@ struct Ray {
         lq_old = (float)LOG2_QOLDINIT;
         if constexpr (kEscapeCull) {
             if (x[1] > (real)p.r_cull_start) {
-                if (start_decided(m, p)) {
+                const int decided = start_decided(m, p);
+                if (decided == 1) {
                     t = p.cfg.lambda1;
                     return true;
                 }
 #if GR_HAS_PASS_CULL
                 // the entry cull is armed (step()): the start test was asked and left the ray undecided, it goes in, the pass
-                // cull is on.  A ray that starts inside R_cull is never armed.
-                if (v[1] < 0.0 && (real)p.r_pass < (real)__builtin_inf() && p.entry_cull != 0) flags = RAY_ENTRY_ARMED;
+                // cull is on.  A ray that starts inside R_cull is never armed.  A ray decided for the deeper limit alone is
+                // traced like an undecided one, armed or not, and carries the defer cull's bit on top.
+                if (v[1] < 0.0 && (real)p.r_pass < (real)__builtin_inf())
+                    flags = (p.entry_cull != 0 ? RAY_ENTRY_ARMED : 0) | (decided == 2 ? RAY_DEFER_DECIDED : 0);
 #endif
             }
         }
@@ -3998,11 +4035,21 @@ struct Ray {
             // E, L, Q come from the current state; the bound of 3 is formed at the lower end of the turning point's bracket, the
             // smallest r of the path, with the current λ, and a failure sets RAY_NO_CULL.  The common path pays the bit test; the
             // closed forms are inlined into this block (why: Metric::pass_cull_rmin).
+            //
+            // DEFER CULL: a ray that Ray::init marked RAY_DEFER_DECIDED is a miss by the start's own decision (start_decided: the
+            // pass cull's closed forms with the depth limit R_defer, and the λ1-first bound from the start state).  It ends at its
+            // first accepted step with R_cull finite, like every early end in this loop; with R_cull = +inf the bit is dropped and
+            // the ray is traced in full.  RAY_ENTRY_ARMED is left as it is on that path: the entry cull was not asked.  The
+            // common path tests both bits with one compare.
             if constexpr (kEscapeCull) {
 #if GR_HAS_PASS_CULL
-                if (flags & RAY_ENTRY_ARMED) {
+                if (flags & (RAY_ENTRY_ARMED | RAY_DEFER_DECIDED)) {
                     const real rc = (real)p.r_cull;
-                    if (x[1] <= rc) {
+                    if (flags & RAY_DEFER_DECIDED) {
+                        // DEFER CULL: the start decided this ray (start_decided, 2) and this is its first accepted step
+                        flags &= ~RAY_DEFER_DECIDED;
+                        if (rc < (real)__builtin_inf()) t = tend;
+                    } else if (x[1] <= rc) {
                         flags &= ~RAY_ENTRY_ARMED;
                         if (rc < (real)__builtin_inf() && cprev > 0.0 && v[1] < 0.0 && (uint32_t)flags < (uint32_t)RAY_NO_CULL) {
                             real g[5];
@@ -4372,7 +4419,7 @@ struct Ray {
             resolve_event(p);
             flags &= ~RAY_EVENT;
         }
-        if constexpr (kEscapeCull) flags &= ~(RAY_NO_CULL | RAY_ENTRY_ARMED);      // step-loop bits like RAY_EVENT, not anomalies
+        if constexpr (kEscapeCull) flags &= ~(RAY_NO_CULL | RAY_ENTRY_ARMED | RAY_DEFER_DECIDED);      // step-loop bits like RAY_EVENT, not anomalies
         if (flags & GR_FLAG_MASK) status = GR_STATUS_NO_STATUS;
         const Cold& cd = cold_of(p);
         if (cd.tile_cost) {

@@ -729,12 +729,13 @@ static int32_t sky_prepare(gr_ctx* ctx, Params& p, Cold& cold, hipStream_t strea
 //              (μ = 0) traced forward (λ1 > λ0);
 //   callbacks: no hemisphere, PoloidalShapeChart or winding callback (any of them can set a status after the cull point);
 //   precision: the fp64 kernels (lane and persistent); not fp32, not the tangent kernels.
-// Four switches in the environment, read at every launch (A/B of one build), each on its own mechanism (launch_trace):
+// Five switches in the environment, read at every launch (A/B of one build), each on its own mechanism (launch_trace):
 // GRADUS_MI355X_ESCAPE_CULL=0 -- no ray ends early inside the step loop (the escape, polar-rate and entry culls);
 // GRADUS_MI355X_START_CULL=0 -- no ray is decided at its start (the start cull and the pass cull, Params::r_pass = pass_cull_radius);
 // GRADUS_MI355X_PASS_CULL=0 -- the pass cull alone is off.  The entry cull (Ray::step) asks the pass cull's question inside the step
 // loop and is armed at the start, so each of the three turns it off as well; GRADUS_MI355X_ENTRY_CULL=0 (Params::entry_cull) turns
-// it off alone.
+// it off alone.  The defer cull (Ray::start_decided, Ray::step) is decided by the pass cull at the start and ends its rays in the
+// step loop: each of the three turns it off too, and GRADUS_MI355X_DEFER_CULL=0 (Params::defer_cull) turns it off alone.
 static bool cull_switched_off(const char* name)
 {
     const char* sw = std::getenv(name);
@@ -816,6 +817,7 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
         p.r_cull_start = cull_switched_off("GRADUS_MI355X_START_CULL") ? HUGE_VAL : r_gate;
         p.r_pass = cull_switched_off("GRADUS_MI355X_PASS_CULL") ? HUGE_VAL : pass_cull_radius(p.r_cull_start);
         p.entry_cull = cull_switched_off("GRADUS_MI355X_ENTRY_CULL") ? 0 : 1;
+        p.defer_cull = cull_switched_off("GRADUS_MI355X_DEFER_CULL") ? 0 : 1;
     }
     LaunchKnobs knobs{ kern_sel, block_sel, ctx->n_cu, (int)ctx->waves_per_simd,
                        ctx->d_queue + ctx->queue_next };

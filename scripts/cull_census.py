@@ -20,8 +20,17 @@ With --entry-cull the same tiles go through tests/host_harness_entry_cull.cpp: t
 the disc (must be 0), the ratios the entry cull leaves and the GRADUS_MI355X_ESCAPE_CULL switch ratio.  --ref-zeta Z adds the
 wave-steps and accepted steps relative to a library with R_pass = Z R_cull and no entry cull (0.75: the one before the entry cull).
 
+With --defer-cull the same tiles go through tests/host_harness_defer_cull.cpp: the library as shipped ("all"), the defer cull
+(Ray::start_decided, Ray::step) off alone ("no-defer"), the step loop's culls off ("start") and every cull off ("full"), at the
+library's ζ and ζ_defer or at --zeta and --defer-zeta (the latter builds the harness with that constant).  The result gains a
+"defer_cull" entry: steps and wave-steps of the arms, how many rays the start marked, how many the defer cull and the entry cull
+ended (and how many of all early ends hit the disc: must be 0), the ratios the defer cull leaves and the
+GRADUS_MI355X_ESCAPE_CULL switch ratio.  --ref-zeta Z adds the steps relative to R_pass = Z R_cull without the defer cull (0.55:
+the library before it).
+
     python scripts/cull_census.py [--tiles 1000] [--seed 1] [--pass-cull [--zeta 0.72] [--pass-only]]
     python scripts/cull_census.py --tiles 1500 --seed 3 --entry-cull --pass-only [--zeta 0.60] [--ref-zeta 0.75]
+    python scripts/cull_census.py --tiles 1500 --seed 3 --defer-cull --pass-only [--zeta 0.50] [--defer-zeta 0.35] [--ref-zeta 0.55]
 """
 from __future__ import annotations
 
@@ -101,21 +110,50 @@ def entry_census(tiles=1000, seed=1, zeta=-1.0, ref_zeta=None):
     return res
 
 
+def defer_census(tiles=1000, seed=1, zeta=-1.0, defer_zeta=None, ref_zeta=None):
+    """The defer cull's arms on the tiles census() draws for the same arguments (zeta < 0, defer_zeta None: the library's)."""
+    import gradus_jl_amd as G
+    import harness_defer_cull as Hd
+
+    cfg, pf = bench_scene(G)
+    nt = SIZE // 8
+    picks = np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
+    res, _ = Hd.census(G, cfg, pf, picks, zeta, defer_zeta)
+    res["seed"] = int(seed)
+    res["zeta"] = Hd.zeta() if zeta < 0 else float(zeta)
+    res["zeta_defer"] = Hd.zeta_defer(defer_zeta)
+    res["zeta_dip"] = Hd.zeta_dip()
+    res["r_cull"] = Hd.gate_radius(cfg)
+    if ref_zeta is not None:
+        ref = Hd.render_tiles(G, cfg, pf, picks, 1, 1, 1, 0, ref_zeta, defer_zeta)
+        att = ref["nacc"].astype(np.int64) + ref["nrej"]
+        res["ref_zeta"] = float(ref_zeta)
+        res["wave_steps_vs_ref"] = res["arms"]["all"]["wave_steps"] / int(att.max(axis=1).sum())
+        res["accepted_steps_vs_ref"] = res["arms"]["all"]["accepted_steps"] / int(ref["nacc"].sum())
+        res["attempted_steps_vs_ref"] = res["arms"]["all"]["attempted_steps"] / int(att.sum())
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--pass-cull", action="store_true", help="add the pass cull's arms")
     ap.add_argument("--zeta", type=float, default=-1.0, help="R_pass / R_cull (default: the library's constant)")
-    ap.add_argument("--pass-only", action="store_true", help="with --pass-cull or --entry-cull: skip the four arms of the older culls")
+    ap.add_argument("--pass-only", action="store_true", help="with --pass-cull, --entry-cull or --defer-cull: skip the four arms of the older culls")
     ap.add_argument("--entry-cull", action="store_true", help="add the entry cull's arms")
-    ap.add_argument("--ref-zeta", type=float, default=None, help="with --entry-cull: compare with R_pass / R_cull = this and no entry cull")
+    ap.add_argument("--ref-zeta", type=float, default=None,
+                    help="with --entry-cull / --defer-cull: compare with R_pass / R_cull = this and no entry / defer cull")
+    ap.add_argument("--defer-cull", action="store_true", help="add the defer cull's arms")
+    ap.add_argument("--defer-zeta", type=float, default=None, help="R_defer / R_cull (default: the library's constant)")
     a = ap.parse_args()
-    res = {} if ((a.pass_cull or a.entry_cull) and a.pass_only) else census(a.tiles, a.seed)
+    res = {} if ((a.pass_cull or a.entry_cull or a.defer_cull) and a.pass_only) else census(a.tiles, a.seed)
     if a.pass_cull:
         res["pass_cull"] = pass_census(a.tiles, a.seed, a.zeta)
     if a.entry_cull:
         res["entry_cull"] = entry_census(a.tiles, a.seed, a.zeta, a.ref_zeta)
+    if a.defer_cull:
+        res["defer_cull"] = defer_census(a.tiles, a.seed, a.zeta, a.defer_zeta, a.ref_zeta)
     print(json.dumps(res, indent=1))
 
 
