@@ -57,6 +57,15 @@ gs = np.linspace(0.0, 1.2, 500)
 (_, flux), dt = timed(lambda: G.lineprofile(gs, lambda r: r ** -3.0, m, x, d, maxrₑ=50.0, ensemble=ens))
 print(f"line profile (100 transfer functions + integration): {dt:.2f} s, peak at g = {gs[int(np.argmax(flux))]:.3f}")
 
+# ## A table of transfer functions -> one line profile per fit iteration, integrated on the device
+table = G.make_transfer_function_table(G.KerrMetric, G.ThinDisc(0.0, float("inf")), [0.9, 0.998], [30.0, 60.0], n_radii=30, ensemble=ens)
+point = table(0.95, 40.0)          # a CunninghamTransferGrid between the lattice points
+(flux, dt) = timed(lambda: G.integrate_lineprofile(lambda r: r ** -3.0, point, gs, rmax=50.0, ensemble=ens))
+fits, dt64 = timed(lambda: G.integrate_lineprofiles([lambda r, q=q: r ** -q for q in np.linspace(2.0, 4.0, 64)], [point] * 64, gs,
+                                                    rmax=50.0, ensemble=ens))
+print(f"table point -> line profile on the device: {1e3 * dt:.1f} ms, 64 emissivities in one call: {1e3 * dt64:.1f} ms, "
+      f"peak at g = {gs[int(np.argmax(flux))]:.3f}")
+
 # ## Reverberation transfer functions: binning ...
 x = np.array([0.0, 1000.0, math.radians(60), 0.0])
 d = G.ThinDisc(0.0, 1000.0)

@@ -34,7 +34,7 @@ from .tracing import (EnsembleMI355X, TraceGeodesic, TraceWindings, winding_numb
 from .transfer_functions import (CunninghamTransferData, CunninghamTransferGrid, CunninghamTransferTable,
                                 make_transfer_function_table, transfer_function_grid, InterpolatingTransferBranches, TransferBranches,
                                 cunningham_transfer_function, cunningham_transfer_functions, integrate_lagtransfer,
-                                integrate_lineprofile,
+                                integrate_lineprofile, integrate_lineprofiles,
                                 interpolate_branches, splitbranches, transferfunctions)
 from .reverberation import (AnalyticRadialDiscProfile, DeviceLagTransfer, LagTransferFunction, bin_transfer_function, binflux,
                             continuum_time, lag_frequency,

@@ -26,7 +26,7 @@ def kernel_source_sha16() -> str:
     h = hashlib.sha256()
     root = os.path.dirname(_HERE)
     for rel in ("gradus.jl_amd/csrc/gr_device.hpp", "gradus.jl_amd/csrc/gr_kernels.hpp", "gradus.jl_amd/csrc/gr_tangent.hpp",
-                "gradus.jl_amd/csrc/gr_tabmetric.hpp", "gradus.jl_amd/csrc/gr_lagbin.hpp", "gradus.jl_amd/csrc/metric_table.hip",
+                "gradus.jl_amd/csrc/gr_tabmetric.hpp", "gradus.jl_amd/csrc/gr_lagbin.hpp", "gradus.jl_amd/csrc/gr_tfint.hpp", "gradus.jl_amd/csrc/metric_table.hip",
                 "gradus.jl_amd/csrc/kernels_tu.hip",
                 "gradus.jl_amd/csrc/gradus_mi355x.hip",
                 "include/gradus_mi355x.h"):
@@ -246,6 +246,34 @@ class gr_lagprofile(C.Structure):
     ]
 
 
+class gr_tfset(C.Structure):
+    """One parameter set of gr_tf_lineprofile / gr_tf_lagtransfer: the branches of n_r emission radii (ragged knots behind
+    `off`) and the annuli of the integration with ε and the source -> disc time evaluated at each."""
+
+    _fields_ = [
+        ("n_r", C.c_int64),
+        ("radii", C.c_void_p),
+        ("gmin", C.c_void_p),
+        ("gmax", C.c_void_p),
+        ("off", C.c_void_p),
+        ("knot_g", C.c_void_p),
+        ("knot_f", C.c_void_p),
+        ("knot_t", C.c_void_p),
+        ("n_int", C.c_int64),
+        ("r_int", C.c_void_p),
+        ("eps_int", C.c_void_p),
+        ("tsd_int", C.c_void_p),
+        ("r_min", C.c_double),
+        ("g_scale", C.c_double),
+    ]
+
+
+class gr_tfquad(C.Structure):
+    """integrate_bin's edge width and the quadrature rule on [-1, 1]"""
+
+    _fields_ = [("h", C.c_double), ("n_q", C.c_int64), ("x", C.c_void_p), ("w", C.c_void_p)]
+
+
 class gr_stats(C.Structure):
     _fields_ = [
         ("rays", C.c_int64),
@@ -327,6 +355,8 @@ EXPORTS = [
     "gr_lagtransfer_extrema",
     "gr_lagtransfer_bin",
     "gr_lagtransfer_rows",
+    "gr_tf_lineprofile",
+    "gr_tf_lagtransfer",
     "gr_render_endpoints_multi",
     "gr_trace_endpoints_multi",
     "gr_rayset_endpoints_multi",
@@ -398,6 +428,9 @@ def load():
     L.gr_lagtransfer_extrema.argtypes = [vp, lpp, vp, vp]
     L.gr_lagtransfer_bin.argtypes = [vp, lpp, vp, i64, vp, i64, vp]
     L.gr_lagtransfer_rows.argtypes = [vp, vp]
+    tsp, tqp = C.POINTER(gr_tfset), C.POINTER(gr_tfquad)
+    L.gr_tf_lineprofile.argtypes = [vp, tsp, i64, tqp, vp, i64, vp]
+    L.gr_tf_lagtransfer.argtypes = [vp, tsp, i64, tqp, vp, i64, vp, i64, vp]
     ctxa = C.POINTER(vp)
     L.gr_render_endpoints_multi.argtypes = [ctxa, i32, cfgp, plp, i64, vp, vp]
     L.gr_trace_endpoints_multi.argtypes = [ctxa, i32, cfgp, vp, i64, vp, i64, vp, vp]

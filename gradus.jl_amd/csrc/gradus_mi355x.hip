@@ -28,6 +28,7 @@
 #include "gr_device.hpp"
 #include "gr_mesh_grid.hpp"
 #include "gr_lagbin.hpp"
+#include "gr_tfint.hpp"
 
 using namespace gr;
 
@@ -165,6 +166,7 @@ struct gr_ctx {
     int64_t lds_points = 1;                // one-ray-per-lane kernel: a wave's end-point records leave through LDS as whole runs
     int64_t direct_host = 1;               // gr_render_endpoints into a gr_host_alloc block: the kernel stores across the link itself
     int64_t tangent_pairs = 2;             // tangent kernels: 0 = one lane per ray, 1 = a pair of lanes per ray, 2 = by launch size
+    int64_t tf_chunk = 0;                  // gr_tf_lineprofile / gr_tf_lagtransfer: annuli per workgroup, 0 = auto (the launch shape only)
     int64_t sky_deal = 1;                  // gr_corona_trace: the sky rays of a source dealt to the waves by predicted cost (k_sky_velocities_dealt)
     int64_t xcd_spread = 1;                // one-ray-per-lane kernel, rays in caller order: chunks dealt over the XCDs by digit sum
     int64_t tangent_norm = 1;              // tangent kernels: the tangents are part of the error norm (DiffEqBase on Dual state); 0 = values only
@@ -1162,6 +1164,9 @@ int32_t gr_ctx_set(gr_ctx* c, const char* key, int64_t value)
         c->xcd_spread = value ? 1 : 0;
     } else if (k == "sky_deal") {
         c->sky_deal = value ? 1 : 0;
+    } else if (k == "tf_chunk") {
+        if (value < 0 || value > 65536) return fail(GR_ERR_INVALID_ARGUMENT, "tf_chunk must be in [0, 65536] (0 = auto)");
+        c->tf_chunk = value;
     } else if (k == "lds_points") {
         c->lds_points = value ? 1 : 0;
     } else if (k == "direct_host") {
@@ -2513,6 +2518,79 @@ __global__ void __launch_bounds__(256) k_lag_bin(const double* __restrict__ rows
     }
 }
 
+// ---- transfer functions into flux per bin: integrate_lineprofile / integrate_lagtransfer (integration.jl:336-453); the
+// arithmetic per (annulus, g bin) is gr_tfint.hpp ----
+// Workgroup b serves set b / n_chunks and the annuli [c chunk, (c + 1) chunk) of it, c = b % n_chunks: a wave takes one annulus
+// at a time (its radial blend and weight are wave-uniform), its lanes the g bins.  PASS 0: the largest |deposit| of every set
+// (red[set], the bits of a non-negative double).  PASS 1: every deposit as two integers on the set's fixed-point grid sc[set],
+// acc[set][cell] = Σ hi, acc[set][cells + cell] = Σ lo with cell = j (line profile) or j n_t + i_t (LAG) -- integer sums do
+// not depend on the order of the additions, so the launch shape does not show in the result.  LDS = 1: the set's histogram is
+// private to the workgroup in LDS (2 x 8 x cells bytes, at most 40 KB) and leaves as one global atomic per non-empty entry.
+template <int LAG, int PASS, int LDS>
+__global__ void __launch_bounds__(256) k_tf(const gr_tf::Set* __restrict__ sets, gr_tf::Quad quad, const double* __restrict__ g_edges, int n_g,
+                                            const double* __restrict__ t_edges, int n_t, int chunk, int n_chunks,
+                                            unsigned long long* red, const CoronaScale* __restrict__ sc, unsigned long long* acc)
+{
+    extern __shared__ unsigned long long tf_hist[];
+    const int set = (int)(blockIdx.x / (unsigned)n_chunks), c = (int)(blockIdx.x % (unsigned)n_chunks);
+    const gr_tf::Set s = sets[set];
+    const int cells = LAG ? n_g * n_t : n_g;
+    unsigned long long* h = nullptr;
+    CoronaScale scale{};
+    if (PASS == 1) {
+        acc += (size_t)set * 2 * (size_t)cells;
+        h = LDS ? tf_hist : acc;
+        scale = sc[set];
+        if (LDS) {
+            for (int i = threadIdx.x; i < 2 * cells; i += blockDim.x) tf_hist[i] = 0ull;
+            __syncthreads();
+        }
+    }
+    const int64_t a0 = (int64_t)c * chunk, a1 = a0 + chunk < s.n_int ? a0 + chunk : s.n_int;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned long long vmax = 0ull;
+    for (int64_t ia = a0 + wave; ia < a1; ia += 4) {
+        const gr_tf::Annulus an = gr_tf::annulus_of(s, ia);
+        for (int j = lane; j < n_g - 1; j += 64) {
+            double v[2];
+            int cell[2] = { -1, -1 };
+            if (LAG) {
+                int it[2];
+                if (gr_tf::lag_deposits(s, an, quad, g_edges, j, t_edges, n_t, v, it)) {
+                    if (it[0] < n_t) cell[0] = j * n_t + it[0];
+                    if (it[1] < n_t) cell[1] = j * n_t + it[1];
+                }
+            } else if (gr_tf::line_deposit(s, an, quad, g_edges, j, v[0])) {
+                cell[0] = j;
+            }
+#pragma unroll
+            for (int k = 0; k < (LAG ? 2 : 1); ++k) {
+                if (cell[k] < 0) continue;
+                if (PASS == 0) {
+                    const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(v[k]));
+                    vmax = b > vmax ? b : vmax;
+                } else {
+                    long long fh, fl;
+                    corona_split(v[k], scale, fh, fl);
+                    atomicAdd(h + cell[k], (unsigned long long)fh);
+                    atomicAdd(h + cells + cell[k], (unsigned long long)fl);
+                }
+            }
+        }
+    }
+    if (PASS == 0) {
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_down(vmax, off, 64);
+            vmax = o > vmax ? o : vmax;
+        }
+        if (lane == 0 && vmax) atomicMax(red + set, vmax);
+    } else if (LDS) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * cells; i += blockDim.x)
+            if (tf_hist[i] != 0ull) atomicAdd(acc + i, tf_hist[i]);
+    }
+}
+
 int32_t rayset_share(const gr_rayset* rays, int32_t n, int k, gr_rayset& out, int64_t* off_out);      // (below, with the other *_multi helpers)
 }  // namespace
 }  // extern "C++"
@@ -2905,6 +2983,166 @@ int32_t gr_lagtransfer_rows(gr_ctx* ctx, double* out)
     if (ctx->lag_n > 0) GR_HIP(hipMemcpyAsync(out, ctx->d_lag, sizeof(double) * 4 * (size_t)ctx->lag_n, hipMemcpyDeviceToHost, ctx->stream));
     GR_HIP(hipStreamSynchronize(ctx->stream));
     return GR_OK;
+}
+
+// ---- transfer functions integrated on the device: gr_tf_lineprofile / gr_tf_lagtransfer ----
+// the checks that read only the arguments, before anything touches the device
+static int32_t tf_args(const gr_tfset* sets, int64_t n_sets, const gr_tfquad* quad, const double* g_edges, int64_t n_g,
+                       const double* t_edges, int64_t n_t, bool lag, const double* out)
+{
+    if (!sets) return fail(GR_ERR_INVALID_ARGUMENT, "sets is null");
+    if (!quad) return fail(GR_ERR_INVALID_ARGUMENT, "quad is null");
+    if (!g_edges) return fail(GR_ERR_INVALID_ARGUMENT, "g edges are null");
+    if (lag && !t_edges) return fail(GR_ERR_INVALID_ARGUMENT, "t edges are null");
+    if (!out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
+    if (n_sets < 1) return fail(GR_ERR_INVALID_ARGUMENT, "n_sets must be at least 1");
+    if (n_g < 2) return fail(GR_ERR_INVALID_ARGUMENT, "g axis: at least two edges");
+    if (lag && n_t < 2) return fail(GR_ERR_INVALID_ARGUMENT, "t axis: at least two edges");
+    const int64_t lim = (int64_t)1 << 24;
+    if (n_sets > lim || n_g > lim || n_t > lim || n_sets * n_g > lim || n_sets * n_g * n_t > lim)
+        return fail(GR_ERR_INVALID_ARGUMENT, "at most 2^24 cells (n_sets * n_g * n_t)");
+    if (!quad->x || !quad->w) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfquad: nodes / weights are null");
+    if (quad->n_q < 1 || quad->n_q > gr_tf::kMaxQuad) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfquad: n_q must be in 1 ... 32");
+    for (int64_t k = 0; k < n_sets; ++k) {
+        const gr_tfset& s = sets[k];
+        const std::string who = "gr_tfset " + std::to_string(k) + ": ";
+        if (s.n_r < 2) return fail(GR_ERR_INVALID_ARGUMENT, who + "n_r >= 2 emission radii are needed");
+        if (s.n_int < 2) return fail(GR_ERR_INVALID_ARGUMENT, who + "n_int >= 2 annuli are needed");
+        if (s.n_r > lim || s.n_int > lim) return fail(GR_ERR_INVALID_ARGUMENT, who + "at most 2^24 radii / annuli");
+        if (!s.radii || !s.gmin || !s.gmax || !s.off || !s.knot_g || !s.knot_f || !s.knot_t)
+            return fail(GR_ERR_INVALID_ARGUMENT, who + "a transfer-function array is null");
+        if (!s.r_int || !s.eps_int || (lag && !s.tsd_int)) return fail(GR_ERR_INVALID_ARGUMENT, who + "an annulus array is null");
+        if (s.off[0] < 0) return fail(GR_ERR_INVALID_ARGUMENT, who + "offsets must ascend from off[0] >= 0");
+        for (int64_t i = 0; i < 2 * s.n_r; ++i) {
+            const int64_t n = s.off[i + 1] - s.off[i];
+            if (s.off[i + 1] < s.off[i]) return fail(GR_ERR_INVALID_ARGUMENT, who + "offsets must ascend");
+            if (n < 2 || n > gr_tf::kMaxKnots) return fail(GR_ERR_INVALID_ARGUMENT, who + "a branch needs 2 ... 1024 knots");
+        }
+    }
+    return GR_OK;
+}
+
+// Both calls: stage every set in one block (descriptors, edges, arrays), find each set's largest deposit, accumulate on the
+// grids that gives, read the integers back.  The block is the context's input scratch or, beyond 32 MiB, a buffer of this call.
+static int32_t tf_integrate(gr_ctx* ctx, const gr_tfset* sets, int64_t n_sets, const gr_tfquad* quad, const double* g_edges, int64_t n_g,
+                            const double* t_edges, int64_t n_t, bool lag, double* out)
+{
+    int32_t rc;
+    if ((rc = tf_args(sets, n_sets, quad, g_edges, n_g, t_edges, n_t, lag, out)) != GR_OK) return rc;
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!lag) n_t = 1;
+    GR_HIP(hipSetDevice(ctx->device));
+    const size_t ns = (size_t)n_sets, cells = (size_t)(n_g * n_t);
+    // layout in units of 8 bytes: descriptors | g edges | t edges | per set: radii gmin gmax r_int eps tsd off kg kf kt
+    static_assert(sizeof(gr_tf::Set) % 8 == 0 && sizeof(CoronaScale) == 16, "8-byte units");
+    const size_t desc_w = ns * (sizeof(gr_tf::Set) / 8);
+    size_t words = desc_w + (size_t)n_g + (lag ? (size_t)n_t : 0);
+    int64_t max_int = 0;
+    for (size_t k = 0; k < ns; ++k) {
+        const gr_tfset& s = sets[k];
+        words += 3 * (size_t)s.n_r + 3 * (size_t)s.n_int + (2 * (size_t)s.n_r + 1) + 3 * (size_t)(s.off[2 * s.n_r] - s.off[0]);
+        max_int = s.n_int > max_int ? s.n_int : max_int;
+    }
+    const size_t up_w = words;                                   // what is uploaded; behind it: red | scales | acc
+    const size_t red_w = up_w, sc_w = red_w + ns, acc_w = sc_w + 2 * ns;
+    const size_t bytes = 8 * (acc_w + 2 * ns * cells) + 64;
+    void* own = nullptr;
+    struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } free_own{own};
+    char* base;
+    if (bytes > ((size_t)32 << 20)) {
+        GR_HIP(hipMalloc(&own, bytes));
+        base = (char*)own;
+    } else {
+        if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, bytes)) != GR_OK) return rc;
+        base = (char*)ctx->d_in;
+    }
+    std::vector<uint64_t> blob(up_w);
+    const double* d0 = (const double*)base;
+    size_t at = desc_w;
+    auto put = [&](const void* src, size_t n) {
+        std::memcpy(blob.data() + at, src, 8 * n);
+        const double* d = d0 + at;
+        at += n;
+        return d;
+    };
+    const double* d_g = put(g_edges, (size_t)n_g);
+    const double* d_t = lag ? put(t_edges, (size_t)n_t) : d_g;
+    for (size_t k = 0; k < ns; ++k) {
+        const gr_tfset& s = sets[k];
+        const size_t nr = (size_t)s.n_r, ni = (size_t)s.n_int, nk = (size_t)(s.off[2 * s.n_r] - s.off[0]);
+        gr_tf::Set d;
+        d.n_r = s.n_r; d.n_int = s.n_int; d.r_min = s.r_min; d.g_scale = s.g_scale;
+        d.radii = put(s.radii, nr); d.gmin = put(s.gmin, nr); d.gmax = put(s.gmax, nr);
+        d.r_int = put(s.r_int, ni); d.eps = put(s.eps_int, ni);
+        d.tsd = lag ? put(s.tsd_int, ni) : d.eps;
+        int64_t* off = (int64_t*)(blob.data() + at);
+        d.off = (const int64_t*)put(s.off, 2 * nr + 1);
+        for (size_t i = 0; i <= 2 * nr; ++i) off[i] -= s.off[0];             // (the staged knots begin at the set's first)
+        d.kg = put(s.knot_g + s.off[0], nk); d.kf = put(s.knot_f + s.off[0], nk); d.kt = put(s.knot_t + s.off[0], nk);
+        std::memcpy(blob.data() + k * (sizeof(gr_tf::Set) / 8), &d, sizeof d);
+    }
+    gr_tf::Quad q{};
+    q.h = quad->h; q.n = (int)quad->n_q;
+    for (int i = 0; i < q.n; ++i) { q.x[i] = quad->x[i]; q.w[i] = quad->w[i]; }
+    unsigned long long* d_red = (unsigned long long*)base + red_w;
+    CoronaScale* d_sc = (CoronaScale*)((unsigned long long*)base + sc_w);
+    unsigned long long* d_acc = (unsigned long long*)base + acc_w;
+    GR_HIP(hipMemcpyAsync(base, blob.data(), 8 * up_w, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemsetAsync(d_red, 0, 8 * (acc_w - red_w + 2 * ns * cells), ctx->stream));
+    // annuli per workgroup: one per wave unless that makes more than 2^16 workgroups
+    int64_t chunk = ctx->tf_chunk;
+    if (chunk <= 0) {
+        chunk = 4;
+        while ((int64_t)ns * ((max_int + chunk - 1) / chunk) > 65536) chunk *= 2;
+    }
+    const int64_t n_chunks = (max_int + chunk - 1) / chunk;
+    if ((int64_t)ns * n_chunks > ((int64_t)1 << 30)) return fail(GR_ERR_INVALID_ARGUMENT, "tf_chunk: more than 2^30 workgroups");
+    const dim3 grid((unsigned)((int64_t)ns * n_chunks)), block(256);
+    const gr_tf::Set* d_sets = (const gr_tf::Set*)base;
+    if (lag) hipLaunchKernelGGL((k_tf<1, 0, 0>), grid, block, 0, ctx->stream, d_sets, q, d_g, (int)n_g, d_t, (int)n_t, (int)chunk, (int)n_chunks, d_red, d_sc, d_acc);
+    else     hipLaunchKernelGGL((k_tf<0, 0, 0>), grid, block, 0, ctx->stream, d_sets, q, d_g, (int)n_g, d_t, (int)n_t, (int)chunk, (int)n_chunks, d_red, d_sc, d_acc);
+    GR_HIP(hipGetLastError());
+    std::vector<unsigned long long> red(ns);
+    GR_HIP(hipMemcpyAsync(red.data(), d_red, 8 * ns, hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<CoronaGrid> grids(ns);
+    std::vector<CoronaScale> scales(ns);
+    for (size_t k = 0; k < ns; ++k) {
+        double vmax;
+        std::memcpy(&vmax, &red[k], sizeof vmax);
+        grids[k] = corona_grid(vmax, 2 * sets[k].n_int);         // a cell takes at most two deposits per annulus
+        scales[k] = grids[k].sc;
+    }
+    GR_HIP(hipMemcpyAsync(d_sc, scales.data(), sizeof(CoronaScale) * ns, hipMemcpyHostToDevice, ctx->stream));
+    const size_t lds = sizeof(unsigned long long) * 2 * cells;
+    if (lds <= 40 * 1024) {
+        if (lag) hipLaunchKernelGGL((k_tf<1, 1, 1>), grid, block, lds, ctx->stream, d_sets, q, d_g, (int)n_g, d_t, (int)n_t, (int)chunk, (int)n_chunks, d_red, d_sc, d_acc);
+        else     hipLaunchKernelGGL((k_tf<0, 1, 1>), grid, block, lds, ctx->stream, d_sets, q, d_g, (int)n_g, d_t, (int)n_t, (int)chunk, (int)n_chunks, d_red, d_sc, d_acc);
+    } else {
+        if (lag) hipLaunchKernelGGL((k_tf<1, 1, 0>), grid, block, 0, ctx->stream, d_sets, q, d_g, (int)n_g, d_t, (int)n_t, (int)chunk, (int)n_chunks, d_red, d_sc, d_acc);
+        else     hipLaunchKernelGGL((k_tf<0, 1, 0>), grid, block, 0, ctx->stream, d_sets, q, d_g, (int)n_g, d_t, (int)n_t, (int)chunk, (int)n_chunks, d_red, d_sc, d_acc);
+    }
+    GR_HIP(hipGetLastError());
+    std::vector<long long> acc(2 * ns * cells);
+    GR_HIP(hipMemcpyAsync(acc.data(), d_acc, 8 * acc.size(), hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t k = 0; k < ns; ++k) {
+        const long long* a = acc.data() + 2 * cells * k;
+        for (size_t c = 0; c < cells; ++c) out[k * cells + c] = gr_lag::corona_sum(a[c], a[cells + c], grids[k]);
+    }
+    return GR_OK;
+}
+
+int32_t gr_tf_lineprofile(gr_ctx* ctx, const gr_tfset* sets, int64_t n_sets, const gr_tfquad* quad, const double* g_edges, int64_t n_g,
+                          double* out)
+{
+    return tf_integrate(ctx, sets, n_sets, quad, g_edges, n_g, nullptr, 1, false, out);
+}
+
+int32_t gr_tf_lagtransfer(gr_ctx* ctx, const gr_tfset* sets, int64_t n_sets, const gr_tfquad* quad, const double* g_edges, int64_t n_g,
+                          const double* t_edges, int64_t n_t, double* out)
+{
+    return tf_integrate(ctx, sets, n_sets, quad, g_edges, n_g, t_edges, n_t, true, out);
 }
 
 int32_t gr_ray_tangent(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,

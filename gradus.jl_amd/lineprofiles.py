@@ -139,10 +139,11 @@ def _rayset(config, plane, keep):
 
 
 def lineprofile(bins, ε, m, u, d, method=None, *, λ_max=None, redshift_pf=None, minrₑ=None, maxrₑ=50.0,
-                plane=None, callback="default", ensemble=None, stats=False, **solver_args):
+                plane=None, callback="default", ensemble=None, stats=False, integrate_on_device=False, **solver_args):
     """lineprofile(bins, ε, m, u, d, [method]; ...) -> (bins, normalised flux).  As in the reference
     (line-profiles.jl:100-119) the default method is TransferFunctionMethod(); BinningMethod() bins the
-    image plane `plane` (fused on the device for a power-law ε)."""
+    image plane `plane` (fused on the device for a power-law ε).  `integrate_on_device=True` (TransferFunctionMethod
+    only) also integrates the transfer functions on the device (gr_tf_lineprofile) instead of in numpy."""
     if method is None:
         method = TransferFunctionMethod()
     if isinstance(method, TransferFunctionMethod):
@@ -155,6 +156,11 @@ def lineprofile(bins, ε, m, u, d, method=None, *, λ_max=None, redshift_pf=None
         tfs = transferfunctions(m, u, d, minrₑ=(m.isco() + 1e-2 if minrₑ is None else minrₑ), maxrₑ=maxrₑ, numrₑ=numrₑ,
                                 ensemble=ensemble, **kw)
         bins = np.ascontiguousarray(bins, dtype=np.float64)
+        if integrate_on_device:
+            from .tracing import EnsembleMI355X
+
+            return bins, integrate_lineprofile(ε, tfs, bins, h=h, n_radii=n_radii,
+                                               ensemble=EnsembleMI355X() if ensemble is None else ensemble)
         return bins, integrate_lineprofile(ε, tfs, bins, h=h, n_radii=n_radii)
     if method is not None and not isinstance(method, BinningMethod):
         raise NotImplementedError("method must be BinningMethod() or TransferFunctionMethod()")

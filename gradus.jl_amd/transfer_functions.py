@@ -856,11 +856,19 @@ def _integrate_bins(S, lo, hi, gmin, gmax, h, X, W):
 
 
 def integrate_lineprofile(ε, tfs: InterpolatingTransferBranches, g_grid, *, rmin=None, rmax=None, g_scale=1.0, h=1e-8,
-                          n_radii=1000, quadrature_points=7):
+                          n_radii=1000, quadrature_points=7, ensemble=None):
     """integrate_lineprofile (integration.jl:205-262,330-372): ∫∫ over rₑ (inverse grid, n_radii annuli)
     and over each bin of g (Gauss-Legendre, with the analytic treatment of the integrable
-    1/sqrt(g✶(1-g✶)) edges :152-203), then `_normalize!` (utils.jl:113-125)."""
+    1/sqrt(g✶(1-g✶)) edges :152-203), then `_normalize!` (utils.jl:113-125).
+
+    `tfs` is anything with `.at(r)`: InterpolatingTransferBranches, a CunninghamTransferGrid, a point of a
+    CunninghamTransferTable.  `ensemble=EnsembleMI355X(...)` integrates on the device (gr_tf_lineprofile) instead of in
+    the numpy loop below; the two agree to rounding (1e-12 of the peak, tests/test_gpu_tfint.py)."""
     from .planes import InverseGrid
+
+    if ensemble is not None:
+        return integrate_lineprofiles([ε], [tfs], g_grid, rmin=rmin, rmax=rmax, g_scale=g_scale, h=h, n_radii=n_radii,
+                                      quadrature_points=quadrature_points, ensemble=ensemble)[0]
 
     g_grid = np.asarray(g_grid, dtype=np.float64)
     rmin = tfs.inner_radius() if rmin is None else rmin
@@ -897,13 +905,21 @@ def integrate_lineprofile(ε, tfs: InterpolatingTransferBranches, g_grid, *, rmi
 
 
 def integrate_lagtransfer(prof, tfs: InterpolatingTransferBranches, g_grid, t_grid, *, rmin=None, rmax=None, g_scale=1.0,
-                          h=1e-8, n_radii=1000, quadrature_points=7, t0=0.0):
+                          h=1e-8, n_radii=1000, quadrature_points=7, t0=0.0, ensemble=None):
     """integrate_lagtransfer (integration.jl:264-289,374-453): the (g, t) response of the disc to a flash
     of the corona.  `prof` provides emissivity_at(r) and coordtime_at(r) (source -> disc time); each
     annulus and g-bin deposits its lower- and upper-branch flux at (source -> disc) + (disc -> observer)
     - t0.  Rows are then normalised like the line profile (`_normalize!` for matrices; its final
-    row-maximum rescaling is discarded by the reference's own call chain and is not applied)."""
+    row-maximum rescaling is discarded by the reference's own call chain and is not applied).
+
+    `ensemble=EnsembleMI355X(...)` integrates on the device (gr_tf_lagtransfer): ε and the source -> disc time are
+    evaluated at the annuli here, so any profile serves."""
     from .planes import GeometricGrid
+
+    if ensemble is not None:
+        return _integrate_lagtransfer_device(prof, tfs, g_grid, t_grid, rmin=rmin, rmax=rmax, g_scale=g_scale, h=h,
+                                             n_radii=n_radii, quadrature_points=quadrature_points, t0=t0,
+                                             call=_tf_library_call(ensemble, True))
 
     g_grid = np.asarray(g_grid, dtype=np.float64)
     t_grid = np.asarray(t_grid, dtype=np.float64)
@@ -967,6 +983,139 @@ def integrate_lagtransfer(prof, tfs: InterpolatingTransferBranches, g_grid, t_gr
 
 
 # ------------------------------------------------------------------------------------------
+# the same integrals on the device (gr_tf_lineprofile / gr_tf_lagtransfer; csrc/gr_tfint.hpp)
+# ------------------------------------------------------------------------------------------
+def _tf_pack(tfs):
+    """(radii, gmin, gmax, off, knot_g, knot_f, knot_t) of gr_tfset: per radius the lower, then the upper branch.  A grid
+    has one g✶ axis for every branch: it is replicated, so that the device knows ragged branches only."""
+    if isinstance(tfs, CunninghamTransferGrid):
+        n_r, n_k = tfs.r_grid.size, tfs.g_star_grid.size
+        off = np.arange(2 * n_r + 1, dtype=np.int64) * n_k
+        kg = np.tile(np.asarray(tfs.g_star_grid, dtype=np.float64), 2 * n_r)
+        kf = np.stack([np.asarray(tfs.lower_f).T, np.asarray(tfs.upper_f).T], axis=1).reshape(-1)
+        kt = np.stack([np.asarray(tfs.lower_time).T, np.asarray(tfs.upper_time).T], axis=1).reshape(-1)
+        radii, gmin, gmax = tfs.r_grid, tfs.g_min, tfs.g_max
+    elif isinstance(tfs, InterpolatingTransferBranches):
+        parts = [(getattr(b, side + "_g"), getattr(b, side + "_f"), getattr(b, side + "_t"))
+                 for b in tfs.branches for side in ("lower", "upper")]
+        off = np.concatenate([[0], np.cumsum([p[0].size for p in parts])]).astype(np.int64)
+        kg, kf, kt = (np.concatenate([p[k] for p in parts]) for k in range(3))
+        radii, gmin, gmax = tfs.radii, tfs.gmin, tfs.gmax
+    else:
+        raise NotImplementedError(f"the device integrates InterpolatingTransferBranches and CunninghamTransferGrid, not {type(tfs).__name__}")
+    c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    return c(radii), c(gmin), c(gmax), np.ascontiguousarray(off), c(kg), c(kf), c(kt)
+
+
+def _tf_set(tfs, r_int, eps, tsd, rmin, g_scale):
+    """(gr_tfset, the arrays it points to)"""
+    from . import _lib
+
+    radii, gmin, gmax, off, kg, kf, kt = _tf_pack(tfs)
+    r_int, eps, tsd = (np.ascontiguousarray(a, dtype=np.float64) for a in (r_int, eps, tsd))
+    assert eps.size == r_int.size == tsd.size
+    s = _lib.gr_tfset()
+    s.n_r, s.radii, s.gmin, s.gmax = radii.size, radii.ctypes.data, gmin.ctypes.data, gmax.ctypes.data
+    s.off, s.knot_g, s.knot_f, s.knot_t = off.ctypes.data, kg.ctypes.data, kf.ctypes.data, kt.ctypes.data
+    s.n_int, s.r_int, s.eps_int, s.tsd_int = r_int.size, r_int.ctypes.data, eps.ctypes.data, tsd.ctypes.data
+    s.r_min, s.g_scale = float(rmin), float(g_scale)
+    return s, (radii, gmin, gmax, off, kg, kf, kt, r_int, eps, tsd)
+
+
+def _tf_library_call(ensemble, lag):
+    """the library's entry point bound to the ensemble's context, with the argument list of `_tf_run`'s `call`"""
+    from . import _lib
+
+    L, ctx = _lib.load(), ensemble.ctx.handle
+    fn = L.gr_tf_lagtransfer if lag else L.gr_tf_lineprofile
+    return lambda *args: _lib.check(fn(ctx, *args))
+
+
+def _tf_run(sets, g_grid, t_grid, h, quadrature_points, call):
+    """raw sums (n_sets, n_g) or (n_sets, n_g, n_t) of the packed sets: the quadrature rule is the host route's"""
+    import ctypes as C
+
+    from . import _lib
+
+    X, W = np.polynomial.legendre.leggauss(quadrature_points)
+    X, W = np.ascontiguousarray(X), np.ascontiguousarray(W)
+    q = _lib.gr_tfquad(float(h), X.size, X.ctypes.data, W.ctypes.data)
+    arr = (_lib.gr_tfset * len(sets))(*sets)
+    g_grid = np.ascontiguousarray(g_grid, dtype=np.float64)
+    if t_grid is None:
+        out = np.zeros((len(sets), g_grid.size))
+        call(arr, len(sets), C.byref(q), g_grid.ctypes.data, g_grid.size, out.ctypes.data)
+    else:
+        t_grid = np.ascontiguousarray(t_grid, dtype=np.float64)
+        out = np.zeros((len(sets), g_grid.size, t_grid.size))
+        call(arr, len(sets), C.byref(q), g_grid.ctypes.data, g_grid.size, t_grid.ctypes.data, t_grid.size, out.ctypes.data)
+    return out
+
+
+def _per_set(v, n, name):
+    if v is None or np.isscalar(v):
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"{name}: one value, or one per set")
+    return v
+
+
+def integrate_lineprofiles(εs, tfs_list, g_grid, *, rmin=None, rmax=None, g_scale=1.0, h=1e-8, n_radii=1000,
+                           quadrature_points=7, ensemble, _call=None):
+    """integrate_lineprofile for many parameter sets in ONE device call -- the shape of a spectral fit
+    (GradusSpectralModels.invoke!: a table point, an emissivity and an inner radius per evaluation).  `εs[k]` and
+    `tfs_list[k]` belong together; `rmin`, `rmax` and `g_scale` are one value or one per set.  Returns the normalised
+    profiles, (n_sets, len(g_grid)).  A set gives the same bits alone or in any batch."""
+    from .planes import InverseGrid
+
+    n = len(tfs_list)
+    if len(εs) != n or n < 1:
+        raise ValueError("one emissivity per set of transfer functions")
+    if ensemble is None and _call is None:
+        raise ValueError("integrate_lineprofiles runs on the device: pass ensemble=EnsembleMI355X(...) (integrate_lineprofile is the host route)")
+    g_grid = np.ascontiguousarray(g_grid, dtype=np.float64)
+    sets, keep = [], []
+    for ε, tfs, r0, r1, gs in zip(εs, tfs_list, _per_set(rmin, n, "rmin"), _per_set(rmax, n, "rmax"), _per_set(g_scale, n, "g_scale")):
+        r0 = tfs.inner_radius() if r0 is None else r0
+        r1 = tfs.outer_radius() if r1 is None else r1
+        radii = np.asarray(InverseGrid()(r0, r1, n_radii), dtype=np.float64)
+        eps = np.array([float(ε(r)) for r in radii])
+        s, k = _tf_set(tfs, radii, eps, np.zeros(radii.size), r0, gs)
+        sets.append(s)
+        keep.append(k)
+    raw = _tf_run(sets, g_grid, None, h, quadrature_points, _tf_library_call(ensemble, False) if _call is None else _call)
+    # _normalize!, per set as integrate_lineprofile ends
+    flux = raw.copy()
+    flux[:, :-1] = flux[:, :-1] / (g_grid[1:] + g_grid[:-1])
+    for row in flux:
+        total = row[:-1].sum()
+        if total > 0:
+            row /= total
+    return flux
+
+
+def _integrate_lagtransfer_device(prof, tfs, g_grid, t_grid, *, rmin, rmax, g_scale, h, n_radii, quadrature_points, t0, call):
+    from .planes import GeometricGrid
+
+    g_grid = np.ascontiguousarray(g_grid, dtype=np.float64)
+    t_grid = np.ascontiguousarray(t_grid, dtype=np.float64)
+    rmin = tfs.inner_radius() if rmin is None else rmin
+    rmax = tfs.outer_radius() if rmax is None else rmax
+    radii = np.asarray(GeometricGrid()(rmin, rmax, n_radii), dtype=np.float64)
+    eps = np.array([float(prof.emissivity_at(r)) for r in radii])
+    tsd = np.array([float(prof.coordtime_at(r)) - t0 for r in radii])
+    s, keep = _tf_set(tfs, radii, eps, tsd, rmin, g_scale)
+    out = _tf_run([s], g_grid, t_grid, h, quadrature_points, call)[0]
+    flux = out.copy()
+    flux[:-1, :] = flux[:-1, :] / (g_grid[1:] + g_grid[:-1])[:, None]
+    total = flux[:-1, :].sum()
+    if total > 0:
+        flux = flux / total
+    return flux
+
+
+# ------------------------------------------------------------------------------------------
 # grids and tables of transfer functions (cunningham-transfer-functions.jl:440-530, types.jl:14-130)
 # ------------------------------------------------------------------------------------------
 @dataclass
@@ -990,6 +1139,37 @@ class CunninghamTransferGrid:
 
     def fields(self):
         return (self.r_grid, self.g_star_grid, self.g_min, self.g_max, self.lower_f, self.upper_f, self.lower_time, self.upper_time)
+
+    def at(self, r):
+        """(grid::CunninghamTransferGrid)(r) (transfer-functions-2d.jl:45-69,90-99): (gmin, gmax, summed-branch evaluator)
+        at radius r, and `_last` with the four blended fields, as InterpolatingTransferBranches.at gives them -- so
+        integrate_lineprofile and integrate_lagtransfer take a grid, or a point of a CunninghamTransferTable, as they take
+        branches.  Columns idx and idx + 1 are evaluated on g_star_grid with the branch route's interpolator and blended by θ.
+
+        The reference marks a grid's branches `SameDomain` and lets its line-profile integrand share one knot search
+        between the fields through an index cache (integration.jl:137-146).  That cache's start index is never reset
+        between annuli, so what it returns depends on the calls made before; it is not reproduced here: every evaluation
+        searches g_star_grid afresh (the plain `(grid)(r)` semantics, which is also what integrate_lagtransfer uses)."""
+        n = self.r_grid.size
+        idx = int(np.clip(np.searchsorted(self.r_grid, r, side="right") - 1, 0, n - 2))
+        r1, r2 = self.r_grid[idx], self.r_grid[idx + 1]
+        w = (r - r1) / (r2 - r1)
+        gmin = (1 - w) * self.g_min[idx] + w * self.g_min[idx + 1]
+        gmax = (1 - w) * self.g_max[idx] + w * self.g_max[idx + 1]
+        x = self.g_star_grid
+
+        def lerp(field):
+            ya, yb = np.ascontiguousarray(field[:, idx]), np.ascontiguousarray(field[:, idx + 1])
+            return lambda gs: (1 - w) * _interp(x, ya, gs) + w * _interp(x, yb, gs)
+
+        self._last = dict(lower_f=lerp(self.lower_f), upper_f=lerp(self.upper_f),
+                          lower_t=lerp(self.lower_time), upper_t=lerp(self.upper_time))
+
+        def both(gs):
+            fl, fu = self._last["lower_f"](gs), self._last["upper_f"](gs)
+            return np.where(np.isnan(fl), 0.0, fl) + np.where(np.isnan(fu), 0.0, fu)
+
+        return gmin, gmax, both
 
 
 def transfer_function_grid(itfs_or_metric, *args, Ng=20, h_grid=1e-3, **kwargs):

@@ -305,7 +305,9 @@ int32_t gr_ctx_destroy(gr_ctx* ctx);
  * be outstanding at once, default 8192 -- a request beyond it is refused with GR_ERR_OUT_OF_MEMORY and the caller falls back to
  * pageable memory: a garbage-collected caller sees a 100-byte wrapper, not the block behind it);
  * ("pinned_huge", process-wide: 1 [default] = gr_host_alloc blocks of 8 MiB and more are mappings on transparent huge pages
- * registered with the runtime (13 ms for 608 MiB), 0 = every block from hipHostMalloc (122-365 ms)). */
+ * registered with the runtime (13 ms for 608 MiB), 0 = every block from hipHostMalloc (122-365 ms));
+ * ("tf_chunk", annuli per workgroup of gr_tf_lineprofile / gr_tf_lagtransfer, 0 = auto [default], at most 65536: the launch
+ * shape only, the results are the same bits for every value). */
 int32_t gr_ctx_set(gr_ctx* ctx, const char* key, int64_t value);
 
 /* ---- pinned result buffers (ABI 5).  The reference allocates the result of ensemble_solve_tracing_problem itself
@@ -607,6 +609,55 @@ int32_t gr_lagtransfer_extrema(gr_ctx* ctx, const gr_lagprofile* profile, double
 int32_t gr_lagtransfer_bin(gr_ctx* ctx, const gr_lagprofile* profile, const double* E_edges, int64_t n_E,
                            const double* t_edges, int64_t n_t, double* out /* host, n_E x n_t, row-major [E][t], raw Σf */);
 int32_t gr_lagtransfer_rows(gr_ctx* ctx, double* out /* host, n x 4 */);
+
+/* ---- transfer functions integrated on the device (added within ABI 8, nothing else changes): integrate_lineprofile and
+ * integrate_lagtransfer (src/transfer-functions/integration.jl:161-453) for one or many parameter sets in one call -- the
+ * shape of a spectral fit, which integrates a table point, an emissivity and an inner radius per iteration.
+ * A gr_tfset is self-contained:
+ *   transfer functions  n_r >= 2 emission radii (ascending) with their gmin / gmax, and per radius a lower and an upper branch:
+ *                       branch (k, lower) owns the knots [off[2k], off[2k+1]), (k, upper) the knots [off[2k+1], off[2k+2]) of
+ *                       knot_g (g✶, ascending), knot_f and knot_t; 2 ... 1024 knots per branch, off ascending from off[0] >= 0.
+ *                       A CunninghamTransferGrid is the case where every branch has the same knots: the caller replicates them.
+ *   annuli              n_int >= 2 integration radii r_int (the caller forms the grid: inverse for a line profile, geometric
+ *                       for a lag transfer function), ε(rₑ) and coordtime(rₑ) - t0 at each of them (any emissivity the caller
+ *                       can evaluate), r_min (the first annulus is as wide as the second) and g_scale.
+ * gr_tfquad: the edge width h of integrate_bin and a quadrature rule on [-1, 1] of n_q <= 32 nodes.
+ * Per annulus the branches of the two radii around rₑ are blended linearly (NaNLinearInterpolator per branch, then
+ * (1 - w) y1 + w y2), the bin integrals get the weight (rₑ - r_prev) rₑ ε π / (gmax - gmin), and a lag deposit goes to the first
+ * t edge >= its arrival time (dropped past the last edge).  Results are RAW sums: _normalize! stays with the caller.  Row
+ * n_g - 1 of every set is 0 (n_g edges bound n_g - 1 bins).
+ * The sums are integers on a fixed-point grid chosen per set from its largest deposit, like those of gr_lagtransfer_bin: the
+ * same arguments give the same bits on every run and for every launch shape, and a set gives the same bits alone or in a batch.
+ * All pointers are host pointers, staged per call; the calls keep nothing on the context and disturb nothing it holds.
+ * GR_ERR_INVALID_ARGUMENT, before anything touches the device, for: a null pointer, n_sets < 1, n_r < 2, n_int < 2, n_g < 2,
+ * n_t < 2, n_q outside 1 ... 32, a branch with fewer than 2 or more than 1024 knots, offsets that do not ascend, and more than
+ * 2^24 cells (n_sets n_g n_t). */
+typedef struct gr_tfset {
+    int64_t n_r;              /* emission radii                                             */
+    const double* radii;      /* n_r, ascending                                             */
+    const double* gmin;       /* n_r                                                        */
+    const double* gmax;       /* n_r                                                        */
+    const int64_t* off;       /* 2 n_r + 1 offsets into the knot arrays                     */
+    const double* knot_g;     /* off[2 n_r] knots g✶, ascending within a branch             */
+    const double* knot_f;     /* transfer function on the knots                             */
+    const double* knot_t;     /* disc -> observer coordinate time on the knots              */
+    int64_t n_int;            /* annuli                                                     */
+    const double* r_int;      /* n_int integration radii                                    */
+    const double* eps_int;    /* n_int emissivities ε(rₑ)                                   */
+    const double* tsd_int;    /* n_int source -> disc times minus t0 (lag transfer only)    */
+    double r_min;             /* inner radius of the integration                            */
+    double g_scale;           /* the g edges are divided by it                              */
+} gr_tfset;
+typedef struct gr_tfquad {
+    double h;                 /* integrate_bin's edge width in g✶                           */
+    int64_t n_q;              /* 1 ... 32 nodes                                             */
+    const double* x;          /* nodes on [-1, 1]                                           */
+    const double* w;          /* weights                                                    */
+} gr_tfquad;
+int32_t gr_tf_lineprofile(gr_ctx* ctx, const gr_tfset* sets, int64_t n_sets, const gr_tfquad* quad, const double* g_edges,
+                          int64_t n_g, double* out /* host, n_sets x n_g, raw sums */);
+int32_t gr_tf_lagtransfer(gr_ctx* ctx, const gr_tfset* sets, int64_t n_sets, const gr_tfquad* quad, const double* g_edges,
+                          int64_t n_g, const double* t_edges, int64_t n_t, double* out /* host, n_sets x n_g x n_t, raw sums */);
 
 /* ---- tabulated metrics (ABI 7; segments, axis terms: ABI 8; GR_METRIC_TABULATED): the AbstractMetric plugin interface on the device ----
  * Host-only functions (no context, no device): plan a grid, learn its nodes, fit, check.
