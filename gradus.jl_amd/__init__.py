@@ -10,7 +10,8 @@ from . import device, distributed
 from . import corona, reverberation, transfer_functions
 from .corona import (BeamedPointSource, BothHemispheres, CoronaGeodesics, DiscCorona, EvenGenerator, EvenSampler,
                      GoldenSpiralGenerator, LampPostModel, LowerHemisphere, PowerLawSpectrum, RadialDiscProfile, RingCorona,
-                     SourceVelocities,
+                     SourceVelocities, DiscCoronaProfile, RingCoronaProfile, TimeDependentRadialDiscProfile,
+                     emissivity_interp, emissivity_interp_limits,
                      RandomGenerator, WeierstrassSampler, coordtime_at, emissivity_at, emissivity_profile,
                      energy_ratio, lorentz_factor, sky_angles_to_velocity, tetradframe_matrix, tracecorona)
 from .distributed import gather_buffers, gather_image, gather_image_async, gather_points, shard_plan
@@ -35,7 +36,7 @@ from .transfer_functions import (CunninghamTransferData, CunninghamTransferGrid,
                                 make_transfer_function_table, transfer_function_grid, InterpolatingTransferBranches, TransferBranches,
                                 cunningham_transfer_function, cunningham_transfer_functions, integrate_lagtransfer,
                                 integrate_lineprofile, integrate_lineprofiles,
-                                interpolate_branches, splitbranches, transferfunctions)
+                                interpolate_branches, splitbranches, time_dependent_emissivity_table, transferfunctions)
 from .reverberation import (AnalyticRadialDiscProfile, DeviceLagTransfer, LagTransferFunction, bin_transfer_function, binflux,
                             continuum_time, lag_frequency,
                             lagtransfer, lagtransfer_device, observer_to_disc)

@@ -26,7 +26,7 @@ def kernel_source_sha16() -> str:
     h = hashlib.sha256()
     root = os.path.dirname(_HERE)
     for rel in ("gradus.jl_amd/csrc/gr_device.hpp", "gradus.jl_amd/csrc/gr_kernels.hpp", "gradus.jl_amd/csrc/gr_tangent.hpp",
-                "gradus.jl_amd/csrc/gr_tabmetric.hpp", "gradus.jl_amd/csrc/gr_lagbin.hpp", "gradus.jl_amd/csrc/gr_tfint.hpp", "gradus.jl_amd/csrc/metric_table.hip",
+                "gradus.jl_amd/csrc/gr_tabmetric.hpp", "gradus.jl_amd/csrc/gr_lagbin.hpp", "gradus.jl_amd/csrc/gr_tfint.hpp", "gradus.jl_amd/csrc/gr_tftd.hpp", "gradus.jl_amd/csrc/metric_table.hip",
                 "gradus.jl_amd/csrc/kernels_tu.hip",
                 "gradus.jl_amd/csrc/gradus_mi355x.hip",
                 "include/gradus_mi355x.h"):
@@ -274,6 +274,21 @@ class gr_tfquad(C.Structure):
     _fields_ = [("h", C.c_double), ("n_q", C.c_int64), ("x", C.c_void_p), ("w", C.c_void_p)]
 
 
+class gr_tfprofile(C.Structure):
+    """The time-dependent emissivity of gr_tf_lagtransfer_td: rings of two arms, an arm a run of curves (ρ, t, ε)"""
+
+    _fields_ = [
+        ("n_rings", C.c_int64),
+        ("ring_weight", C.c_void_p),
+        ("ring_dt", C.c_void_p),
+        ("arm_off", C.c_void_p),
+        ("curve_off", C.c_void_p),
+        ("knot_r", C.c_void_p),
+        ("knot_t", C.c_void_p),
+        ("knot_e", C.c_void_p),
+    ]
+
+
 class gr_stats(C.Structure):
     _fields_ = [
         ("rays", C.c_int64),
@@ -357,6 +372,7 @@ EXPORTS = [
     "gr_lagtransfer_rows",
     "gr_tf_lineprofile",
     "gr_tf_lagtransfer",
+    "gr_tf_lagtransfer_td",
     "gr_render_endpoints_multi",
     "gr_trace_endpoints_multi",
     "gr_rayset_endpoints_multi",
@@ -431,6 +447,7 @@ def load():
     tsp, tqp = C.POINTER(gr_tfset), C.POINTER(gr_tfquad)
     L.gr_tf_lineprofile.argtypes = [vp, tsp, i64, tqp, vp, i64, vp]
     L.gr_tf_lagtransfer.argtypes = [vp, tsp, i64, tqp, vp, i64, vp, i64, vp]
+    L.gr_tf_lagtransfer_td.argtypes = [vp, tsp, C.POINTER(gr_tfprofile), tqp, vp, i64, vp, i64, i64, i64, C.c_double, vp, vp]
     ctxa = C.POINTER(vp)
     L.gr_render_endpoints_multi.argtypes = [ctxa, i32, cfgp, plp, i64, vp, vp]
     L.gr_trace_endpoints_multi.argtypes = [ctxa, i32, cfgp, vp, i64, vp, i64, vp, vp]

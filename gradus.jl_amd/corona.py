@@ -242,8 +242,10 @@ class SourceVelocities:
 class RingCorona(AbstractCoronaModel):
     """RingCorona(vf, r, h): an infinitely thin ring of radius r at height h (extended.jl:55-82).  A
     representative point of the ring is returned; axis symmetry does the rest.  Its emissivity goes
-    through the generic Monte-Carlo route (`emissivity_profile(..., sampler=...)`); the reference's
-    dedicated arm-by-arm integrator (ring.jl) is not restated."""
+    through the generic Monte-Carlo route (`emissivity_profile(..., sampler=...)`).  Its time-dependent emissivity is a
+    `RingCoronaProfile` (two arms of per-slice curves, built from arrays), which `integrate_lagtransfer` integrates on the
+    host and, with `ensemble=`, on the device (ring.jl:857-950); the reference's producer of the arms from traced slices
+    (ring.jl:1-485) is not restated."""
 
     fixed_position = True
 
@@ -266,7 +268,9 @@ class DiscCorona(AbstractCoronaModel):
     """DiscCorona(vf, r, h): a disc of radius r at height h above the accretion disc (extended.jl:165-181); every sample leaves
     from a point of its own, x = rand() r along the disc (sample_position_velocity, extended.jl:176-183).  Its emissivity goes
     through the Monte-Carlo route (`emissivity_profile(..., sampler=...)`: tracecorona + RadialDiscProfile); the reference's
-    concentric-ring method (extended.jl:185-200, time-dependent ring profiles) is not restated.  `seed`: the generator behind rand()."""
+    concentric-ring profile is `DiscCoronaProfile` (rings of `RingCoronaProfile`, built from arrays), which `integrate_lagtransfer`
+    integrates on the host and, with `ensemble=`, on the device; tracing the rings' arms (extended.jl:185-200) is not restated.
+    `seed`: the generator behind rand()."""
 
     def __init__(self, *args, r=5.0, h=5.0, vf=SourceVelocities.co_rotating, seed=None):
         if len(args) == 3:
@@ -553,6 +557,158 @@ def emissivity_at(prof, r):
 
 def coordtime_at(prof, r):
     return prof.coordtime_at(r)
+
+
+# ------------------------------------------------------------------------------------------
+# time-dependent profiles of the extended coronae (src/corona/radial.jl:164-324)
+# ------------------------------------------------------------------------------------------
+class _TimeInterpolation:
+    """NaNLinearInterpolator over an arm's knots (t, ε) sorted by t, default 0: `.t`, `.u` and a call"""
+
+    def __init__(self, t, u):
+        self.t, self.u = t, u
+
+    def __call__(self, x):
+        with np.errstate(all="ignore"):
+            return _nan_linear_interp(self.t, self.u, x, 0.0)
+
+
+def _in_range(interp, x):
+    """an arm's ε(t) where its first knot <= x <= its last knot, 0 elsewhere: everywhere, if its last knot is NaN"""
+    x = np.asarray(x, dtype=np.float64)
+    inside = (x >= interp.t[0]) & (x <= interp.t[-1])
+    if not np.any(inside):
+        return np.zeros(x.shape)
+    return np.where(inside, interp(np.where(inside, x, interp.t[0])), 0.0)
+
+
+class TimeDependentRadialDiscProfile:
+    """radial.jl:171-227: one arm of a ring corona.  Slice i of the source's sky met the disc along the curve
+    (radii[i], t[i], ε[i]), radii[i] ascending.  At a radius ρ every slice whose curve covers ρ gives a knot (t, ε); the
+    emissivity as a function of time interpolates the knots sorted by t (a stable sort, NaN last)."""
+
+    def __init__(self, weights, radii, t, ε):
+        as_list = lambda v: [np.ascontiguousarray(a, dtype=np.float64) for a in v]
+        self.weights = np.asarray(weights, dtype=np.float64)
+        self.radii, self.t, self.ε = as_list(radii), as_list(t), as_list(ε)
+        self._last = None
+        if not (len(self.radii) == len(self.t) == len(self.ε) == self.weights.size):
+            raise ValueError("one weight, one radii, one t and one ε array per slice")
+        for r, t_, e in zip(self.radii, self.t, self.ε):
+            if not (r.ndim == 1 and r.shape == t_.shape == e.shape and r.size >= 2):
+                raise ValueError("a slice is three arrays of one length, at least 2")
+
+    def _knots(self, ρ):
+        """(t, ε) of every slice at ρ, NaN where the slice does not cover it (kept for the last ρ: the limits and the
+        interpolation of one annulus ask for the same knots)"""
+        ρ = float(ρ)
+        if self._last is not None and self._last[0] == ρ:
+            return self._last[1], self._last[2]
+        ts, εs = np.full(len(self.radii), np.nan), np.full(len(self.radii), np.nan)
+        for i, radii in enumerate(self.radii):
+            if radii[0] <= ρ <= radii[-1]:
+                ts[i] = _nan_linear_interp(radii, self.t[i], ρ)
+                εs[i] = _nan_linear_interp(radii, self.ε[i], ρ)
+        self._last = (ρ, ts, εs)
+        return ts, εs
+
+    def emissivity_at(self, ρ):
+        """the time-averaged value: Σ over the slices that cover ρ"""
+        ρ = float(ρ)
+        total = 0.0
+        for radii, ε in zip(self.radii, self.ε):
+            total = total + (float(_nan_linear_interp(radii, ε, ρ)) if radii[0] <= ρ <= radii[-1] else 0.0)
+        return total
+
+    def emissivity_interp(self, ρ):
+        ts, εs = self._knots(ρ)
+        J = np.argsort(ts, kind="stable")          # sortperm: stable, NaN last
+        return _TimeInterpolation(ts[J], εs[J])
+
+    def emissivity_interp_limits(self, ρ):
+        ts, _ = self._knots(ρ)
+        ts = ts[~np.isnan(ts)]
+        return (float(ts.min()), float(ts.max())) if ts.size else (0.0, 0.0)
+
+
+class RingCoronaProfile:
+    """radial.jl:235-267: the two arms of a ring.  An arm counts at time x only between its first and its last knot -- so
+    not at all at a radius that one of its slices misses (its last knot is then NaN)."""
+
+    def __init__(self, left_arm, right_arm):
+        self.left_arm, self.right_arm = left_arm, right_arm
+
+    def emissivity_at(self, ρ):
+        return self.left_arm.emissivity_at(ρ) + self.right_arm.emissivity_at(ρ)
+
+    def emissivity_interp(self, ρ):
+        left, right = self.left_arm.emissivity_interp(ρ), self.right_arm.emissivity_interp(ρ)
+        return lambda x: _in_range(left, x) + _in_range(right, x)
+
+    def emissivity_interp_limits(self, ρ):
+        l_min, l_max = self.left_arm.emissivity_interp_limits(ρ)
+        r_min, r_max = self.right_arm.emissivity_interp_limits(ρ)
+        return min(l_min, r_min), max(l_max, r_max)
+
+
+def _no_delay(radius):
+    return 0.0
+
+
+class DiscCoronaProfile:
+    """radial.jl:269-324: concentric rings at `radii` (equally spaced: ring i weighs radii[i] (radii[1] - radii[0])), ring i
+    delayed by propagation_velocity(radii[i])."""
+
+    def __init__(self, radii, rings, propagation_velocity=_no_delay):
+        self.radii = np.asarray(radii, dtype=np.float64)
+        self.rings = list(rings)
+        self.propagation_velocity = propagation_velocity
+        if self.radii.size != len(self.rings) or len(self.rings) < 2:
+            raise ValueError("a DiscCoronaProfile needs one radius per ring and at least 2 rings")
+
+    def with_propagation_velocity(self, func):
+        return DiscCoronaProfile(self.radii, self.rings, func)
+
+    def _ring_weighting(self, i):
+        return float(self.radii[i] * (self.radii[1] - self.radii[0]))
+
+    def _delays(self):
+        return [float(self.propagation_velocity(float(r))) for r in self.radii]
+
+    def emissivity_at(self, ρ):
+        total = 0.0
+        for i, ring in enumerate(self.rings):
+            total = total + ring.emissivity_at(ρ) * self._ring_weighting(i)
+        return total
+
+    def emissivity_interp(self, ρ):
+        funcs = [ring.emissivity_interp(ρ) for ring in self.rings]
+        dts = self._delays()
+
+        def sum_ring_contributions(x):
+            x = np.asarray(x, dtype=np.float64)
+            total = np.zeros(x.shape)
+            for i, f in enumerate(funcs):
+                total = total + f(x - dts[i]) * self._ring_weighting(i)
+            return total
+
+        return sum_ring_contributions
+
+    def emissivity_interp_limits(self, ρ):
+        lo = hi = None
+        for dt, ring in zip(self._delays(), self.rings):
+            a, b = ring.emissivity_interp_limits(ρ)
+            a, b = a + dt, b + dt
+            lo, hi = (a, b) if lo is None else (min(lo, a), max(hi, b))
+        return lo, hi
+
+
+def emissivity_interp(prof, ρ):
+    return prof.emissivity_interp(ρ)
+
+
+def emissivity_interp_limits(prof, ρ):
+    return prof.emissivity_interp_limits(ρ)
 
 
 def _bucket_index(values, bins):

@@ -29,6 +29,7 @@
 #include "gr_mesh_grid.hpp"
 #include "gr_lagbin.hpp"
 #include "gr_tfint.hpp"
+#include "gr_tftd.hpp"
 
 using namespace gr;
 
@@ -2591,6 +2592,197 @@ __global__ void __launch_bounds__(256) k_tf(const gr_tf::Set* __restrict__ sets,
     }
 }
 
+// ---- the lag transfer function of a time-dependent emissivity (RingCoronaProfile / DiscCoronaProfile; ring.jl:857-950); the
+// arithmetic is gr_tftd.hpp ----
+// k_tftd_em: workgroup ia forms what annulus ia needs of the profile, em[ia] = (t_lo, t_hi, ε(time_k) for k < n_time).
+// Pass A: a wave per arm, lanes over its slices: the extrema of the slices' t at ρ by shuffles, folded into the wave's limits
+// and then across the four waves.  Pass B, arm by arm in ring order: the slices' (t, ε) into LDS, each slice's rank by counting
+// (a stable sort, NaN last), the sorted knots into LDS, and thread k adds the arm at time_k - dt to the samples it owns:
+// (left + right) w_i, ring by ring, the order of the host route.  Every em[ia][k] has one writer and one order of additions.
+__global__ void __launch_bounds__(256) k_tftd_em(const gr_tf::Set* __restrict__ set, const gr_tftd::Profile* __restrict__ profile, int n_time,
+                                                 double* __restrict__ em)
+{
+    GR_LAG_NO_CONTRACT
+    __shared__ double raw_t[gr_tftd::kMaxCurves], raw_e[gr_tftd::kMaxCurves], knot_t[gr_tftd::kMaxCurves], knot_e[gr_tftd::kMaxCurves];
+    __shared__ double wave_lo[4], wave_hi[4];
+    __shared__ int wave_any[4];
+    const gr_tftd::Profile p = *profile;
+    const int64_t ia = blockIdx.x;
+    const double rho = set->r_int[ia];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int n_arms = 2 * (int)p.n_rings;
+    // pass A
+    double w_lo = 0.0, w_hi = 0.0;
+    bool w_any = false;
+    for (int arm = wave; arm < n_arms; arm += 4) {
+        const int64_t c0 = p.arm_off[arm], nc = p.arm_off[arm + 1] - c0;
+        double lo = INFINITY, hi = -INFINITY;
+        int count = 0;
+        for (int64_t j = lane; j < nc; j += 64) {
+            double t, e;
+            gr_tftd::slice_at(p, c0 + j, rho, t, e);
+            if (t == t) {
+                lo = fmin(lo, t);
+                hi = fmax(hi, t);
+                ++count;
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            lo = fmin(lo, __shfl_xor(lo, off, 64));
+            hi = fmax(hi, __shfl_xor(hi, off, 64));
+            count += __shfl_xor(count, off, 64);
+        }
+        gr_tftd::fold_limits(lo, hi, count, p.dt[arm >> 1], !w_any, w_lo, w_hi);
+        w_any = true;
+    }
+    if (lane == 0) {
+        wave_lo[wave] = w_lo;
+        wave_hi[wave] = w_hi;
+        wave_any[wave] = w_any ? 1 : 0;
+    }
+    __syncthreads();
+    double t_lo = wave_lo[0], t_hi = wave_hi[0];             // (wave 0 always has an arm: n_arms >= 2)
+    for (int k = 1; k < 4; ++k)
+        if (wave_any[k]) {
+            t_lo = fmin(t_lo, wave_lo[k]);
+            t_hi = fmax(t_hi, wave_hi[k]);
+        }
+    double* row = em + (size_t)ia * (size_t)(2 + n_time);
+    if (tid == 0) {
+        row[0] = t_lo;
+        row[1] = t_hi;
+    }
+    // pass B
+    constexpr int kOwn = (int)(gr_tftd::kMaxTime / 256);
+    double sum[kOwn], left[kOwn], time[kOwn];
+#pragma unroll
+    for (int s = 0; s < kOwn; ++s) {
+        const int k = tid + 256 * s;
+        sum[s] = left[s] = 0.0;
+        time[s] = k < n_time ? gr_tftd::time_sample(t_lo, t_hi, n_time, k) : 0.0;
+    }
+    for (int arm = 0; arm < n_arms; ++arm) {
+        const int64_t c0 = p.arm_off[arm];
+        const int nc = (int)(p.arm_off[arm + 1] - c0);
+        for (int j = tid; j < nc; j += 256) gr_tftd::slice_at(p, c0 + j, rho, raw_t[j], raw_e[j]);
+        __syncthreads();
+        for (int j = tid; j < nc; j += 256) {
+            const int r = gr_tftd::rank_of(raw_t, nc, j);
+            knot_t[r] = raw_t[j];
+            knot_e[r] = raw_e[j];
+        }
+        __syncthreads();
+        const double dt = p.dt[arm >> 1], w = p.w[arm >> 1];
+#pragma unroll
+        for (int s = 0; s < kOwn; ++s) {
+            if (tid + 256 * s >= n_time) continue;
+            const double v = gr_tftd::arm_at(knot_t, knot_e, nc, time[s] - dt);
+            if (arm & 1) {
+                const double both = left[s] + v, term = both * w;
+                sum[s] += term;
+            } else {
+                left[s] = v;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < kOwn; ++s)
+        if (tid + 256 * s < n_time) row[2 + tid + 256 * s] = sum[s];
+}
+
+// k_tftd: the launch shape of k_tf -- workgroup c serves the annuli [c chunk, (c + 1) chunk), a wave one annulus at a time, its
+// lanes the (g bin, fine bin) pairs -- and each lane walks the n_time samples of em[ia].  PASS 0: the largest |deposit| (red[0]).
+// PASS 1: every deposit as two integers on the grid sc[0], into the workgroup's LDS histogram (LDS = 1) or into acc.  The
+// samples ascend, so consecutive deposits of a branch mostly share a t cell: the lane keeps the cell's running integer pair
+// and adds it once when the cell changes -- integer sums, so the result does not see it.
+template <int PASS, int LDS>
+__global__ void __launch_bounds__(256) k_tftd(const gr_tf::Set* __restrict__ set, gr_tf::Quad quad, const double* __restrict__ g_edges, int n_g,
+                                              const double* __restrict__ t_edges, int n_t, int upscale, int n_time, double t0,
+                                              const double* __restrict__ em, int chunk, unsigned long long* red,
+                                              const CoronaScale* __restrict__ sc, unsigned long long* acc)
+{
+    GR_LAG_NO_CONTRACT
+    extern __shared__ unsigned long long tftd_hist[];
+    const gr_tf::Set s = *set;
+    const int cells = n_g * n_t;
+    unsigned long long* h = nullptr;
+    CoronaScale scale{};
+    if (PASS == 1) {
+        h = LDS ? tftd_hist : acc;
+        scale = sc[0];
+        if (LDS) {
+            for (int i = threadIdx.x; i < 2 * cells; i += blockDim.x) tftd_hist[i] = 0ull;
+            __syncthreads();
+        }
+    }
+    const int64_t a0 = (int64_t)blockIdx.x * chunk, a1 = a0 + chunk < s.n_int ? a0 + chunk : s.n_int;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n_fine = (n_g - 1) * upscale;
+    unsigned long long vmax = 0ull;
+    for (int64_t ia = a0 + wave; ia < a1; ia += 4) {
+        const gr_tf::Annulus an = gr_tf::annulus_of(s, ia);
+        const double* row = em + (size_t)ia * (size_t)(2 + n_time);
+        const double t_lo = row[0], t_hi = row[1];
+        const double dt_step = (t_hi - t_lo) / (double)n_time;
+        for (int idx = lane; idx < n_fine; idx += 64) {
+            const int j = idx / upscale, i = idx - j * upscale;
+            const double glo = gr_tf::clampd(g_edges[j] / s.g_scale, an.gmin, an.gmax), ghi = gr_tf::clampd(g_edges[j + 1] / s.g_scale, an.gmin, an.gmax);
+            if (glo == ghi) continue;
+            double lo, hi;
+            gr_tftd::fine_bin(glo, ghi, upscale, i, lo, hi);
+            const gr_tftd::FineBin fb = gr_tftd::fine_bin_of(s, an, quad, lo, hi);
+            int cur[2] = { -1, -1 };
+            long long run_hi[2] = { 0, 0 }, run_lo[2] = { 0, 0 };
+            for (int k = 0; k < n_time; ++k) {
+                const double time = gr_tftd::time_sample(t_lo, t_hi, n_time, k), e = row[2 + k];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    double v;
+                    int it;
+                    if (!gr_tftd::deposit(fb.k[b], fb.tb[b], time, e, dt_step, t0, t_edges, n_t, v, it)) continue;
+                    if (PASS == 0) {
+                        const unsigned long long bits = (unsigned long long)__double_as_longlong(fabs(v));
+                        vmax = bits > vmax ? bits : vmax;
+                    } else {
+                        const int cell = j * n_t + it;
+                        if (cell != cur[b]) {
+                            if (cur[b] >= 0) {
+                                atomicAdd(h + cur[b], (unsigned long long)run_hi[b]);
+                                atomicAdd(h + cells + cur[b], (unsigned long long)run_lo[b]);
+                            }
+                            cur[b] = cell;
+                            run_hi[b] = run_lo[b] = 0;
+                        }
+                        long long fh, fl;
+                        corona_split(v, scale, fh, fl);
+                        run_hi[b] += fh;
+                        run_lo[b] += fl;
+                    }
+                }
+            }
+            if (PASS == 1) {
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+                    if (cur[b] >= 0) {
+                        atomicAdd(h + cur[b], (unsigned long long)run_hi[b]);
+                        atomicAdd(h + cells + cur[b], (unsigned long long)run_lo[b]);
+                    }
+            }
+        }
+    }
+    if (PASS == 0) {
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_down(vmax, off, 64);
+            vmax = o > vmax ? o : vmax;
+        }
+        if (lane == 0 && vmax) atomicMax(red, vmax);
+    } else if (LDS) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * cells; i += blockDim.x)
+            if (tftd_hist[i] != 0ull) atomicAdd(acc + i, tftd_hist[i]);
+    }
+}
+
 int32_t rayset_share(const gr_rayset* rays, int32_t n, int k, gr_rayset& out, int64_t* off_out);      // (below, with the other *_multi helpers)
 }  // namespace
 }  // extern "C++"
@@ -2988,7 +3180,7 @@ int32_t gr_lagtransfer_rows(gr_ctx* ctx, double* out)
 // ---- transfer functions integrated on the device: gr_tf_lineprofile / gr_tf_lagtransfer ----
 // the checks that read only the arguments, before anything touches the device
 static int32_t tf_args(const gr_tfset* sets, int64_t n_sets, const gr_tfquad* quad, const double* g_edges, int64_t n_g,
-                       const double* t_edges, int64_t n_t, bool lag, const double* out)
+                       const double* t_edges, int64_t n_t, bool lag, const double* out, bool annulus_values = true)
 {
     if (!sets) return fail(GR_ERR_INVALID_ARGUMENT, "sets is null");
     if (!quad) return fail(GR_ERR_INVALID_ARGUMENT, "quad is null");
@@ -3011,7 +3203,7 @@ static int32_t tf_args(const gr_tfset* sets, int64_t n_sets, const gr_tfquad* qu
         if (s.n_r > lim || s.n_int > lim) return fail(GR_ERR_INVALID_ARGUMENT, who + "at most 2^24 radii / annuli");
         if (!s.radii || !s.gmin || !s.gmax || !s.off || !s.knot_g || !s.knot_f || !s.knot_t)
             return fail(GR_ERR_INVALID_ARGUMENT, who + "a transfer-function array is null");
-        if (!s.r_int || !s.eps_int || (lag && !s.tsd_int)) return fail(GR_ERR_INVALID_ARGUMENT, who + "an annulus array is null");
+        if (!s.r_int || (annulus_values && (!s.eps_int || (lag && !s.tsd_int)))) return fail(GR_ERR_INVALID_ARGUMENT, who + "an annulus array is null");
         if (s.off[0] < 0) return fail(GR_ERR_INVALID_ARGUMENT, who + "offsets must ascend from off[0] >= 0");
         for (int64_t i = 0; i < 2 * s.n_r; ++i) {
             const int64_t n = s.off[i + 1] - s.off[i];
@@ -3143,6 +3335,157 @@ int32_t gr_tf_lagtransfer(gr_ctx* ctx, const gr_tfset* sets, int64_t n_sets, con
                           const double* t_edges, int64_t n_t, double* out)
 {
     return tf_integrate(ctx, sets, n_sets, quad, g_edges, n_g, t_edges, n_t, true, out);
+}
+
+// ---- gr_tf_lagtransfer_td: the lag transfer function of a time-dependent emissivity ----
+// the checks that read only the arguments
+static int32_t tftd_args(const gr_tfprofile* p, int64_t g_upscale, int64_t n_time)
+{
+    if (!p) return fail(GR_ERR_INVALID_ARGUMENT, "prof is null");
+    if (n_time < 2 || n_time > gr_tftd::kMaxTime) return fail(GR_ERR_INVALID_ARGUMENT, "n_time must be in 2 ... 1024");
+    if (g_upscale < 1 || g_upscale > gr_tftd::kMaxUpscale) return fail(GR_ERR_INVALID_ARGUMENT, "g_upscale must be in 1 ... 64");
+    if (p->n_rings < 1 || p->n_rings > gr_tftd::kMaxRings) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: n_rings must be in 1 ... 1024");
+    if (!p->ring_weight || !p->ring_dt || !p->arm_off || !p->curve_off || !p->knot_r || !p->knot_t || !p->knot_e)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: an array is null");
+    if (p->arm_off[0] < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: arm offsets must ascend from arm_off[0] >= 0");
+    for (int64_t a = 0; a < 2 * p->n_rings; ++a) {
+        const int64_t n = p->arm_off[a + 1] - p->arm_off[a];
+        if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: arm offsets must ascend");
+        if (n < 2 || n > gr_tftd::kMaxCurves) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: an arm needs 2 ... 1024 curves");
+    }
+    const int64_t c0 = p->arm_off[0], c1 = p->arm_off[2 * p->n_rings];
+    if (p->curve_off[c0] < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: curve offsets must ascend from an offset >= 0");
+    for (int64_t c = c0; c < c1; ++c) {
+        const int64_t n = p->curve_off[c + 1] - p->curve_off[c];
+        if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: curve offsets must ascend");
+        if (n < 2) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: a curve needs at least 2 knots");
+    }
+    if (p->curve_off[c1] - p->curve_off[c0] > ((int64_t)1 << 28)) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tfprofile: at most 2^28 knots");
+    return GR_OK;
+}
+
+// One block as tf_integrate stages it: descriptors | edges | the set's arrays (ε = 1) | the profile's arrays, behind them
+// em | red | scale | acc.  k_tftd_em fills em, k_tftd<0> finds the largest deposit, k_tftd<1> accumulates on the grid it gives.
+int32_t gr_tf_lagtransfer_td(gr_ctx* ctx, const gr_tfset* set, const gr_tfprofile* prof, const gr_tfquad* quad, const double* g_edges,
+                             int64_t n_g, const double* t_edges, int64_t n_t, int64_t g_upscale, int64_t n_time, double t0, double* out,
+                             double* em_out)
+{
+    int32_t rc;
+    if ((rc = tf_args(set, 1, quad, g_edges, n_g, t_edges, n_t, true, out, false)) != GR_OK) return rc;
+    if ((rc = tftd_args(prof, g_upscale, n_time)) != GR_OK) return rc;
+    if (n_g * g_upscale > ((int64_t)1 << 24)) return fail(GR_ERR_INVALID_ARGUMENT, "at most 2^24 fine g bins (n_g * g_upscale)");
+    if (set->n_int * g_upscale * n_time > ((int64_t)1 << 38)) return fail(GR_ERR_INVALID_ARGUMENT, "at most 2^38 deposits per cell (n_int * g_upscale * n_time)");
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    GR_HIP(hipSetDevice(ctx->device));
+    const gr_tfset& s = *set;
+    const gr_tfprofile& p = *prof;
+    const size_t cells = (size_t)(n_g * n_t);
+    const size_t nr = (size_t)s.n_r, ni = (size_t)s.n_int, nk = (size_t)(s.off[2 * s.n_r] - s.off[0]);
+    const size_t rings = (size_t)p.n_rings;
+    const int64_t c0 = p.arm_off[0], c1 = p.arm_off[2 * p.n_rings], k0 = p.curve_off[c0];
+    const size_t n_curves = (size_t)(c1 - c0), n_knots = (size_t)(p.curve_off[c1] - k0);
+    static_assert(sizeof(gr_tf::Set) % 8 == 0 && sizeof(gr_tftd::Profile) % 8 == 0, "8-byte units");
+    const size_t set_w = sizeof(gr_tf::Set) / 8, desc_w = set_w + sizeof(gr_tftd::Profile) / 8;
+    const size_t up_w = desc_w + (size_t)n_g + (size_t)n_t + 3 * nr + 2 * ni + (2 * nr + 1) + 3 * nk
+                        + 2 * rings + (2 * rings + 1) + (n_curves + 1) + 3 * n_knots;
+    const size_t em_row = 2 + (size_t)n_time;
+    const size_t em_w = up_w, red_w = em_w + ni * em_row, sc_w = red_w + 1, acc_w = sc_w + 2;
+    const size_t bytes = 8 * (acc_w + 2 * cells) + 64;
+    void* own = nullptr;
+    struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } free_own{own};
+    char* base;
+    if (bytes > ((size_t)32 << 20)) {
+        GR_HIP(hipMalloc(&own, bytes));
+        base = (char*)own;
+    } else {
+        if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, bytes)) != GR_OK) return rc;
+        base = (char*)ctx->d_in;
+    }
+    std::vector<uint64_t> blob(up_w);
+    const double* d0 = (const double*)base;
+    size_t at = desc_w;
+    auto put = [&](const void* src, size_t n) {
+        std::memcpy(blob.data() + at, src, 8 * n);
+        const double* d = d0 + at;
+        at += n;
+        return d;
+    };
+    const double* d_g = put(g_edges, (size_t)n_g);
+    const double* d_t = put(t_edges, (size_t)n_t);
+    gr_tf::Set d;
+    d.n_r = s.n_r; d.n_int = s.n_int; d.r_min = s.r_min; d.g_scale = s.g_scale;
+    d.radii = put(s.radii, nr); d.gmin = put(s.gmin, nr); d.gmax = put(s.gmax, nr);
+    d.r_int = put(s.r_int, ni);
+    {
+        const std::vector<double> ones(ni, 1.0);                 // the annulus weight has no ε: annulus_of multiplies by 1
+        d.eps = d.tsd = put(ones.data(), ni);
+    }
+    {
+        int64_t* off = (int64_t*)(blob.data() + at);
+        d.off = (const int64_t*)put(s.off, 2 * nr + 1);
+        for (size_t i = 0; i <= 2 * nr; ++i) off[i] -= s.off[0];
+    }
+    d.kg = put(s.knot_g + s.off[0], nk); d.kf = put(s.knot_f + s.off[0], nk); d.kt = put(s.knot_t + s.off[0], nk);
+    std::memcpy(blob.data(), &d, sizeof d);
+    gr_tftd::Profile dp;
+    dp.n_rings = p.n_rings;
+    dp.w = put(p.ring_weight, rings); dp.dt = put(p.ring_dt, rings);
+    {
+        int64_t* off = (int64_t*)(blob.data() + at);
+        dp.arm_off = (const int64_t*)put(p.arm_off, 2 * rings + 1);
+        for (size_t i = 0; i <= 2 * rings; ++i) off[i] -= c0;
+        off = (int64_t*)(blob.data() + at);
+        dp.curve_off = (const int64_t*)put(p.curve_off + c0, n_curves + 1);
+        for (size_t i = 0; i <= n_curves; ++i) off[i] -= k0;
+    }
+    dp.kr = put(p.knot_r + k0, n_knots); dp.kt = put(p.knot_t + k0, n_knots); dp.ke = put(p.knot_e + k0, n_knots);
+    std::memcpy(blob.data() + set_w, &dp, sizeof dp);
+    if (at != up_w) return fail(GR_ERR_INVALID_ARGUMENT, "gr_tf_lagtransfer_td: the staged block does not match its layout");
+    gr_tf::Quad q{};
+    q.h = quad->h; q.n = (int)quad->n_q;
+    for (int i = 0; i < q.n; ++i) { q.x[i] = quad->x[i]; q.w[i] = quad->w[i]; }
+    double* d_em = (double*)base + em_w;
+    unsigned long long* d_red = (unsigned long long*)base + red_w;
+    CoronaScale* d_sc = (CoronaScale*)((unsigned long long*)base + sc_w);
+    unsigned long long* d_acc = (unsigned long long*)base + acc_w;
+    const gr_tf::Set* d_set = (const gr_tf::Set*)base;
+    const gr_tftd::Profile* d_prof = (const gr_tftd::Profile*)((const uint64_t*)base + set_w);
+    GR_HIP(hipMemcpyAsync(base, blob.data(), 8 * up_w, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemsetAsync(d_red, 0, 8 * (acc_w - red_w + 2 * cells), ctx->stream));
+    hipLaunchKernelGGL(k_tftd_em, dim3((unsigned)ni), dim3(256), 0, ctx->stream, d_set, d_prof, (int)n_time, d_em);
+    GR_HIP(hipGetLastError());
+    int64_t chunk = ctx->tf_chunk;
+    if (chunk <= 0) {
+        chunk = 4;
+        while ((s.n_int + chunk - 1) / chunk > 65536) chunk *= 2;
+    }
+    const int64_t n_chunks = (s.n_int + chunk - 1) / chunk;
+    const dim3 grid((unsigned)n_chunks), block(256);              // (n_int <= 2^24 annuli, a chunk holds at least one)
+    hipLaunchKernelGGL((k_tftd<0, 0>), grid, block, 0, ctx->stream, d_set, q, d_g, (int)n_g, d_t, (int)n_t, (int)g_upscale, (int)n_time, t0,
+                       (const double*)d_em, (int)chunk, d_red, d_sc, d_acc);
+    GR_HIP(hipGetLastError());
+    unsigned long long red = 0ull;
+    GR_HIP(hipMemcpyAsync(&red, d_red, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (em_out) GR_HIP(hipMemcpyAsync(em_out, d_em, 8 * ni * em_row, hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
+    double vmax;
+    std::memcpy(&vmax, &red, sizeof vmax);
+    // a cell takes at most two deposits per annulus, fine bin and time sample
+    const CoronaGrid grd = corona_grid(vmax, 2 * s.n_int * g_upscale * n_time);
+    GR_HIP(hipMemcpyAsync(d_sc, &grd.sc, sizeof(CoronaScale), hipMemcpyHostToDevice, ctx->stream));
+    const size_t lds = sizeof(unsigned long long) * 2 * cells;
+    if (lds <= 40 * 1024)
+        hipLaunchKernelGGL((k_tftd<1, 1>), grid, block, lds, ctx->stream, d_set, q, d_g, (int)n_g, d_t, (int)n_t, (int)g_upscale, (int)n_time, t0,
+                           (const double*)d_em, (int)chunk, d_red, d_sc, d_acc);
+    else
+        hipLaunchKernelGGL((k_tftd<1, 0>), grid, block, 0, ctx->stream, d_set, q, d_g, (int)n_g, d_t, (int)n_t, (int)g_upscale, (int)n_time, t0,
+                           (const double*)d_em, (int)chunk, d_red, d_sc, d_acc);
+    GR_HIP(hipGetLastError());
+    std::vector<long long> acc(2 * cells);
+    GR_HIP(hipMemcpyAsync(acc.data(), d_acc, 8 * acc.size(), hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t c = 0; c < cells; ++c) out[c] = gr_lag::corona_sum(acc[c], acc[cells + c], grd);
+    return GR_OK;
 }
 
 int32_t gr_ray_tangent(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,

@@ -905,7 +905,7 @@ def integrate_lineprofile(ε, tfs: InterpolatingTransferBranches, g_grid, *, rmi
 
 
 def integrate_lagtransfer(prof, tfs: InterpolatingTransferBranches, g_grid, t_grid, *, rmin=None, rmax=None, g_scale=1.0,
-                          h=1e-8, n_radii=1000, quadrature_points=7, t0=0.0, ensemble=None):
+                          h=1e-8, n_radii=1000, quadrature_points=7, t0=0.0, ensemble=None, g_grid_upscale=None, n_time_steps=None):
     """integrate_lagtransfer (integration.jl:264-289,374-453): the (g, t) response of the disc to a flash
     of the corona.  `prof` provides emissivity_at(r) and coordtime_at(r) (source -> disc time); each
     annulus and g-bin deposits its lower- and upper-branch flux at (source -> disc) + (disc -> observer)
@@ -913,9 +913,26 @@ def integrate_lagtransfer(prof, tfs: InterpolatingTransferBranches, g_grid, t_gr
     row-maximum rescaling is discarded by the reference's own call chain and is not applied).
 
     `ensemble=EnsembleMI355X(...)` integrates on the device (gr_tf_lagtransfer): ε and the source -> disc time are
-    evaluated at the annuli here, so any profile serves."""
+    evaluated at the annuli here, so any profile serves.
+
+    A `RingCoronaProfile` or a `DiscCoronaProfile` (corona.py) is a time-dependent emissivity and takes the method of
+    its own (ring.jl:857-950): every g bin is cut into `g_grid_upscale` (default 1) fine bins, and each branch of each
+    fine bin is smeared over `n_time_steps` (default 100, the reference's N_t_steps) arrival times between the profile's
+    limits at the annulus, weighted by ε(t) there.  With `ensemble=` that is gr_tf_lagtransfer_td.  The two keywords belong
+    to these profiles alone."""
+    from .corona import DiscCoronaProfile, RingCoronaProfile
     from .planes import GeometricGrid
 
+    if isinstance(prof, (RingCoronaProfile, DiscCoronaProfile)):
+        kw = dict(rmin=rmin, rmax=rmax, g_scale=g_scale, h=h, n_radii=n_radii, quadrature_points=quadrature_points, t0=t0,
+                  g_grid_upscale=1 if g_grid_upscale is None else g_grid_upscale,
+                  n_time_steps=100 if n_time_steps is None else n_time_steps)
+        if ensemble is not None:
+            return _integrate_lagtransfer_td_device(prof, tfs, g_grid, t_grid, call=_tftd_library_call(ensemble), **kw)
+        return _integrate_lagtransfer_td(prof, tfs, g_grid, t_grid, **kw)
+    if g_grid_upscale is not None or n_time_steps is not None:
+        raise NotImplementedError("g_grid_upscale and n_time_steps belong to the time-dependent profiles "
+                                  f"(RingCoronaProfile, DiscCoronaProfile), not to {type(prof).__name__}")
     if ensemble is not None:
         return _integrate_lagtransfer_device(prof, tfs, g_grid, t_grid, rmin=rmin, rmax=rmax, g_scale=g_scale, h=h,
                                              n_radii=n_radii, quadrature_points=quadrature_points, t0=t0,
@@ -1107,6 +1124,167 @@ def _integrate_lagtransfer_device(prof, tfs, g_grid, t_grid, *, rmin, rmax, g_sc
     tsd = np.array([float(prof.coordtime_at(r)) - t0 for r in radii])
     s, keep = _tf_set(tfs, radii, eps, tsd, rmin, g_scale)
     out = _tf_run([s], g_grid, t_grid, h, quadrature_points, call)[0]
+    flux = out.copy()
+    flux[:-1, :] = flux[:-1, :] / (g_grid[1:] + g_grid[:-1])[:, None]
+    total = flux[:-1, :].sum()
+    if total > 0:
+        flux = flux / total
+    return flux
+
+
+# ------------------------------------------------------------------------------------------
+# the lag transfer function of a time-dependent emissivity (ring.jl:857-950): the host route, then the device's
+# (gr_tf_lagtransfer_td; csrc/gr_tftd.hpp)
+# ------------------------------------------------------------------------------------------
+def _td_check(g_grid_upscale, n_time_steps):
+    if not (1 <= int(g_grid_upscale) <= 64) or int(g_grid_upscale) != g_grid_upscale:
+        raise ValueError("g_grid_upscale must be an integer in 1 ... 64")
+    if not (2 <= int(n_time_steps) <= 1024) or int(n_time_steps) != n_time_steps:
+        raise ValueError("n_time_steps must be an integer in 2 ... 1024")
+    return int(g_grid_upscale), int(n_time_steps)
+
+
+def time_dependent_emissivity_table(prof, radii, n_time_steps=100):
+    """Per radius what the time loop of an annulus needs of a time-dependent profile: row = (t_lo, t_hi, ε(time_k) for the
+    n_time_steps samples of linspace(t_lo, t_hi, n_time_steps)).  The layout of gr_tf_lagtransfer_td's em_out."""
+    table = np.zeros((len(radii), 2 + n_time_steps))
+    for row, rₑ in zip(table, radii):
+        a, b = prof.emissivity_interp_limits(rₑ)
+        row[0], row[1] = a, b
+        row[2:] = prof.emissivity_interp(rₑ)(np.linspace(a, b, n_time_steps))
+    return table
+
+
+def _integrate_lagtransfer_td(prof, tfs, g_grid, t_grid, *, rmin, rmax, g_scale, h, n_radii, quadrature_points, t0, g_grid_upscale,
+                              n_time_steps, _deposits=None):
+    """ring.jl:857-950.  ε(time) depends on the annulus and the sample only, so it is evaluated once per annulus, not
+    once per fine bin as the reference does: the sums are the same.  `_deposits`: a list that receives the number of
+    deposits that landed on the grid with a value other than 0."""
+    from .planes import GeometricGrid
+
+    U, n_time = _td_check(g_grid_upscale, n_time_steps)
+    g_grid = np.asarray(g_grid, dtype=np.float64)
+    t_grid = np.asarray(t_grid, dtype=np.float64)
+    rmin = tfs.inner_radius() if rmin is None else rmin
+    rmax = tfs.outer_radius() if rmax is None else rmax
+    X, W = np.polynomial.legendre.leggauss(quadrature_points)
+    radii = np.asarray(GeometricGrid()(rmin, rmax, n_radii))
+    table = time_dependent_emissivity_table(prof, radii, n_time)
+    out = np.zeros((g_grid.size, t_grid.size))
+    count = 0
+    r_prev = rmin - (radii[1] - rmin)
+    for rₑ, row in zip(radii, table):
+        gmin, gmax, _ = tfs.at(rₑ)
+        br = tfs._last
+        span = gmax - gmin
+
+        def make_S(fb):
+            def S(g):
+                gs = (g - gmin) / span
+                f = fb(gs)
+                with np.errstate(all="ignore"):
+                    return (g * g) * np.where(np.isnan(f), 0.0, f) * g / np.sqrt(gs * (1.0 - gs))
+            return S
+
+        def times(gs):
+            gs = np.clip(gs, 0.0, 1.0)
+            tl, tu = br["lower_t"](gs), br["upper_t"](gs)
+            lo_e, hi_e = gs < h, gs > 1.0 - h
+            ω = np.where(lo_e, gs / h, 1.0 - (1.0 - gs) / h)
+            at = np.where(lo_e, h, 1.0 - h)
+            tle, tue = br["lower_t"](at), br["upper_t"](at)
+            edge = lo_e | hi_e
+            return np.where(edge, tle * ω + (1.0 - ω) * tue, tl), np.where(edge, tue * ω + (1.0 - ω) * tle, tu)
+
+        θ = (rₑ - r_prev) * rₑ * math.pi / span             # no ε here: it is a function of time
+        r_prev = rₑ
+        a, b, em = row[0], row[1], row[2:]
+        δt = (b - a) / n_time
+        sample = np.linspace(a, b, n_time)
+        glo = np.clip(g_grid[:-1] / g_scale, gmin, gmax)
+        ghi = np.clip(g_grid[1:] / g_scale, gmin, gmax)
+        live = np.nonzero(glo != ghi)[0]
+        if live.size == 0:
+            continue
+        Δg = (ghi[live] - glo[live]) / U
+        lo = (glo[live][:, None] + np.arange(U)[None, :] * Δg[:, None]).ravel()
+        hi = lo + np.repeat(Δg, U)
+        rows = np.repeat(live, U)
+        tl1, tu1 = times((lo - gmin) / span)
+        tl2, tu2 = times((hi - gmin) / span)
+        for fb, tb in ((br["lower_f"], (tl1 + tl2) / 2), (br["upper_f"], (tu1 + tu2) / 2)):
+            k = _integrate_bins(make_S(fb), lo, hi, gmin, gmax, h, X, W)
+            arrival = (tb[:, None] + sample[None, :]) - t0
+            cell = np.searchsorted(t_grid, arrival.ravel(), side="left").reshape(arrival.shape)
+            value = ((k * θ)[:, None] * em[None, :]) * δt
+            ok = cell < t_grid.size
+            np.add.at(out, (np.broadcast_to(rows[:, None], cell.shape)[ok], cell[ok]), value[ok])
+            count += int(np.count_nonzero(ok & (value != 0.0)))
+    if _deposits is not None:
+        _deposits.append(count)
+    flux = out.copy()
+    flux[:-1, :] = flux[:-1, :] / (g_grid[1:] + g_grid[:-1])[:, None]
+    total = flux[:-1, :].sum()
+    if total > 0:
+        flux = flux / total
+    return flux
+
+
+def _tftd_profile(prof):
+    """(gr_tfprofile, the arrays it points to): the rings' weights and delays are evaluated here"""
+    from . import _lib
+    from .corona import RingCoronaProfile
+
+    if isinstance(prof, RingCoronaProfile):
+        rings, w, dt = [prof], [1.0], [0.0]
+    else:
+        rings = prof.rings
+        w, dt = [prof._ring_weighting(i) for i in range(len(rings))], prof._delays()
+    arms = [arm for ring in rings for arm in (ring.left_arm, ring.right_arm)]
+    arm_off = np.concatenate([[0], np.cumsum([len(arm.radii) for arm in arms])]).astype(np.int64)
+    curves = [(r, t, e) for arm in arms for r, t, e in zip(arm.radii, arm.t, arm.ε)]
+    curve_off = np.concatenate([[0], np.cumsum([c[0].size for c in curves])]).astype(np.int64)
+    kr, kt, ke = (np.ascontiguousarray(np.concatenate([c[k] for c in curves]), dtype=np.float64) for k in range(3))
+    w, dt = np.ascontiguousarray(w, dtype=np.float64), np.ascontiguousarray(dt, dtype=np.float64)
+    p = _lib.gr_tfprofile(len(rings), w.ctypes.data, dt.ctypes.data, arm_off.ctypes.data, curve_off.ctypes.data,
+                          kr.ctypes.data, kt.ctypes.data, ke.ctypes.data)
+    return p, (w, dt, arm_off, curve_off, kr, kt, ke)
+
+
+def _tftd_library_call(ensemble):
+    """gr_tf_lagtransfer_td bound to the ensemble's context, with the argument list of `_integrate_lagtransfer_td_device`'s `call`"""
+    from . import _lib
+
+    L, ctx = _lib.load(), ensemble.ctx.handle
+    return lambda *args: _lib.check(L.gr_tf_lagtransfer_td(ctx, *args))
+
+
+def _integrate_lagtransfer_td_device(prof, tfs, g_grid, t_grid, *, rmin, rmax, g_scale, h, n_radii, quadrature_points, t0,
+                                     g_grid_upscale, n_time_steps, call, em_out=None):
+    """`em_out`: a list that receives the (n_radii, 2 + n_time_steps) table the device formed (time_dependent_emissivity_table)"""
+    import ctypes as C
+
+    from . import _lib
+    from .planes import GeometricGrid
+
+    U, n_time = _td_check(g_grid_upscale, n_time_steps)
+    g_grid = np.ascontiguousarray(g_grid, dtype=np.float64)
+    t_grid = np.ascontiguousarray(t_grid, dtype=np.float64)
+    rmin = tfs.inner_radius() if rmin is None else rmin
+    rmax = tfs.outer_radius() if rmax is None else rmax
+    radii = np.asarray(GeometricGrid()(rmin, rmax, n_radii), dtype=np.float64)
+    s, keep = _tf_set(tfs, radii, np.ones(radii.size), np.zeros(radii.size), rmin, g_scale)
+    s.eps_int = s.tsd_int = None                            # (not read: the weight has no ε, the times come from the profile)
+    p, keep_p = _tftd_profile(prof)
+    X, W = np.polynomial.legendre.leggauss(quadrature_points)
+    X, W = np.ascontiguousarray(X), np.ascontiguousarray(W)
+    q = _lib.gr_tfquad(float(h), X.size, X.ctypes.data, W.ctypes.data)
+    out = np.zeros((g_grid.size, t_grid.size))
+    em = np.zeros((radii.size, 2 + n_time)) if em_out is not None else None
+    call(C.byref(s), C.byref(p), C.byref(q), g_grid.ctypes.data, g_grid.size, t_grid.ctypes.data, t_grid.size, U, n_time, float(t0),
+         out.ctypes.data, em.ctypes.data if em is not None else None)
+    if em_out is not None:
+        em_out.append(em)
     flux = out.copy()
     flux[:-1, :] = flux[:-1, :] / (g_grid[1:] + g_grid[:-1])[:, None]
     total = flux[:-1, :].sum()

@@ -659,6 +659,40 @@ int32_t gr_tf_lineprofile(gr_ctx* ctx, const gr_tfset* sets, int64_t n_sets, con
 int32_t gr_tf_lagtransfer(gr_ctx* ctx, const gr_tfset* sets, int64_t n_sets, const gr_tfquad* quad, const double* g_edges,
                           int64_t n_g, const double* t_edges, int64_t n_t, double* out /* host, n_sets x n_g x n_t, raw sums */);
 
+/* ---- the lag transfer function of a time-dependent emissivity (added within ABI 8, nothing else changes):
+ * integrate_lagtransfer for the RingCoronaProfile / DiscCoronaProfile of an extended corona (src/corona/radial.jl:164-324,
+ * src/corona/models/ring.jl:857-950).  A gr_tfprofile is n_rings rings of two arms; an arm is a run of 2 ... 1024 curves
+ * (one per slice of the source's sky), a curve >= 2 knots (ρ ascending, t, ε) on the disc.  At an annulus every curve that
+ * covers rₑ gives a knot (t, ε) by NaNLinearInterpolator, a curve that does not a NaN; an arm's ε(t) interpolates its knots
+ * sorted by t (stable, NaN last) between the first and the last of them and is 0 outside -- so everywhere, if any slice
+ * misses rₑ.  The profile at time x is Σ_i (left_i(x - ring_dt[i]) + right_i(x - ring_dt[i])) ring_weight[i]; its limits are
+ * the extrema over the arms of the knots' times plus ring_dt, an arm without a knot counting as (0, 0).
+ * One set per call; eps_int and tsd_int of the set are not read (they may be null).  Per annulus the weight is
+ * (rₑ - r_prev) rₑ π / (gmax - gmin); every g bin is cut into g_upscale fine bins, and each branch of each fine bin deposits
+ * ((integrate_bin weight) ε(time_k)) (t_hi - t_lo) / n_time at the first t edge >= (branch time + time_k) - t0 for the n_time
+ * samples time_k of linspace(t_lo, t_hi, n_time) (dropped past the last edge).  Results are RAW sums on a fixed-point grid,
+ * as gr_tf_lagtransfer forms them: the same arguments give the same bits on every run and for every "tf_chunk".
+ * em_out, unless null, receives per annulus t_lo, t_hi and the n_time values ε(time_k).
+ * All pointers are host pointers, staged per call; nothing is kept on the context.
+ * GR_ERR_INVALID_ARGUMENT, before anything touches the device, for: what gr_tf_lagtransfer refuses, a null pointer, n_rings
+ * outside 1 ... 1024, an arm with fewer than 2 or more than 1024 curves, a curve with fewer than 2 knots, offsets that do not
+ * ascend, n_time outside 2 ... 1024 and g_upscale outside 1 ... 64. */
+typedef struct gr_tfprofile {
+    int64_t n_rings;            /* 1 ... 1024                                                                   */
+    const double* ring_weight;  /* n_rings (1 for a single RingCoronaProfile)                                   */
+    const double* ring_dt;      /* n_rings (0 for a single RingCoronaProfile)                                   */
+    const int64_t* arm_off;     /* 2 n_rings + 1: arm (i, left) owns curves [arm_off[2i], arm_off[2i+1]), (i, right) the next run */
+    const int64_t* curve_off;   /* arm_off[2 n_rings] + 1 offsets into the knot arrays                          */
+    const double* knot_r;       /* ρ, ascending within a curve                                                  */
+    const double* knot_t;       /* source -> disc coordinate time on the knots                                  */
+    const double* knot_e;       /* emissivity on the knots                                                      */
+} gr_tfprofile;
+int32_t gr_tf_lagtransfer_td(gr_ctx* ctx, const gr_tfset* set, const gr_tfprofile* prof, const gr_tfquad* quad,
+                             const double* g_edges, int64_t n_g, const double* t_edges, int64_t n_t,
+                             int64_t g_upscale, int64_t n_time, double t0,
+                             double* out /* host, n_g x n_t raw sums */,
+                             double* em_out /* host or NULL: n_int x (2 + n_time): t_lo, t_hi, em[k] */);
+
 /* ---- tabulated metrics (ABI 7; segments, axis terms: ABI 8; GR_METRIC_TABULATED): the AbstractMetric plugin interface on the device ----
  * Host-only functions (no context, no device): plan a grid, learn its nodes, fit, check.
  *
