@@ -329,20 +329,6 @@ constexpr creal SINCOS_ROT_MAX = 0.03125;
 // most one scalar / literal operand: the other constant has to sit in a vector register.  Left to itself the compiler
 // rebuilds both (v_mov_b32 pairs + a copy) at each of the six stage points of a step -- 36 of the step's ~130 non-FP64
 // vector instructions.  So each such FMA is opened as a product and a sum, one scalar operand each.
-//
-// RotK is what an earlier form left behind: it kept the two addends (1/120, 1/24) in registers for the life of the ray.
-// Nothing reads them now, and the compiler drops them -- but with the member gone from Ray it allocates the registers of
-// k_trace_persistent<TabulatedMetric, GR_DISC_MESH> differently (two v_mov_b32 more) and swaps operands in 87 other kernels.
-// The struct, Ray::rotk and its load() stay so that removing the build switches compiles to the same kernels
-// (profiles/r8_refactor_isa.txt); they can go with the next change that alters the integrator's code anyway.
-struct RotK {
-    real s2, c2;
-    GR_DEV void load()
-    {
-        s2 = 8.3333333333333333e-03;
-        c2 = 4.1666666666666664e-02;
-    }
-};
 template <class T>
 GR_DEV void sincos_rot_impl(T th0, T s0, T c0, T th, T& s_out, T& c_out)
 {
@@ -2965,7 +2951,6 @@ struct Ray {
     hreal dt, h;      // proposed step, last used step
     real cprev;       // disc condition at x
     real sth, cth;    // sin θ, cos θ at x (base of the stage rotations)
-    RotK rotk;        // unread (see RotK)
     float lq_old;       // log2(qold)
     int32_t ev_top;     // upper bracket j of Θ = j/7 when an event is pending
     int64_t j;          // local (swizzled) ray index
@@ -3524,7 +3509,6 @@ struct Ray {
         j = jl;
         status = GR_STATUS_NO_STATUS;
         flags = 0; nacc = 0; nrej = 0; ev_top = 0;
-        rotk.load();
         constrained_u0(m, p, jl, x, v);
         t = p.cfg.lambda0;
         h = 0.0;
@@ -4413,7 +4397,10 @@ struct Ray {
     }
 
     // unpack_solution + apply_to_image!
-    GR_DEV void finalize(const Metric& m, const Params& p, const LdsView& lds)
+    // decided_at_start: init() returned true for this ray (the start cull).  Under the cull's gating an image launch ignores its
+    // misses (escape_cull_radius: the filter is "intersected"), so the pixel is the fill value and nothing else of the ray is
+    // read: it goes straight to its store.
+    GR_DEV void finalize(const Metric& m, const Params& p, const LdsView& lds, bool decided_at_start = false)
     {
         if (kContinuous && (flags & RAY_EVENT)) {
             resolve_event(p);
@@ -4425,6 +4412,12 @@ struct Ray {
         if (cd.tile_cost) {
             const int64_t ti = tile_cost_index(cd);
             if (ti >= 0) cd.tile_cost[ti] = (uint32_t)(nacc + nrej);
+        }
+        if constexpr (kEscapeCull) {
+            if (decided_at_start && cd.out_mode == 0) {
+                cd.image[cd.out_global ? range_map(cd, j) : j] = (double)(real)cd.pf.fill;
+                return;
+            }
         }
         if (cd.out_mode == 1) {
             real x0[4], v0[4];

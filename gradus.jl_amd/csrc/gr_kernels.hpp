@@ -4,6 +4,7 @@
 #pragma once
 
 #include "gr_device.hpp"
+#include "gr_stats_fold.hpp"
 #include <type_traits>
 
 namespace GR_NS {
@@ -23,16 +24,49 @@ struct LaneStats {
         const int s = (r.flags & GR_FLAG_MASK) ? GR_STATUS_NO_STATUS : r.status;
         st[0] += (s == 0); st[1] += (s == 1); st[2] += (s == 2); st[3] += (s == 3);
     }
+    // Σ over the wave's 64 lanes of a count below 2^26, the same value in every lane: six 32-bit shuffles where the 64-bit
+    // sums took twelve each.  Every lane of the wave is here (flush() is called outside divergent code; a lane without a ray --
+    // the last wave of a 5000-ray set has 8 -- brings zeros).
+    static GR_DEV unsigned wave_sum(unsigned x)
+    {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += (unsigned)__shfl_xor((int)x, off, 64);
+        return (unsigned)__builtin_amdgcn_readfirstlane((int)x);
+    }
+    // The wave's nine sums go to ONE ROW of the context's partials block (gr_stats_fold.hpp); k_stats_fold adds the rows up into
+    // the caller's counters behind the trace kernel.  ONE_RAY: a lane has counted one ray at most (the one-ray-per-lane kernel),
+    // so rays, flagged and the four status counts are 0 or 1 per lane and their sums are read off ballots; the persistent
+    // kernel's lanes count many rays and sum them like the step counts.  A step count is any 32-bit number: its low 26 bits and
+    // the 6 bits above them are summed apart (64 x 2^26 = 2^32), the tops of acc and rej in one reduction (12 bits each after
+    // the sum).  rhs = 2 rays + 6 (accepted + rejected) is formed from the sums.
+    template <bool ONE_RAY>
     GR_DEV void flush(unsigned long long* out) const
     {
         if (!out) return;
-        unsigned long long v[N_STAT] = { rays, acc, rej, 2ull * rays + 6ull * ((unsigned long long)acc + rej), flagged, st[0], st[1], st[2], st[3] };
+        constexpr unsigned LO = (1u << 26) - 1u;
+        const unsigned top = wave_sum((acc >> 26) | ((rej >> 26) << 12));
+        const unsigned long long n_acc = (unsigned long long)wave_sum(acc & LO) + ((unsigned long long)(top & 0xfffu) << 26);
+        const unsigned long long n_rej = (unsigned long long)wave_sum(rej & LO) + ((unsigned long long)(top >> 12) << 26);
+        unsigned long long n_rays, n_flag, n_st[4];
+        if constexpr (ONE_RAY) {
+            n_rays = (unsigned long long)__popcll(__ballot(rays != 0));
+            n_flag = (unsigned long long)__popcll(__ballot(flagged != 0));
 #pragma unroll
-        for (int i = 0; i < N_STAT; ++i) {
-            unsigned long long x = v[i];
+            for (int i = 0; i < 4; ++i) n_st[i] = (unsigned long long)__popcll(__ballot(st[i] != 0));
+        } else {
+            // (a lane of the persistent kernel draws fewer than 2^26 of a launch's rays)
+            n_rays = wave_sum(rays);
+            n_flag = wave_sum(flagged);
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-            if ((threadIdx.x & 63) == 0 && x) atomicAdd(out + i, x);
+            for (int i = 0; i < 4; ++i) n_st[i] = wave_sum(st[i]);
+        }
+        const unsigned long long v[N_STAT] = { n_rays, n_acc, n_rej, 2ull * n_rays + 6ull * (n_acc + n_rej), n_flag, n_st[0], n_st[1], n_st[2], n_st[3] };
+        static_assert(N_STAT == gr_fold::kStatCols, "gr_stats_fold.hpp folds nine columns");
+        if ((threadIdx.x & 63) == 0) {
+            unsigned long long* row = out + (size_t)gr_fold::row_of(blockIdx.x) * gr_fold::kStatStride;
+#pragma unroll
+            for (int i = 0; i < N_STAT; ++i)
+                if (v[i]) atomicAdd(row + i, v[i]);
         }
     }
 };
@@ -267,19 +301,25 @@ __global__ void __launch_bounds__(256, GR_LANE_MIN_WAVES) k_trace_lane(const Par
 #endif
     if (gid < p.n) {
         Ray<Metric, DISC> ray;
-        const typename ColdSel<Metric>::type cs = cold_store_of<ColdSel<Metric>>(p);
+        // The cold lane storage is set up on the path that enters the step loop: a ray decided at its start has no use for it.
+        // (A tabulated metric's patch cache is laid out by the whole wave behind a barrier, cold_store_of: before any lane leaves.)
+        typename ColdSel<Metric>::type cs{};
+        if constexpr (ColdSel<Metric>::kTab) cs = cold_store_of<ColdSel<Metric>>(p);
         unsigned long long tab_t0 = 0;
         if constexpr (ColdSel<Metric>::kTab) tab_t0 = wall_clock64();
         // (a ray the start cull decides takes no step at all: Ray::init)
-        if (!ray.init(m, p, tile_swizzle(cold_of(p), gid)))
+        const bool decided = ray.init(m, p, tile_swizzle(cold_of(p), gid));
+        if (!decided) {
+            if constexpr (!ColdSel<Metric>::kTab) cs = cold_store_of<ColdSel<Metric>>(p);
             while (!ray.step(m, p, cs)) {}
+        }
         // In a one-wave workgroup finalize() lays the end-point record down in the LDS bytes other lanes of this wave use as
         // cold storage inside step() (lds_prologue): every lane must have LEFT the loop before any lane stores.  The
         // structured loop exit guarantees that today; the barrier states it, so that no later pass may sink finalize() into a
         // per-lane exit block.  It emits no instruction.
         __builtin_amdgcn_wave_barrier();
         GR_PARAMS_AFTER_LOOP(p, pl, zoff)
-        ray.finalize(m, pl, lds);
+        ray.finalize(m, pl, lds, decided);
         if constexpr (ColdSel<Metric>::kTab && LANES_PER_RAY_LOG2 == 0) {
             // A tabulated metric: what a tile costs is how long its wave lived, not how many steps its rays took -- a wave at
             // the shadow's edge, its lanes in a dozen different patches, spends 4x the time per step of one inside a single patch
@@ -317,7 +357,7 @@ __global__ void __launch_bounds__(256, GR_LANE_MIN_WAVES) k_trace_lane(const Par
 #endif
     points_epilogue(lds);
     lds_epilogue(p.cold, p.lds_bins, lds);
-    ls.flush(p.stats);
+    ls.template flush<true>(p.stats);
 }
 
 // ---- kernel 1: persistent grid with wave-ballot refill ----
@@ -361,7 +401,7 @@ __global__ void __launch_bounds__(256, GR_PERSISTENT_MIN_WAVES) k_trace_persiste
                 if (!active && mine < p.n) {
                     decided = ray.init(m, p, tile_swizzle(cold_of(p), mine));
                     if (decided) {
-                        ray.finalize(m, p, lds);
+                        ray.finalize(m, p, lds, true);
                         ls.add(ray);
                     } else
                         active = true;
@@ -379,7 +419,7 @@ __global__ void __launch_bounds__(256, GR_PERSISTENT_MIN_WAVES) k_trace_persiste
         }
     }
     lds_epilogue(p.cold, p.lds_bins, lds);
-    ls.flush(p.stats);
+    ls.template flush<false>(p.stats);
 }
 
 // ---- geodesics with every accepted step saved: one ray per lane, ray j writes rows of 9 doubles

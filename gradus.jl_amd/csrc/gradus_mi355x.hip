@@ -26,6 +26,7 @@
 
 #define GR_NS gr
 #include "gr_device.hpp"
+#include "gr_stats_fold.hpp"
 #include "gr_mesh_grid.hpp"
 #include "gr_lagbin.hpp"
 #include "gr_tfint.hpp"
@@ -116,6 +117,8 @@ struct gr_ctx {
     unsigned long long* d_queue = nullptr; // ring of work counters (one per in-flight launch)
     int queue_slots = 64, queue_next = 0;
     unsigned long long* d_stats = nullptr; // for host-buffer entry points
+    unsigned long long* d_stat_part = nullptr; // ring of partials blocks (gr_stats_fold.hpp), one per in-flight launch: all zero between launches
+    int stat_next = 0;
     double* d_disc_table = nullptr;        // device copy of a tabulated disc profile
     size_t disc_table_bytes = 0;
     double* d_mesh = nullptr;              // GR_DISC_MESH: the grid-sorted triangle table (gr_mesh_grid.hpp), kept while the
@@ -739,6 +742,19 @@ static int32_t sky_prepare(gr_ctx* ctx, Params& p, Cold& cold, hipStream_t strea
 // loop and is armed at the start, so each of the three turns it off as well; GRADUS_MI355X_ENTRY_CULL=0 (Params::entry_cull) turns
 // it off alone.  The defer cull (Ray::start_decided, Ray::step) is decided by the pass cull at the start and ends its rays in the
 // step loop: each of the three turns it off too, and GRADUS_MI355X_DEFER_CULL=0 (Params::defer_cull) turns it off alone.
+// The statistics of a launch: the trace kernel's waves have added their sums to the rows of one partials block (LaneStats::flush);
+// this adds the column sums to the caller's nine counters -- with atomics, as the waves themselves did before: launches on other
+// streams may be adding to the same counters -- and leaves the block zero for the launch that draws it next.  One workgroup.
+__global__ void __launch_bounds__(64) k_stats_fold(unsigned long long* part, unsigned long long* counters)
+{
+    const int t = (int)threadIdx.x;
+    unsigned long long s = 0;
+    if (t < gr_fold::kStatCols) s = gr_fold::column_sum(part, gr_fold::kStatRows, gr_fold::kStatStride, t);
+    __syncthreads();
+    if (t < gr_fold::kStatCols && s) atomicAdd(counters + t, s);
+    for (int i = t; i < gr_fold::kStatWords; i += 64) part[i] = 0;
+}
+
 static bool cull_switched_off(const char* name)
 {
     const char* sw = std::getenv(name);
@@ -835,8 +851,19 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
 #ifdef GR_WAVE_TIMELINE
     p.queue = g_debug_timeline;      // debug builds: 4 x u64 per wave of a one-ray-per-lane launch (gr_kernels.hpp)
 #endif
+    // statistics: the waves add to a partials block of the context, k_stats_fold adds that to the caller's counters
+    unsigned long long* const caller_stats = p.stats;
+    if (caller_stats) {
+        p.stats = ctx->d_stat_part + (size_t)ctx->stat_next * gr_fold::kStatWords;
+        ctx->stat_next = (ctx->stat_next + 1) % ctx->queue_slots;
+    }
     const hipError_t le = fn(knobs.kernel, knobs.block, knobs.n_cu, knobs.waves_per_simd, knobs.queue, &p, stream);
     if (le != hipSuccess) return fail(GR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(le));
+    if (caller_stats) {
+        hipLaunchKernelGGL(k_stats_fold, dim3(1), dim3(64), 0, stream, p.stats, caller_stats);
+        GR_HIP(hipGetLastError());
+        p.stats = caller_stats;
+    }
     if (stream == ctx->stream) GR_HIP(hipEventRecord(ctx->ev_k, stream));      // host variants: where the kernel ends
     if (p.disc_table || p.chart_table || cold.pf.n_plunge > 0 || p.cfg.metric_id == GR_METRIC_TABULATED || sky) {
         const int32_t trc = tables_release(ctx, stream);
@@ -971,6 +998,15 @@ int32_t gr_ctx_create(int32_t device, gr_ctx** out)
         if (hipMalloc((void**)&c->d_queue, sizeof(unsigned long long) * c->queue_slots) != hipSuccess) { rc = fail(GR_ERR_OUT_OF_MEMORY, "hipMalloc(queue) failed"); break; }
         if (hipMalloc((void**)&c->d_stats, sizeof(unsigned long long) * N_STAT) != hipSuccess) { rc = fail(GR_ERR_OUT_OF_MEMORY, "hipMalloc(stats) failed"); break; }
         if (hipMalloc((void**)&c->d_cold, sizeof(Cold) * c->queue_slots) != hipSuccess) { rc = fail(GR_ERR_OUT_OF_MEMORY, "hipMalloc(cold) failed"); break; }
+        {
+            const size_t part_bytes = sizeof(unsigned long long) * gr_fold::kStatWords * (size_t)c->queue_slots;
+            if (hipMalloc((void**)&c->d_stat_part, part_bytes) != hipSuccess) { rc = fail(GR_ERR_OUT_OF_MEMORY, "hipMalloc(stats partials) failed"); break; }
+            // (zero before any stream of the caller's can reach it: the wait is for that)
+            if (hipMemsetAsync(c->d_stat_part, 0, part_bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+                rc = fail(GR_ERR_HIP, "hipMemset(stats partials) failed");
+                break;
+            }
+        }
         if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess || hipEventCreate(&c->ev_k) != hipSuccess
             || hipEventCreateWithFlags(&c->ev_cost, hipEventDisableTiming) != hipSuccess
             || hipEventCreateWithFlags(&c->ev_tables, hipEventDisableTiming) != hipSuccess) { rc = fail(GR_ERR_HIP, "hipEventCreate failed"); break; }
@@ -997,6 +1033,7 @@ int32_t gr_ctx_destroy(gr_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->d_stats) (void)hipFree(c->d_stats);
+    if (c->d_stat_part) (void)hipFree(c->d_stat_part);
     if (c->d_cold) (void)hipFree(c->d_cold);
     if (c->d_disc_table) (void)hipFree(c->d_disc_table);
     if (c->d_mesh) (void)hipFree(c->d_mesh);

@@ -17,7 +17,12 @@ sys.path.insert(0, root)
 tmp = tempfile.mkdtemp()
 src = os.path.join(tmp, "a", "b", "csrc")          # the sources include "../../include/gradus_mi355x.h" relative to csrc
 os.makedirs(src); os.makedirs(os.path.join(tmp, "a", "include"))
-names = ["gr_device.hpp", "gr_kernels.hpp", "gr_tangent.hpp", "gr_mesh_grid.hpp", "gr_tabmetric.hpp", "gradus_mi355x.hip", "kernels_tu.hip", "metric_table.hip"]
+# every source and header of csrc, as the working tree or the revision has them
+if rev == "WORK":
+    names = sorted(f for f in os.listdir(os.path.join(root, "gradus.jl_amd", "csrc")) if f.endswith((".hpp", ".hip")))
+else:
+    listed = subprocess.check_output(["git", "-C", root, "ls-tree", "--name-only", rev, "gradus.jl_amd/csrc/"], text=True).split()
+    names = sorted(os.path.basename(f) for f in listed if f.endswith((".hpp", ".hip")))
 if rev == "WORK":
     for f in names:
         shutil.copy(os.path.join(root, "gradus.jl_amd", "csrc", f), src)
