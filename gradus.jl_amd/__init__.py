@@ -13,7 +13,8 @@ from .corona import (BeamedPointSource, BothHemispheres, CoronaGeodesics, DiscCo
                      SourceVelocities, DiscCoronaProfile, RingCoronaProfile, TimeDependentRadialDiscProfile,
                      emissivity_interp, emissivity_interp_limits,
                      RandomGenerator, WeierstrassSampler, coordtime_at, emissivity_at, emissivity_profile,
-                     energy_ratio, lorentz_factor, sky_angles_to_velocity, tetradframe_matrix, tracecorona)
+                     energy_ratio, lorentz_factor, sky_angles_to_velocity, tetradframe_matrix, tracecorona,
+                     DEFAULT_β_ANGLES, LongitudalArms, corona_arm_traces, corona_arms, disc_corona_profile, ring_corona_profile)
 from .distributed import gather_buffers, gather_image, gather_image_async, gather_points, shard_plan
 from .geometry import (CompositeGeometry, DatumPlane, EllipticalDisc, MeshAccretionGeometry, PrecessingDisc, ShakuraSunyaev, ThickDisc,
                        ThinDisc, WarpedThinDisc, bounding_box)

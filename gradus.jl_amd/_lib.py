@@ -289,6 +289,20 @@ class gr_tfprofile(C.Structure):
     ]
 
 
+class gr_ringset(C.Structure):
+    """The rings of gr_ring_rays / gr_ring_arms: per ring a frame of 28 doubles, the slices' angles β, a slice's base angles"""
+
+    _fields_ = [
+        ("n_rings", C.c_int64),
+        ("n_slices", C.c_int64),
+        ("n_base", C.c_int64),
+        ("extrema_iter", C.c_int64),
+        ("frames", C.c_void_p),
+        ("betas", C.c_void_p),
+        ("base_angles", C.c_void_p),
+    ]
+
+
 class gr_stats(C.Structure):
     _fields_ = [
         ("rays", C.c_int64),
@@ -373,6 +387,8 @@ EXPORTS = [
     "gr_tf_lineprofile",
     "gr_tf_lagtransfer",
     "gr_tf_lagtransfer_td",
+    "gr_ring_rays",
+    "gr_ring_arms",
     "gr_render_endpoints_multi",
     "gr_trace_endpoints_multi",
     "gr_rayset_endpoints_multi",
@@ -448,6 +464,8 @@ def load():
     L.gr_tf_lineprofile.argtypes = [vp, tsp, i64, tqp, vp, i64, vp]
     L.gr_tf_lagtransfer.argtypes = [vp, tsp, i64, tqp, vp, i64, vp, i64, vp]
     L.gr_tf_lagtransfer_td.argtypes = [vp, tsp, C.POINTER(gr_tfprofile), tqp, vp, i64, vp, i64, i64, i64, C.c_double, vp, vp]
+    L.gr_ring_rays.argtypes = [vp, cfgp, C.POINTER(gr_ringset), pfp, i64, vp, vp, vp, vp, stp]
+    L.gr_ring_arms.argtypes = [vp, cfgp, C.POINTER(gr_ringset), pfp, vp, vp, stp]
     ctxa = C.POINTER(vp)
     L.gr_render_endpoints_multi.argtypes = [ctxa, i32, cfgp, plp, i64, vp, vp]
     L.gr_trace_endpoints_multi.argtypes = [ctxa, i32, cfgp, vp, i64, vp, i64, vp, vp]

@@ -243,9 +243,10 @@ class RingCorona(AbstractCoronaModel):
     """RingCorona(vf, r, h): an infinitely thin ring of radius r at height h (extended.jl:55-82).  A
     representative point of the ring is returned; axis symmetry does the rest.  Its emissivity goes
     through the generic Monte-Carlo route (`emissivity_profile(..., sampler=...)`).  Its time-dependent emissivity is a
-    `RingCoronaProfile` (two arms of per-slice curves, built from arrays), which `integrate_lagtransfer` integrates on the
-    host and, with `ensemble=`, on the device (ring.jl:857-950); the reference's producer of the arms from traced slices
-    (ring.jl:1-485) is not restated."""
+    `RingCoronaProfile` (two arms of per-slice curves), which `integrate_lagtransfer` integrates on the host and, with
+    `ensemble=`, on the device (ring.jl:857-950); `ring_corona_profile` (or `emissivity_profile(..., time_dependent=True)`)
+    builds it from the model: the arms of every slice of the ring's sky are traced and searched on the device (`corona_arms`,
+    ring.jl:1-485)."""
 
     fixed_position = True
 
@@ -268,8 +269,9 @@ class DiscCorona(AbstractCoronaModel):
     """DiscCorona(vf, r, h): a disc of radius r at height h above the accretion disc (extended.jl:165-181); every sample leaves
     from a point of its own, x = rand() r along the disc (sample_position_velocity, extended.jl:176-183).  Its emissivity goes
     through the Monte-Carlo route (`emissivity_profile(..., sampler=...)`: tracecorona + RadialDiscProfile); the reference's
-    concentric-ring profile is `DiscCoronaProfile` (rings of `RingCoronaProfile`, built from arrays), which `integrate_lagtransfer`
-    integrates on the host and, with `ensemble=`, on the device; tracing the rings' arms (extended.jl:185-200) is not restated.
+    concentric-ring profile is `DiscCoronaProfile` (rings of `RingCoronaProfile`), which `integrate_lagtransfer` integrates on
+    the host and, with `ensemble=`, on the device; `disc_corona_profile` (or `emissivity_profile(..., time_dependent=True)`) builds
+    it from the model, the arms of all its rings traced in one device call (extended.jl:185-200).
     `seed`: the generator behind rand()."""
 
     def __init__(self, *args, r=5.0, h=5.0, vf=SourceVelocities.co_rotating, seed=None):
@@ -949,12 +951,14 @@ def device_radial_profile(m, d, model, spectrum=None, *, λmax=10_000.0, sampler
     return (prof, st) if stats else prof
 
 
-def _point_source_emissivity(m, spec, source_velocity, r, δs, points, disc_velocity):
-    """lamp-post.jl:118-156 on sorted arrays."""
+def _point_source_emissivity(m, spec, source_velocity, r, δs, points, disc_velocity, gs=None):
+    """lamp-post.jl:118-156 on sorted arrays.  `gs`: the energy ratios, where the caller has them already (rows traced on the
+    device carry g; `points` then needs its "x" field only)."""
     v_disc = disc_velocity(points["x"])
     n = r.size
-    vsrc = np.tile(np.asarray(source_velocity, dtype=np.float64), (n, 1))
-    gs = energy_ratio(m, points, vsrc, v_disc)
+    if gs is None:
+        vsrc = np.tile(np.asarray(source_velocity, dtype=np.float64), (n, 1))
+        gs = energy_ratio(m, points, vsrc, v_disc)
     γ = lorentz_factor(m, points["x"], v_disc)
     k = np.arange(n)
     i2 = np.where(k == 0, 1, np.where(k != n - 1, k + 1, k - 1))
@@ -982,9 +986,18 @@ def polar_angle_velocities(m, x, v, δs, ϕ=0.0):
 
 
 def emissivity_profile(m, d, model, spectrum=None, *, λmax=10_000.0, δmin=0.01, δmax=179.99, sampler=None,
-                       n_samples=1000, grid=None, N=100, callback="default", ensemble=None, **kwargs):
+                       n_samples=1000, grid=None, N=100, callback="default", ensemble=None, time_dependent=False, **kwargs):
     """emissivity_profile(m, d, model, [spectrum]; n_samples, sampler, N, grid) emissivity.jl:118-168;
-    point sources without an explicit sampler take the angular method of lamp-post.jl:68-115,158-166."""
+    point sources without an explicit sampler take the angular method of lamp-post.jl:68-115,158-166.
+    `time_dependent=True` is the reference's EmissivityProfileSetup{true}: a RingCorona gives a RingCoronaProfile
+    (`ring_corona_profile`), a DiscCorona a DiscCoronaProfile (`disc_corona_profile`); their keywords (βs, extrema_iter, h, n_rings,
+    chart, route, tracer) pass through and λmax is theirs (10⁶, ring.jl:266), not this function's."""
+    if time_dependent:
+        if isinstance(model, RingCorona):
+            return ring_corona_profile(m, d, model, spectrum=spectrum, n_samples=n_samples, ensemble=ensemble, **kwargs)
+        if isinstance(model, DiscCorona):
+            return disc_corona_profile(m, d, model, spectrum=spectrum, n_samples=n_samples, ensemble=ensemble, **kwargs)
+        raise NotImplementedError(f"no time-dependent emissivity profile for {type(model).__name__}")
     spectrum = PowerLawSpectrum(2.0) if spectrum is None else spectrum
     if callback == "default":
         callback = domain_upper_hemisphere()
@@ -1002,3 +1015,468 @@ def emissivity_profile(m, d, model, spectrum=None, *, λmax=10_000.0, δmin=0.01
     cg = tracecorona(m, d, model, sampler=sampler, λmax=λmax, n_samples=n_samples, ensemble=ensemble)
     return build_radial_profile(m, spectrum, cg.geodesic_points, cg.source_velocity, grid=grid, N=N,
                                 disc_velocity=disc_velocity)
+
+
+# ------------------------------------------------------------------------------------------
+# the longitudinal arms of ring coronae (src/corona/models/ring.jl:1-485, src/corona/models/extended.jl:89-200)
+# ------------------------------------------------------------------------------------------
+INVPHI = (math.sqrt(5.0) - 1.0) / 2.0          # ring.jl:1
+_HIT = int(StatusCodes.IntersectedWithGeometry)
+
+
+def DEFAULT_β_ANGLES(n=100):
+    """extended.jl:53"""
+    return np.sort(np.linspace(0.0, math.pi - math.pi / n, n))
+
+
+@dataclass
+class LongitudalArms:
+    """extended.jl:89-97: what one β slice of a ring's sky lights on the disc, as two arms (r ascending, t, ε on them)"""
+
+    β: float
+    left_r: np.ndarray
+    left_t: np.ndarray
+    left_ε: np.ndarray
+    right_r: np.ndarray
+    right_t: np.ndarray
+    right_ε: np.ndarray
+
+
+def ring_base_angles(n_samples=1000, extrema_iter=80, h=1e-7):
+    """The local angles of a slice's base rays (_RingCoronaCache, ring.jl:74-96): N = n_samples - 2 extrema_iter of them, ascending --
+    range(h, π - h, N / 2) and the same shifted by π.  The reference's two errors for too few samples and an odd N."""
+    N = int(n_samples) - 2 * int(extrema_iter)
+    if N <= 0:
+        raise ValueError(f"Too few samples for selected method. Pass `n_samples` of more than {2 * int(extrema_iter)}")
+    if N % 2 != 0:
+        raise ValueError(f"`n_samples` must be an even number for this method (given {N})")
+    left = np.linspace(h, math.pi - h, N // 2)
+    return np.sort(np.concatenate([left, np.mod(left + math.pi, TWO_PI)]))
+
+
+def rodrigues_rotate(k, v, θ):
+    """emissivity.jl:220"""
+    return v * np.cos(θ) + np.cross(k, v) * np.sin(θ) + k * np.dot(k, v) * (1.0 - np.cos(θ))
+
+
+def ring_sky_angles(x, β, θ):
+    """rotatorfunctor (ring.jl:105-118) up to the sky angles: (th, ph) of the ray at local angle θ in the slice β of the sky of x"""
+    axis = x[2]
+    k = _cart_local_direction(axis, 0.0)
+    θ = np.atleast_1d(np.asarray(θ, dtype=np.float64))
+    th, ph = np.zeros(θ.size), np.zeros(θ.size)
+    for i, t in enumerate(θ):
+        b = rodrigues_rotate(k, _cart_local_direction(t + axis, 0.0), β)
+        ph[i] = np.arctan2(b[1], b[0])
+        th[i] = np.arctan2(np.sqrt(b[1] ** 2 + b[0] ** 2), b[2])
+    return th, ph
+
+
+def ring_velocities(m, x, v_source, β, θ):
+    """rotatorfunctor (ring.jl:105-118) on the host: the unconstrained velocities (n, 4) of the rays at local angles θ"""
+    th, ph = ring_sky_angles(x, β, θ)
+    return sky_angles_to_velocity(m, x, v_source, th, ph)
+
+
+def ring_frames(m, models):
+    """Per ring the 28 doubles gr_ring_rays / gr_ring_arms form its rays from -- the layout of a row of gr_rayset.sky_rows: position,
+    tetrad times Jacobian, the source velocity with its index lowered, (g_tt, 0, 0, g_tϕ).  The tetrad is host work: a ring has one
+    position.  Returns (frames (n, 28), positions (n, 4), source velocities (n, 4))."""
+    frames, xs, vs = np.zeros((len(models), 28)), np.zeros((len(models), 4)), np.zeros((len(models), 4))
+    for k, model in enumerate(models):
+        x, v = model.sample_position_velocity(m)
+        x, v = np.array(x, dtype=np.float64), np.asarray(v, dtype=np.float64)
+        B = np.eye(4)
+        B[1:, 1:] = _cart_to_spher_jacobian(x[2], x[3])
+        g = _components_at(m, x)
+        frames[k, 0:4] = x
+        frames[k, 4:20] = (tetradframe_matrix(m, x, v) @ B).ravel()
+        frames[k, 20:24] = (g[0] * v[0] + g[4] * v[3], g[1] * v[1], g[2] * v[2], g[3] * v[3] + g[4] * v[0])
+        frames[k, 24:28] = (g[0], 0.0, 0.0, g[4])
+        xs[k], vs[k] = x, v
+    return frames, xs, vs
+
+
+# ---- bracket and golden-section update: gr_ringarm.hpp in numpy, bit for bit (sums, differences, one product) ----
+def _better(target, a, b):
+    return a < b if target == 0 else a > b
+
+
+def determine_bracket(rows, angles, target):
+    """_determine_bracket (ring.jl:131-166) on a slice's base rows (g, ρ, t, status): (a - 2δ, b + 2δ, best_estimate), or None when
+    no row met the geometry.  The strict comparison keeps the FIRST extreme row, whose two neighbour-is-a-miss widenings count."""
+    N = rows.shape[0]
+    hit = rows[:, 3].astype(np.int64) == _HIT
+    if not hit.any():
+        return None
+    ρ = np.where(hit, rows[:, 1], np.inf if target == 0 else -np.inf)
+    i = int(np.argmin(ρ) if target == 0 else np.argmax(ρ))
+    a = b = float(angles[i])
+    if i < N - 1 and not hit[i + 1]:
+        b = float(angles[i + 1])
+    if i > 0 and not hit[i - 1]:
+        a = float(angles[i - 1])
+    δ = math.pi / min(N, 32)
+    return a - 2.0 * δ, b + 2.0 * δ, float(rows[i, 1])
+
+
+class GoldenSearch:
+    """The state of one _golden_bracket! (ring.jl:172-237)"""
+
+    __slots__ = ("a", "b", "best", "n", "iters", "too_many", "done", "target")
+
+    def __init__(self, a, b, best, target):
+        self.a, self.b, self.best, self.target = a, b, best, target
+        self.n = self.iters = 0
+        self.too_many = self.done = False
+
+    def probes(self):
+        return self.b - (self.b - self.a) * INVPHI, self.a + (self.b - self.a) * INVPHI
+
+    def update(self, extrema_iter, c_status, c_ρ, d_status, d_ρ):
+        """one iteration given the probes' outcomes: 0 nothing kept, 1 the probe at c, 2 the probe at d.  best is never updated;
+        n also counts every iteration once iters has passed extrema_iter"""
+        c, d = self.probes()
+        c_value = c_ρ if c_status == _HIT else self.best
+        d_value = d_ρ if d_status == _HIT else self.best
+        append = 0
+        if _better(self.target, c_value, d_value):
+            if _better(self.target, c_value, self.best):
+                self.n += 1
+                append = 1
+            elif self.too_many:
+                self.n += 1
+            self.b = d
+        else:
+            if _better(self.target, d_value, self.best):
+                self.n += 1
+                append = 2
+            elif self.too_many:
+                self.n += 1
+            self.a = c
+        self.iters += 1
+        if not self.too_many and self.iters > extrema_iter:
+            self.too_many = True
+        self.done = not (self.n < extrema_iter)
+        return append
+
+
+class NoHitError(ValueError):
+    pass
+
+
+def _no_hit_error(missing, n_slices):
+    names = ", ".join(f"(ring {s // n_slices}, slice {s % n_slices})" for s in missing[:8])
+    return NoHitError(f"no base ray met the disc in {names}{' ...' if len(missing) > 8 else ''}: no extremum to search for "
+                      "(the reference fails in _determine_bracket, ring.jl:163)")
+
+
+def lockstep_arm_traces(tracer, n_rings, n_slices, base_angles, extrema_iter, searches_out=None):
+    """_ring_arm_traces! (ring.jl:250-288) for every slice of every ring, the searches advancing together: every row comes from
+    `tracer(ring, slice, angles) -> rows (n, 4) = (g, ρ, t, status)`, called once for the base rays and once per iteration with
+    the two probes of every live search.  Returns what gr_ring_arms returns: rows (n_rings, n_slices, N + 2 extrema_iter, 5) =
+    (θ as probed, g, ρ, t, status) and counts (n_rings, n_slices, 3) = (N, kept by the minima search, kept by the maxima search),
+    (N, -1, -1) for a slice without a hit.  `searches_out`: a dict that receives the final GoldenSearch of search 2 (ring n_slices +
+    slice) + target."""
+    base = np.ascontiguousarray(base_angles, dtype=np.float64)
+    S, NB, E = n_rings * n_slices, base.size, int(extrema_iter)
+    ring_of, slice_of = np.arange(S) // n_slices, np.arange(S) % n_slices
+    rows0 = np.asarray(tracer(np.repeat(ring_of, NB), np.repeat(slice_of, NB), np.tile(base, S))).reshape(S, NB, 4)
+    rows = np.zeros((S, NB + 2 * E, 5))
+    rows[:, :NB, 0], rows[:, :NB, 1:] = base, rows0
+    counts = np.zeros((S, 3), dtype=np.int64)
+    counts[:, 0] = NB
+    searches, kept = {}, {}
+    for s in range(S):
+        for target in (0, 1):
+            br = determine_bracket(rows0[s], base, target)
+            if br is None:
+                counts[s, 1:] = -1
+            else:
+                searches[2 * s + target], kept[2 * s + target] = GoldenSearch(*br, target), []
+    for _ in range(2 * E + 1):
+        live = [q for q, sr in searches.items() if not sr.done]
+        if not live:
+            break
+        angles = np.array([θ for q in live for θ in searches[q].probes()])
+        sl = np.repeat(np.array(live) // 2, 2)
+        pr = np.asarray(tracer(ring_of[sl], slice_of[sl], angles)).reshape(len(live), 2, 4)
+        for k, q in enumerate(live):
+            append = searches[q].update(E, int(pr[k, 0, 3]), float(pr[k, 0, 1]), int(pr[k, 1, 3]), float(pr[k, 1, 1]))
+            if append and len(kept[q]) < E:
+                kept[q].append(np.concatenate([[angles[2 * k + append - 1]], pr[k, append - 1]]))
+    if searches_out is not None:
+        searches_out.update(searches)
+    for q, run in kept.items():
+        s, target = q // 2, q % 2
+        at = NB + (counts[s, 1] if target else 0)
+        counts[s, 1 + target] = len(run)
+        if run:
+            rows[s, at:at + len(run)] = np.array(run)
+    return rows.reshape(n_rings, n_slices, NB + 2 * E, 5), counts.reshape(n_rings, n_slices, 3)
+
+
+class RingTracer:
+    """`tracer(ring, slice, angles) -> rows` on the device (gr_ring_rays): the rays of (ring, slice, local angle) triples formed and
+    traced by the kernels gr_ring_arms uses.  `launches` and `rays` count what went through it."""
+
+    def __init__(self, m, d, models, βs, *, λmax=1_000_000.0, chart=None, ensemble=None, **solver_args):
+        from . import _lib
+        from .pointfunctions import GR_PF_REDSHIFT, PointFunction
+        from .rendering import abi_pointfunction
+        from .tracing import chart_for_metric, tracing_configuration
+
+        self.m = m
+        self.frames, self.xs, self.v_src = ring_frames(m, models)
+        self.βs = np.ascontiguousarray(βs, dtype=np.float64)
+        chart = chart_for_metric(m, 1_000_000.0) if chart is None else chart
+        x_far = self.xs[int(np.argmax(self.xs[:, 1]))]          # (the outermost ring: the chart's range checks)
+        self.config = tracing_configuration(m, x_far, np.zeros((1, 4)), d, (0.0, λmax), callback=domain_upper_hemisphere(), chart=chart,
+                                            ensemble=ensemble, **solver_args)
+        self.ensemble = self.config.ensemble
+        if getattr(m, "M", None) == 0.0:
+            # flat space: no orbit, no ISCO, no plunge -- the rows' ρ and t are straight lines' (their g is not defined)
+            r_isco, self.plunging, self.disc_velocity = float(np.finfo(np.float64).tiny), None, None
+        else:
+            r_isco, self.plunging = m.isco(), _plunging_table(m, self.ensemble)
+            self.disc_velocity = keplerian_velocity_projector(m, plunging=self.plunging, ensemble=self.ensemble)
+        self.pf, self._keep_pf = abi_pointfunction(PointFunction(None, device_pf=GR_PF_REDSHIFT, extra={"r_isco": r_isco, "plunge": self.plunging}))
+        self.cfg = self.config.abi_config()
+        self.launches = self.rays = 0
+        self._lib = _lib
+
+    def ringset(self, base_angles=None, extrema_iter=0):
+        rs = self._lib.gr_ringset()
+        rs.n_rings, rs.n_slices = self.frames.shape[0], self.βs.size
+        rs.frames, rs.betas = self.frames.ctypes.data, self.βs.ctypes.data
+        if base_angles is not None:
+            rs.n_base, rs.extrema_iter, rs.base_angles = base_angles.size, int(extrema_iter), base_angles.ctypes.data
+        return rs
+
+    def __call__(self, ring, slice_, angles, velocities=False, stats=None):
+        import ctypes as C
+
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        pairs = np.ascontiguousarray(np.stack([np.asarray(ring), np.asarray(slice_)], axis=1), dtype=np.int64)
+        rows, v = np.zeros((angles.size, 4)), (np.zeros((angles.size, 4)) if velocities else None)
+        rs = self.ringset()
+        self._lib.check(self._lib.load().gr_ring_rays(self.ensemble.ctx.handle, C.byref(self.cfg), C.byref(rs), C.byref(self.pf), angles.size,
+                                                     pairs.ctypes.data, angles.ctypes.data, rows.ctypes.data, None if v is None else v.ctypes.data,
+                                                     None if stats is None else C.byref(stats)))
+        self.launches += 1
+        self.rays += angles.size
+        return (rows, v) if velocities else rows
+
+    def arms(self, base_angles, extrema_iter, stats=None):
+        """gr_ring_arms: the whole producer in one call -> (rows, counts)"""
+        import ctypes as C
+
+        base = np.ascontiguousarray(base_angles, dtype=np.float64)
+        R, S, W = self.frames.shape[0], self.βs.size, base.size + 2 * int(extrema_iter)
+        rows, counts = np.zeros((R, S, W, 5)), np.zeros((R, S, 3), dtype=np.int64)
+        rs = self.ringset(base, extrema_iter)
+        self._lib.check(self._lib.load().gr_ring_arms(self.ensemble.ctx.handle, C.byref(self.cfg), C.byref(rs), C.byref(self.pf), rows.ctypes.data,
+                                                     counts.ctypes.data, None if stats is None else C.byref(stats)))
+        return rows, counts
+
+
+def _arm_traces(m, d, models, βs, *, n_samples=1000, extrema_iter=80, h=1e-7, λmax=1_000_000.0, chart=None, ensemble=None,
+                route="device", tracer=None, stats=None):
+    βs = DEFAULT_β_ANGLES() if βs is None else np.ascontiguousarray(βs, dtype=np.float64)
+    base = ring_base_angles(n_samples, extrema_iter, h)
+    if route not in ("device", "lockstep"):
+        raise ValueError(f"route {route!r}: \"device\" or \"lockstep\"")
+    if tracer is None:
+        from .geometry import ThinDisc
+
+        if type(d) is not ThinDisc:
+            raise NotImplementedError("the arms of a ring corona are traced onto a ThinDisc (gr_ring_arms: GR_ERR_UNSUPPORTED otherwise)")
+        tracer = RingTracer(m, d, models, βs, λmax=λmax, chart=chart, ensemble=ensemble)
+    elif route == "device":
+        raise ValueError("a tracer drives the lock-step route: pass route=\"lockstep\"")
+    if route == "device":
+        rows, counts = tracer.arms(base, extrema_iter, stats=stats)
+    else:
+        rows, counts = lockstep_arm_traces(tracer, len(models), βs.size, base, extrema_iter)
+    missing = np.flatnonzero(counts.reshape(-1, 3)[:, 1] < 0)
+    if missing.size:
+        raise _no_hit_error(missing.tolist(), βs.size)
+    return rows, counts, base, tracer
+
+
+def corona_arm_traces(m, d, models, βs=None, **kwargs):
+    """The traced cache of every β slice of every ring of `models` (RingCorona each): (rows, counts, base angles) as gr_ring_arms lays
+    them out.  route "device": one gr_ring_arms call; "lockstep": the same bracket / golden-section logic in numpy, every row through
+    `tracer(ring, slice, angles) -> rows` -- gr_ring_rays unless given.  A slice none of whose base rays met the disc: ValueError.
+    Keywords: n_samples, extrema_iter, h, λmax, chart, ensemble, route, tracer, stats (a gr_stats to fill, device route)."""
+    return _arm_traces(m, d, models, βs, **kwargs)[:3]
+
+
+# ---- a slice's cache -> its two arms (ring.jl:290-438), on the host ----
+def _split_branches_further(inds, rs, cutoff_r=1e3, delta=0.01, min_length=3):
+    """ring.jl:304-351.  `inds`: 1-based indices into rs, as in the reference (so that the index arithmetic reads the same)."""
+    N = len(inds)
+    if N == 0:
+        raise ValueError("an arm without a point (findmin of an empty collection, ring.jl:306)")
+    vals = [rs[i - 1] for i in inds]
+    first_i = int(np.argmin(vals)) + 1                 # findmin: the first minimum
+    prev = vals[first_i - 1]
+    splits = [1, first_i]
+    increasing = True
+    for j in range(N):
+        k = (j + first_i) % N + 1
+        r = rs[inds[k - 1] - 1]
+        if r > cutoff_r:
+            increasing = False
+            prev = r
+            continue
+        if increasing and r < prev - delta:
+            increasing = False
+            splits.append(k - 1 if k > 1 else N)
+        elif not increasing and r > prev + delta:
+            increasing = True
+            splits.append(k - 1 if k > 1 else N)
+        prev = r
+    splits.sort()
+    if len(splits) > 2:
+        # merge slices that are smaller than the minimum length together
+        slices = []
+        i1 = splits[0]
+        for i2 in splits[1:]:
+            if i2 - i1 >= min_length:
+                if N - i2 <= min_length:
+                    i2 = N
+                slices.append(list(inds[i1 - 1:i2]))
+                i1 = i2
+        if i1 < N:
+            slices.append(list(inds[i1 - 1:]))
+        return slices
+    return [list(inds)]
+
+
+def _split_arms_indices(angles, ρs):
+    """ring.jl:353-386: 1-based index lists, each in ascending ρ (canonical_orders!: a stable sort by ρ); vcat(l1, l2)."""
+    ρs = np.asarray(ρs, dtype=np.float64)
+    n = ρs.size
+    start = int(np.flatnonzero(~np.isnan(ρs))[0]) + 1
+    i_min = i_max = start
+    r_min = r_max = ρs[start - 1]
+    for i in range(1, n + 1):
+        r = ρs[i - 1]
+        if r < r_min:
+            i_min, r_min = i, r
+        if r > r_max:
+            i_max, r_max = i, r
+    lo, hi = min(i_min, i_max), max(i_min, i_max)
+    r1 = list(range(hi + 1, n + 1)) + list(range(1, lo))
+    r2 = list(range(lo + 1, hi + 1))
+    canonical = lambda lists: [sorted(I, key=lambda i: ρs[i - 1]) for I in lists]
+    return canonical(_split_branches_further(r1, ρs)) + canonical(_split_branches_further(r2, ρs))
+
+
+def _process_ring_traces(m, spectrum, v_source, disc_velocity, g, ρ, t, δs, where=""):
+    """extended.jl:145-154 through _point_source_emissivity: (r, t, ε) of one arm, r ascending, ε = abs.(ε) (:153).
+    Rows of bit-equal ρ (ring_arm has dropped the re-probed angles; what is left would be two angles with one ρ) keep the first:
+    every Δr of _point_source_emissivity (lamp-post.jl:146-149) stays positive."""
+    J = np.argsort(ρ, kind="stable")
+    g, ρ, t, δs = g[J], ρ[J], t[J], δs[J]
+    first = np.concatenate([[True], np.diff(ρ) != 0.0])
+    g, ρ, t, δs = g[first], ρ[first], t[first], δs[first]
+    if ρ.size < 2:
+        raise ValueError(f"{where}an arm of the slice has fewer than 2 points")
+    points = np.zeros(ρ.size, dtype=[("x", np.float64, (4,))])
+    points["x"][:, 0], points["x"][:, 1], points["x"][:, 2] = t, ρ, math.pi / 2
+    ε, _ = _point_source_emissivity(m, spectrum, v_source, ρ, δs, points, disc_velocity, gs=g)
+    return ρ, t, np.abs(ε)
+
+
+def ring_arm(m, spectrum, v_source, disc_velocity, β, rows, where=""):
+    """_ring_arm! behind its traces (ring.jl:397-437): the filled prefix of a slice's cache (θ, g, ρ, t, status) -> LongitudalArms.
+    The rows carry ρ = r |sin θ| of the hit, not its (r, θ): proper area, disc velocity and Lorentz factor are evaluated at
+    (ρ, π/2) -- the hit itself up to the ThinDisc's gtol cone."""
+    rows = rows[rows[:, 4].astype(np.int64) == _HIT]
+    angles = np.mod(rows[:, 0], TWO_PI)
+    I = np.argsort(angles, kind="stable")
+    rows, angles = rows[I], angles[I]
+    # One departure from the reference.  A golden-section iteration probes again, to rounding, the angle the iteration before it
+    # kept (its c is the earlier d, ring.jl:207-208); both beat best_estimate and both join the cache, so the sorted cache holds
+    # runs of rows at one angle with ρ equal to the last bit or nearly.  The reference splits and weighs them as they are: a run
+    # next to the minimum becomes an "arm" of one radius that displaces a real one (the first-two rule below), and three equal ρ
+    # in a row give Δr = 0 and ε = 0 / 0 (lamp-post.jl:146-149).  Here a row within 1e-12 of the angle before it is the same sample.
+    fresh = np.concatenate([[True], np.diff(angles) > 1e-12])
+    rows, angles = rows[fresh], angles[fresh]
+    ρs = rows[:, 2]
+    if ρs.size < 2:
+        raise ValueError(f"{where}fewer than 2 rays of the slice met the disc")
+    lists = _split_arms_indices(angles, ρs)
+    if len(lists) < 2:
+        raise ValueError(f"{where}the slice has one arm only")
+    arms = []
+    for I1 in lists[:2]:          # `r1, r2 = _split_arms_indices(...)` (ring.jl:415): the first two lists, however many there are
+        if len(I1) < 2:
+            raise ValueError(f"{where}an arm of the slice has fewer than 2 points")
+        sel = np.array(I1) - 1
+        arms.append(_process_ring_traces(m, spectrum, v_source, disc_velocity, rows[sel, 1], ρs[sel], rows[sel, 3], angles[sel], where))
+    (lr, lt, le), (rr, rt, re_) = arms
+    return LongitudalArms(float(β), lr, lt, le, rr, rt, re_)
+
+
+def _arms_of_models(m, d, models, βs, *, spectrum=None, disc_velocity=None, ensemble=None, **kw):
+    """the LongitudalArms of every slice of every ring: [ring][slice]"""
+    βs = DEFAULT_β_ANGLES() if βs is None else np.ascontiguousarray(βs, dtype=np.float64)
+    spectrum = PowerLawSpectrum(2.0) if spectrum is None else spectrum
+    rows, counts, _, tracer = _arm_traces(m, d, models, βs, ensemble=ensemble, **kw)
+    if isinstance(tracer, RingTracer):
+        v_srcs = tracer.v_src
+        disc_velocity = tracer.disc_velocity if disc_velocity is None else disc_velocity
+    else:
+        v_srcs = ring_frames(m, models)[2]
+        disc_velocity = keplerian_velocity_projector(m, ensemble=ensemble) if disc_velocity is None else disc_velocity
+    out = []
+    for i in range(len(models)):
+        arms = []
+        for j, β in enumerate(βs):
+            filled = int(counts[i, j].sum())
+            arms.append(ring_arm(m, spectrum, v_srcs[i], disc_velocity, β, rows[i, j, :filled], where=f"ring {i}, slice {j}: "))
+        out.append(arms)
+    return out
+
+
+def corona_arms(m, d, model, βs=None, *, n_samples=1000, extrema_iter=80, h=1e-7, λmax=1_000_000.0, chart=None, spectrum=None,
+                ensemble=None, route="device", tracer=None, disc_velocity=None):
+    """corona_arms(setup, m, d, model::RingCorona, βs) (ring.jl:456-484): the LongitudalArms of every β slice of the ring's sky
+    (βs: DEFAULT_β_ANGLES(100); callback domain_upper_hemisphere(); chart: chart_for_metric(m, 1e6)).  Per slice N = n_samples -
+    2 extrema_iter evenly spaced rays and two golden-section searches for the extrema of ρ.  route "device": gr_ring_arms, all
+    slices' searches in lock-step on the device; "lockstep": the same logic in numpy over `tracer(ring, slice, angles) -> rows
+    (g, ρ, t, status)` -- gr_ring_rays unless given.  `disc_velocity`: the disc's velocity projector (default: Keplerian with the
+    traced plunging table)."""
+    return _arms_of_models(m, d, [model], βs, spectrum=spectrum, disc_velocity=disc_velocity, tracer=tracer, ensemble=ensemble,
+                           n_samples=n_samples, extrema_iter=extrema_iter, h=h, λmax=λmax, chart=chart, route=route)[0]
+
+
+def _make_time_dependent_radial_emissivity(arms):
+    """extended.jl:99-130 (weights of zeros, as there)"""
+    w = np.zeros(len(arms))
+    left = TimeDependentRadialDiscProfile(w, [a.left_r for a in arms], [a.left_t for a in arms], [a.left_ε for a in arms])
+    right = TimeDependentRadialDiscProfile(w, [a.right_r for a in arms], [a.right_t for a in arms], [a.right_ε for a in arms])
+    return RingCoronaProfile(left, right)
+
+
+def ring_corona_profile(m, d, model, βs=None, **kwargs):
+    """emissivity_profile(setup{true}, m, d, model::RingCorona; βs) (extended.jl:133-143) -> RingCoronaProfile; keywords: corona_arms'"""
+    if not isinstance(model, RingCorona):
+        raise TypeError("ring_corona_profile takes a RingCorona")
+    return _make_time_dependent_radial_emissivity(corona_arms(m, d, model, βs, **kwargs))
+
+
+def disc_corona_profile(m, d, model, βs=None, *, n_rings=10, n_samples=1000, extrema_iter=80, h=1e-7, λmax=1_000_000.0, chart=None,
+                        spectrum=None, ensemble=None, route="device", tracer=None, disc_velocity=None):
+    """emissivity_profile(setup{true}, m, d, model::DiscCorona; n_rings) (extended.jl:187-200) -> DiscCoronaProfile over the rings
+    RingCorona(model.vf, r, model.h), r in linspace(1e-2, model.r, n_rings) -- all of them in ONE gr_ring_arms call."""
+    if not isinstance(model, DiscCorona):
+        raise TypeError("disc_corona_profile takes a DiscCorona")
+    radii = np.linspace(1e-2, model.r, int(n_rings))
+    models = [RingCorona(model.vf, float(r), model.h) for r in radii]
+    per_ring = _arms_of_models(m, d, models, βs, spectrum=spectrum, disc_velocity=disc_velocity, tracer=tracer, ensemble=ensemble,
+                               n_samples=n_samples, extrema_iter=extrema_iter, h=h, λmax=λmax, chart=chart, route=route)
+    return DiscCoronaProfile(radii, [_make_time_dependent_radial_emissivity(arms) for arms in per_ring])

@@ -31,6 +31,7 @@
 #include "gr_lagbin.hpp"
 #include "gr_tfint.hpp"
 #include "gr_tftd.hpp"
+#include "gr_ringarm.hpp"
 
 using namespace gr;
 
@@ -3522,6 +3523,298 @@ int32_t gr_tf_lagtransfer_td(gr_ctx* ctx, const gr_tfset* set, const gr_tfprofil
     GR_HIP(hipMemcpyAsync(acc.data(), d_acc, 8 * acc.size(), hipMemcpyDeviceToHost, ctx->stream));
     GR_HIP(hipStreamSynchronize(ctx->stream));
     for (size_t c = 0; c < cells; ++c) out[c] = gr_lag::corona_sum(acc[c], acc[cells + c], grd);
+    return GR_OK;
+}
+
+// ---- the longitudinal arms of ring coronae (corona_arms, src/corona/models/ring.jl:1-485): gr_ring_rays / gr_ring_arms ----
+// The arithmetic is gr_ringarm.hpp's; the trace is launch_trace's ray-summary launch on (x, v) arrays, as a sky source's.
+extern "C++" {
+namespace {
+struct RingDev {      // a staged gr_ringset
+    const double *frames, *betas, *base;
+    int32_t n_rings, n_slices, n_base, extrema_iter;
+};
+// ray j -> x, v and the factor of its g.  With a list: (ring, slice) = ring_slice[j], θ = angles[j]; without: the base rays,
+// ray j = (ring * n_slices + slice) * n_base + i at base angle i
+__global__ void __launch_bounds__(256) k_ring_rays(const RingDev r, int64_t n, const int64_t* ring_slice, const double* angles,
+                                                   double* x, double* v, double* f)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    int ring, slice;
+    double th;
+    if (ring_slice) {
+        ring = (int)ring_slice[2 * j];
+        slice = (int)ring_slice[2 * j + 1];
+        th = angles[j];
+    } else {
+        const int64_t s = j / r.n_base;
+        ring = (int)(s / r.n_slices);
+        slice = (int)(s % r.n_slices);
+        th = r.base[j % r.n_base];
+    }
+    const double* fr = r.frames + (size_t)gr_ring::kFrame * ring;
+    double vv[4], ff;
+    gr_ring::form_ray(fr, r.betas[slice], th, vv, ff);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        x[4 * j + q] = fr[q];
+        v[4 * j + q] = vv[q];
+    }
+    f[j] = ff;
+}
+// one lane per search q = 2 (ring * n_slices + slice) + target: the bracket from the slice's base rows.  A slice without a
+// hit has no search: done from the start, its count -1.
+__global__ void __launch_bounds__(64) k_ring_bracket(const RingDev r, int n_search, const double* rows, gr_ring::Search* searches, int32_t* cnt)
+{
+    const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q >= n_search) return;
+    gr_ring::Search s;
+    const bool have = gr_ring::bracket(rows + (size_t)4 * r.n_base * (q >> 1), r.base, r.n_base, q & 1, s.a, s.b, s.best);
+    s.n = s.iters = s.too_many = 0;
+    s.done = have ? 0 : 1;
+    searches[q] = s;
+    cnt[q] = have ? 0 : -1;
+}
+// one lane per search: a live one takes the next slot of this iteration's list and forms its two probe rays there
+__global__ void __launch_bounds__(64) k_ring_probe(const RingDev r, int n_search, const gr_ring::Search* searches, unsigned long long* live,
+                                                   int32_t* list, double* x, double* v, double* f)
+{
+    const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q >= n_search) return;
+    const gr_ring::Search s = searches[q];
+    if (s.done) return;
+    const size_t slot = (size_t)atomicAdd(live, 1ull);          // < n_search: every search adds at most once
+    list[slot] = q;
+    const int sl = q >> 1;
+    const double* fr = r.frames + (size_t)gr_ring::kFrame * (sl / r.n_slices);
+    const double beta = r.betas[sl % r.n_slices];
+    double th[2];
+    gr_ring::probes(s, th[0], th[1]);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        double vv[4], ff;
+        gr_ring::form_ray(fr, beta, th[k], vv, ff);
+        const size_t j = 2 * slot + k;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            x[4 * j + c] = fr[c];
+            v[4 * j + c] = vv[c];
+        }
+        f[j] = ff;
+    }
+}
+// one lane per slot of the list: the golden update of its search from the two probe rows; a kept probe joins the search's run
+// app[q][extrema_iter][5] = (θ, g, ρ, t, status) (n <= extrema_iter counts every kept probe: the run cannot overflow)
+__global__ void __launch_bounds__(64) k_ring_update(const RingDev r, int n_live, const int32_t* list, const double* prows, gr_ring::Search* searches,
+                                                    int32_t* cnt, double* app)
+{
+    const int slot = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (slot >= n_live) return;
+    const int q = list[slot];
+    gr_ring::Search s = searches[q];
+    double th[2];
+    gr_ring::probes(s, th[0], th[1]);
+    const double* pc = prows + 8 * (size_t)slot;
+    const int append = gr_ring::golden_update(s, q & 1, r.extrema_iter, (int)pc[3], pc[1], (int)pc[7], pc[5]);
+    searches[q] = s;
+    if (append) {
+        const int at = cnt[q];
+        if (at < r.extrema_iter) {
+            const double* row = pc + 4 * (append - 1);
+            double* o = app + 5 * ((size_t)q * r.extrema_iter + at);
+            o[0] = th[append - 1];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[1 + c] = row[c];
+            cnt[q] = at + 1;
+        }
+    }
+}
+// one lane per (slice, slot of its cache): base rows, then what the minima search kept, then the maxima search's; zeros behind
+__global__ void __launch_bounds__(256) k_ring_pack(const RingDev r, int64_t n, const double* rows, const int32_t* cnt, const double* app, double* out)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int width = r.n_base + 2 * r.extrema_iter;
+    const int64_t sl = j / width;
+    const int slot = (int)(j % width);
+    const int c_min = cnt[2 * sl] > 0 ? cnt[2 * sl] : 0, c_max = cnt[2 * sl + 1] > 0 ? cnt[2 * sl + 1] : 0;
+    double o[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    const double* src = nullptr;
+    if (slot < r.n_base) {
+        o[0] = r.base[slot];
+        src = rows + 4 * ((size_t)sl * r.n_base + slot);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[1 + c] = src[c];
+    } else {
+        const int k = slot - r.n_base;
+        if (k < c_min) src = app + 5 * ((size_t)(2 * sl) * r.extrema_iter + k);
+        else if (k < c_min + c_max) src = app + 5 * ((size_t)(2 * sl + 1) * r.extrema_iter + (k - c_min));
+        if (src) {
+#pragma unroll
+            for (int c = 0; c < 5; ++c) o[c] = src[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 5; ++c) out[5 * j + c] = o[c];
+}
+}  // namespace
+}  // extern "C++"
+
+static int32_t ring_args(gr_ctx* ctx, const gr_config* cfg, const gr_ringset* rings, const gr_pointfunction* pf)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!cfg || !rings || !pf) return fail(GR_ERR_INVALID_ARGUMENT, "config / ring set / point function is null");
+    if (cfg->disc_id != GR_DISC_THIN) return fail(GR_ERR_UNSUPPORTED, "the arms of a ring corona are traced onto a ThinDisc only");
+    if (rings->n_rings < 1 || rings->n_slices < 1 || rings->n_rings > (1 << 20) || rings->n_slices > (1 << 20) || !rings->frames || !rings->betas)
+        return fail(GR_ERR_INVALID_ARGUMENT, "ring set: n_rings and n_slices in 1 ... 2^20, frames and betas");
+    if (pf->pf_id != GR_PF_REDSHIFT) return fail(GR_ERR_INVALID_ARGUMENT, "needs the redshift point function");
+    if (pf->has_u_src) return fail(GR_ERR_INVALID_ARGUMENT, "a ring set brings a source velocity per ring: pf->has_u_src must be 0");
+    return GR_OK;
+}
+// the ray-summary launch on n rays written as x[n][4], v[n][4]: rows (g, ρ, t, status), g against each ray's own source (f)
+static int32_t ring_trace(gr_ctx* ctx, const gr_config* cfg, const PfDev& pfd, const double* d_x, const double* d_v, const double* d_f,
+                          int64_t n, double* d_rows, gr_stats* d_stats)
+{
+    Params p;
+    Cold cd;
+    std::memset(&p, 0, sizeof p);
+    std::memset(&cd, 0, sizeof cd);
+    p.cfg = *cfg;
+    p.n = n;
+    p.stats = (unsigned long long*)d_stats;
+    cd.src_mode = 1;
+    cd.out_mode = 4;
+    cd.x = d_x;
+    cd.x_stride = 4;
+    cd.v = d_v;
+    cd.pf = pfd;
+    cd.lp_rmin = 0.0;
+    cd.lp_rmax = INFINITY;
+    cd.lp_pairs = d_rows;
+    cd.range = gr_range{ 0, n, n > 0 ? n : 1, 1 };
+    cd.swizzle = 0;
+    int32_t rc;
+    if ((rc = launch_trace(ctx, p, cd, ctx->stream)) != GR_OK) return rc;
+    hipLaunchKernelGGL(k_sky_scale_g, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rows, d_f, n);
+    GR_HIP(hipGetLastError());
+    return GR_OK;
+}
+
+int32_t gr_ring_rays(gr_ctx* ctx, const gr_config* cfg, const gr_ringset* rings, const gr_pointfunction* pf, int64_t n,
+                     const int64_t* ring_slice, const double* angles, double* rows_out, double* v_out, gr_stats* stats)
+{
+    int32_t rc;
+    if ((rc = ring_args(ctx, cfg, rings, pf)) != GR_OK) return rc;
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if (n < 0 || n > INT32_MAX) return fail(GR_ERR_INVALID_ARGUMENT, "gr_ring_rays: n in 0 ... 2^31 - 1");
+    if (n > 0 && (!ring_slice || !angles || !rows_out)) return fail(GR_ERR_INVALID_ARGUMENT, "gr_ring_rays: ring_slice / angles / rows_out is null");
+    for (int64_t j = 0; j < n; ++j)
+        if (ring_slice[2 * j] < 0 || ring_slice[2 * j] >= rings->n_rings || ring_slice[2 * j + 1] < 0 || ring_slice[2 * j + 1] >= rings->n_slices)
+            return fail(GR_ERR_INVALID_ARGUMENT, "gr_ring_rays: ray " + std::to_string(j) + " names a ring or a slice the set does not have");
+    GR_HIP(hipSetDevice(ctx->device));
+    if (n == 0) return GR_OK;
+    const size_t R = (size_t)rings->n_rings, NS = (size_t)rings->n_slices, N = (size_t)n;
+    const size_t in_w = gr_ring::kFrame * R + NS + N + 2 * N;      // frames | betas | angles | ring_slice (2 n int64)
+    if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, 8 * in_w + 64)) != GR_OK) return rc;
+    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, 8 * 13 * N + 64)) != GR_OK) return rc;
+    double* d_frames = (double*)ctx->d_in;
+    double* d_betas = d_frames + gr_ring::kFrame * R;
+    double* d_angles = d_betas + NS;
+    int64_t* d_rs = (int64_t*)(d_angles + N);
+    double* d_x = (double*)ctx->d_scratch;
+    double *d_v = d_x + 4 * N, *d_f = d_v + 4 * N, *d_rows = d_f + N;
+    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
+    GR_HIP(hipMemcpyAsync(d_frames, rings->frames, 8 * gr_ring::kFrame * R, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemcpyAsync(d_betas, rings->betas, 8 * NS, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemcpyAsync(d_angles, angles, 8 * N, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemcpyAsync(d_rs, ring_slice, 8 * 2 * N, hipMemcpyHostToDevice, ctx->stream));
+    Cold staged;
+    std::memset(&staged, 0, sizeof staged);
+    if ((rc = stage_pf(ctx, cfg, pf, staged.pf, ctx->stream)) != GR_OK) return rc;
+    const RingDev rd{ d_frames, d_betas, nullptr, (int32_t)R, (int32_t)NS, 0, 0 };
+    hipLaunchKernelGGL(k_ring_rays, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, rd, n, (const int64_t*)d_rs,
+                       (const double*)d_angles, d_x, d_v, d_f);
+    GR_HIP(hipGetLastError());
+    if ((rc = ring_trace(ctx, cfg, staged.pf, d_x, d_v, d_f, n, d_rows, stats ? (gr_stats*)ctx->d_stats : nullptr)) != GR_OK) return rc;
+    GR_HIP(hipMemcpyAsync(rows_out, d_rows, 8 * 4 * N, hipMemcpyDeviceToHost, ctx->stream));
+    if (v_out) GR_HIP(hipMemcpyAsync(v_out, d_v, 8 * 4 * N, hipMemcpyDeviceToHost, ctx->stream));
+    return end_host_call(ctx, stats);
+}
+
+int32_t gr_ring_arms(gr_ctx* ctx, const gr_config* cfg, const gr_ringset* rings, const gr_pointfunction* pf, double* rows_out,
+                     int64_t* counts_out, gr_stats* stats)
+{
+    int32_t rc;
+    if ((rc = ring_args(ctx, cfg, rings, pf)) != GR_OK) return rc;
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if (!rings->base_angles || !rows_out || !counts_out) return fail(GR_ERR_INVALID_ARGUMENT, "gr_ring_arms: base_angles / rows_out / counts_out is null");
+    if (rings->n_base < 2 || rings->extrema_iter < 1 || rings->n_base > (1 << 24) || rings->extrema_iter > (1 << 20))
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_ring_arms: n_base in 2 ... 2^24, extrema_iter in 1 ... 2^20");
+    const size_t R = (size_t)rings->n_rings, NS = (size_t)rings->n_slices, NB = (size_t)rings->n_base, E = (size_t)rings->extrema_iter;
+    const size_t S = R * NS, W = NB + 2 * E, n0 = S * NB, Q = 2 * S;
+    if (n0 > (size_t)INT32_MAX || S * W > (size_t)INT32_MAX) return fail(GR_ERR_INVALID_ARGUMENT, "gr_ring_arms: at most 2^31 - 1 base rays and cache rows");
+    GR_HIP(hipSetDevice(ctx->device));
+    static_assert(sizeof(gr_ring::Search) == 40, "five 8-byte units");
+    // frames | betas | base | x0 v0 f0 rows0 | probe x v f rows (2 Q rays) | app | out | searches | cnt | list | live
+    const size_t max_it = 2 * E + 1;
+    const size_t o_frames = 0, o_betas = o_frames + gr_ring::kFrame * R, o_base = o_betas + NS, o_x0 = o_base + NB, o_v0 = o_x0 + 4 * n0,
+                 o_f0 = o_v0 + 4 * n0, o_rows0 = o_f0 + n0, o_px = o_rows0 + 4 * n0, o_pv = o_px + 8 * Q, o_pf = o_pv + 8 * Q, o_prows = o_pf + 2 * Q,
+                 o_app = o_prows + 8 * Q, o_out = o_app + 5 * Q * E, o_search = o_out + 5 * S * W, o_cnt = o_search + 5 * Q, o_list = o_cnt + S,
+                 o_live = o_list + S, total = o_live + max_it + 1;
+    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, 8 * total + 64)) != GR_OK) return rc;
+    double* base = (double*)ctx->d_scratch;
+    gr_ring::Search* d_search = (gr_ring::Search*)(base + o_search);
+    int32_t* d_cnt = (int32_t*)(base + o_cnt);
+    int32_t* d_list = (int32_t*)(base + o_list);
+    unsigned long long* d_live = (unsigned long long*)(base + o_live);
+    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
+    gr_stats* d_stats = stats ? (gr_stats*)ctx->d_stats : nullptr;
+    GR_HIP(hipMemcpyAsync(base + o_frames, rings->frames, 8 * gr_ring::kFrame * R, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemcpyAsync(base + o_betas, rings->betas, 8 * NS, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemcpyAsync(base + o_base, rings->base_angles, 8 * NB, hipMemcpyHostToDevice, ctx->stream));
+    GR_HIP(hipMemsetAsync(d_live, 0, 8 * (max_it + 1), ctx->stream));
+    Cold staged;
+    std::memset(&staged, 0, sizeof staged);
+    if ((rc = stage_pf(ctx, cfg, pf, staged.pf, ctx->stream)) != GR_OK) return rc;
+    const RingDev rd{ base + o_frames, base + o_betas, base + o_base, (int32_t)R, (int32_t)NS, (int32_t)NB, (int32_t)E };
+    // 1. the base rays of every slice, one launch
+    hipLaunchKernelGGL(k_ring_rays, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, ctx->stream, rd, (int64_t)n0, (const int64_t*)nullptr,
+                       (const double*)nullptr, base + o_x0, base + o_v0, base + o_f0);
+    GR_HIP(hipGetLastError());
+    if ((rc = ring_trace(ctx, cfg, staged.pf, base + o_x0, base + o_v0, base + o_f0, (int64_t)n0, base + o_rows0, d_stats)) != GR_OK) return rc;
+    // 2. the brackets
+    const dim3 q_grid((unsigned)((Q + 63) / 64));
+    hipLaunchKernelGGL(k_ring_bracket, q_grid, dim3(64), 0, ctx->stream, rd, (int)Q, (const double*)(base + o_rows0), d_search, d_cnt);
+    GR_HIP(hipGetLastError());
+    // 3. the searches in lock-step: probe rays of the live ones, trace, update
+    for (size_t it = 0; it < max_it; ++it) {
+        hipLaunchKernelGGL(k_ring_probe, q_grid, dim3(64), 0, ctx->stream, rd, (int)Q, (const gr_ring::Search*)d_search, d_live + it, d_list,
+                           base + o_px, base + o_pv, base + o_pf);
+        GR_HIP(hipGetLastError());
+        unsigned long long n_live = 0;
+        GR_HIP(hipMemcpyAsync(&n_live, d_live + it, 8, hipMemcpyDeviceToHost, ctx->stream));
+        GR_HIP(hipStreamSynchronize(ctx->stream));
+        if (n_live == 0) break;
+        if (n_live > Q) return fail(GR_ERR_HIP, "gr_ring_arms: more live searches than searches");
+        if ((rc = ring_trace(ctx, cfg, staged.pf, base + o_px, base + o_pv, base + o_pf, (int64_t)(2 * n_live), base + o_prows, d_stats)) != GR_OK) return rc;
+        hipLaunchKernelGGL(k_ring_update, dim3((unsigned)((n_live + 63) / 64)), dim3(64), 0, ctx->stream, rd, (int)n_live, (const int32_t*)d_list,
+                           (const double*)(base + o_prows), d_search, d_cnt, base + o_app);
+        GR_HIP(hipGetLastError());
+    }
+    // 4. every slice's cache in the reference's order
+    hipLaunchKernelGGL(k_ring_pack, dim3((unsigned)((S * W + 255) / 256)), dim3(256), 0, ctx->stream, rd, (int64_t)(S * W), (const double*)(base + o_rows0),
+                       (const int32_t*)d_cnt, (const double*)(base + o_app), base + o_out);
+    GR_HIP(hipGetLastError());
+    std::vector<int32_t> cnt(Q);
+    GR_HIP(hipMemcpyAsync(rows_out, base + o_out, 8 * 5 * S * W, hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipMemcpyAsync(cnt.data(), d_cnt, 4 * Q, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = end_host_call(ctx, stats)) != GR_OK) return rc;
+    for (size_t s = 0; s < S; ++s) {
+        counts_out[3 * s] = (int64_t)NB;
+        counts_out[3 * s + 1] = cnt[2 * s];
+        counts_out[3 * s + 2] = cnt[2 * s + 1];
+    }
     return GR_OK;
 }
 

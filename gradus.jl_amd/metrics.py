@@ -191,8 +191,8 @@ class BumblebeeMetric(AbstractStaticAxisSymmetric):
 
 @dataclass(frozen=True)
 class KerrNewmanMetric(AbstractStaticAxisSymmetric):
-    """KerrNewmanMetric(M, a, Q) -- src/metrics/kerr-newman-ad.jl:6-64.  Null / uncharged
-    geodesics only: the Lorentz-force term of a charged test particle (q ≠ 0) is not on the device."""
+    """KerrNewmanMetric(M, a, Q) -- src/metrics/kerr-newman-ad.jl:6-64.  The Lorentz-force term of a charged test
+    particle (`q` of tracegeodesics / TraceGeodesic(μ, q), kerr-newman-ad.jl:66-100) is part of this metric's device kernels."""
 
     M: float = 1.0
     a: float = 0.0

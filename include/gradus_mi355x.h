@@ -693,6 +693,49 @@ int32_t gr_tf_lagtransfer_td(gr_ctx* ctx, const gr_tfset* set, const gr_tfprofil
                              double* out /* host, n_g x n_t raw sums */,
                              double* em_out /* host or NULL: n_int x (2 + n_time): t_lo, t_hi, em[k] */);
 
+/* ---- the longitudinal arms of ring coronae (added within ABI 8, nothing else changes): corona_arms for a RingCorona
+ * (src/corona/models/ring.jl:1-485) and for the concentric rings of a DiscCorona (src/corona/models/extended.jl:185-200).
+ * A ring is one representative point; its sky is cut into slices by the angle β about the point's radial direction, and in
+ * a slice a ray leaves at the local angle θ (rotatorfunctor, ring.jl:105-118).  A gr_ringset holds per ring a FRAME of
+ * GR_SKY_ROW doubles, laid out as a row of gr_rayset.sky_rows -- position x[4] (x[2] is the angle of the axis), the matrix
+ * T diag(1, J) [16], the source velocity with its index lowered [4] and (g_tt, 0, 0, g_tϕ) at x [4] -- the n_slices angles β
+ * and the n_base = n_samples - 2 extrema_iter local angles of every slice's base rays, ascending.
+ * Every ray is written as (x, v) on the device and traced by the ray-summary launch of gr_ray_summary (any metric, either
+ * kernel); g of a row is the energy ratio against ITS ring's source velocity and the disc's Keplerian / plunging velocity, as
+ * gr_corona_trace forms it for a source of many positions: pf->pf_id = GR_PF_REDSHIFT and pf->has_u_src = 0.
+ * Only cfg->disc_id == GR_DISC_THIN is accepted (GR_ERR_UNSUPPORTED otherwise).  All pointers are host pointers, staged per
+ * call; nothing is kept on the context.
+ *
+ * gr_ring_rays forms and traces n rays, ray j at the local angle angles[j] in slice ring_slice[2 j + 1] of ring
+ * ring_slice[2 j]: rows_out[j] = (g, ρ, t, status), v_out[j] (unless null) the formed, unconstrained velocity.  n_base,
+ * extrema_iter and base_angles of the set are not read.
+ *
+ * gr_ring_arms is the producer in one call: the base rays of every slice of every ring in one launch, then per slice two
+ * golden-section searches side by side -- for the minimal and for the maximal ρ (_determine_bracket, _golden_bracket!,
+ * ring.jl:131-237) -- all slices in lock-step: per iteration one launch forms the two probe rays of every search that is
+ * still live, one traces them and one updates the brackets, until no search is live (at most 2 extrema_iter + 1 iterations).
+ *   rows_out[ring][slice][n_base + 2 extrema_iter][5] = (θ as probed, g, ρ, t, status): the n_base base rows, then the probes
+ *       the minima search kept, then those the maxima search kept (the reference's order); zeros behind them.
+ *   counts_out[ring][slice][3] = (n_base, kept by the minima search, kept by the maxima search); a slice none of whose base
+ *       rays met the disc -- an error in the reference -- has (n_base, -1, -1) and no search.
+ * GR_ERR_INVALID_ARGUMENT for: a null pointer, n_rings, n_slices or extrema_iter < 1, n_base < 2, more than 2^31 - 1 base rays,
+ * a ring or slice index out of range, pf->has_u_src != 0. */
+typedef struct gr_ringset {
+    int64_t n_rings;
+    int64_t n_slices;
+    int64_t n_base;             /* base rays per slice (gr_ring_arms)                                           */
+    int64_t extrema_iter;       /* the searches' iteration count (gr_ring_arms)                                 */
+    const double* frames;       /* n_rings x GR_SKY_ROW                                                         */
+    const double* betas;        /* n_slices                                                                     */
+    const double* base_angles;  /* n_base, ascending (gr_ring_arms)                                             */
+} gr_ringset;
+int32_t gr_ring_rays(gr_ctx* ctx, const gr_config* cfg, const gr_ringset* rings, const gr_pointfunction* pf, int64_t n,
+                     const int64_t* ring_slice /* host, n x 2 */, const double* angles /* host, n */,
+                     double* rows_out /* host, n x 4 */, double* v_out /* host, n x 4, or NULL */, gr_stats* stats);
+int32_t gr_ring_arms(gr_ctx* ctx, const gr_config* cfg, const gr_ringset* rings, const gr_pointfunction* pf,
+                     double* rows_out /* host, n_rings x n_slices x (n_base + 2 extrema_iter) x 5 */,
+                     int64_t* counts_out /* host, n_rings x n_slices x 3 */, gr_stats* stats);
+
 /* ---- tabulated metrics (ABI 7; segments, axis terms: ABI 8; GR_METRIC_TABULATED): the AbstractMetric plugin interface on the device ----
  * Host-only functions (no context, no device): plan a grid, learn its nodes, fit, check.
  *
