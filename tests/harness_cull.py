@@ -48,6 +48,11 @@ def render_tiles(G, config, pf, tiles, arm):
     return {k: v.reshape(tiles.size, 64) for k, v in out.items()}
 
 
+def _ratio(num, den):
+    """num / den; 1.0 where den is 0: neither arm traced anything (every ray of the tiles was decided at the start)."""
+    return num / den if den else 1.0
+
+
 def census(G, config, pf, tiles):
     """All four arms on the same tiles, and what the culls are judged by.  "wave_steps" is the sum over tiles of the longest lane's
     attempted steps (what a one-wave workgroup costs); "wrongly_decided" counts rays an arm ended early although the full trace
@@ -71,8 +76,8 @@ def census(G, config, pf, tiles):
             "wrongly_decided": int(np.sum(fired & hit)),
         }
     a = res["arms"]
-    res["wave_steps_ratio_vs_escape_cull_alone"] = {k: a[k]["wave_steps"] / a["step"]["wave_steps"] for k in ("both",)}
-    res["wave_steps_ratio_vs_off"] = {k: a[k]["wave_steps"] / a["off"]["wave_steps"] for k in ("start", "step", "both")}
+    res["wave_steps_ratio_vs_escape_cull_alone"] = {k: _ratio(a[k]["wave_steps"], a["step"]["wave_steps"]) for k in ("both",)}
+    res["wave_steps_ratio_vs_off"] = {k: _ratio(a[k]["wave_steps"], a["off"]["wave_steps"]) for k in ("start", "step", "both")}
     # what tests/test_gpu_escape_cull.py brackets: accepted steps with GRADUS_MI355X_ESCAPE_CULL unset over =0 (start cull on in both)
-    res["escape_switch_bracket_ratio"] = a["both"]["accepted_steps"] / a["start"]["accepted_steps"]
+    res["escape_switch_bracket_ratio"] = _ratio(a["both"]["accepted_steps"], a["start"]["accepted_steps"])
     return res, runs

@@ -78,6 +78,11 @@ def render_tiles(G, config, pf, tiles, step, start, entry, defer, zeta=-1.0, def
     return {k: v.reshape(tiles.size, 64) for k, v in out.items()}
 
 
+def _ratio(num, den):
+    """num / den; 1.0 where den is 0: neither arm traced anything (every ray of the tiles was decided at the start)."""
+    return num / den if den else 1.0
+
+
 def census(G, config, pf, tiles, zeta=-1.0, defer_zeta=None):
     """The arms of ARMS on the same tiles.  "wave_steps" is the sum over tiles of the longest lane's attempted steps (what a
     one-wave workgroup costs); "wrongly_ended" counts rays an arm ended early (at the start, on entry or by the defer cull)
@@ -107,8 +112,8 @@ def census(G, config, pf, tiles, zeta=-1.0, defer_zeta=None):
     a = res["arms"]
     res["hit_fraction"] = float(np.mean(base["status"] == hit_code))
     # the launch: the defer cull on against off, every other cull on
-    res["defer_wave_steps_ratio"] = a["all"]["wave_steps"] / a["no-defer"]["wave_steps"]
-    res["defer_accepted_steps_ratio"] = a["all"]["accepted_steps"] / a["no-defer"]["accepted_steps"]
+    res["defer_wave_steps_ratio"] = _ratio(a["all"]["wave_steps"], a["no-defer"]["wave_steps"])
+    res["defer_accepted_steps_ratio"] = _ratio(a["all"]["accepted_steps"], a["no-defer"]["accepted_steps"])
     # what tests/test_gpu_escape_cull.py brackets: accepted steps with GRADUS_MI355X_ESCAPE_CULL unset over =0
-    res["escape_switch_bracket_ratio"] = a["all"]["accepted_steps"] / a["start"]["accepted_steps"]
+    res["escape_switch_bracket_ratio"] = _ratio(a["all"]["accepted_steps"], a["start"]["accepted_steps"])
     return res, runs

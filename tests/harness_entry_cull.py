@@ -84,6 +84,11 @@ def entry_bounds(config, rays, zeta=-1.0):
     return {k: out[:, i] for i, k in enumerate(BOUNDS)}
 
 
+def _ratio(num, den):
+    """num / den; 1.0 where den is 0: neither arm traced anything (every ray of the tiles was decided at the start)."""
+    return num / den if den else 1.0
+
+
 def census(G, config, pf, tiles, zeta=-1.0):
     """The arms of ARMS on the same tiles.  "wave_steps" is the sum over tiles of the longest lane's attempted steps (what a
     one-wave workgroup costs); "wrongly_ended" counts rays the entry cull ended although the arm without it hits the disc.
@@ -111,9 +116,9 @@ def census(G, config, pf, tiles, zeta=-1.0):
     a = res["arms"]
     res["hit_fraction"] = float(np.mean(base["status"] == hit_code))
     # the launch: the entry cull on against off, every other cull on
-    res["entry_wave_steps_ratio"] = a["all"]["wave_steps"] / a["no-entry"]["wave_steps"]
-    res["entry_accepted_steps_ratio"] = a["all"]["accepted_steps"] / a["no-entry"]["accepted_steps"]
+    res["entry_wave_steps_ratio"] = _ratio(a["all"]["wave_steps"], a["no-entry"]["wave_steps"])
+    res["entry_accepted_steps_ratio"] = _ratio(a["all"]["accepted_steps"], a["no-entry"]["accepted_steps"])
     # what tests/test_gpu_escape_cull.py brackets: accepted steps with GRADUS_MI355X_ESCAPE_CULL unset over =0, the decisions at
     # the start on in both arms
-    res["escape_switch_bracket_ratio"] = a["all"]["accepted_steps"] / a["start"]["accepted_steps"]
+    res["escape_switch_bracket_ratio"] = _ratio(a["all"]["accepted_steps"], a["start"]["accepted_steps"])
     return res, runs

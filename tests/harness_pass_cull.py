@@ -89,6 +89,11 @@ def pass_bounds(config, rays, zeta=-1.0):
     return {k: out[:, i] for i, k in enumerate(BOUNDS)}
 
 
+def _ratio(num, den):
+    """num / den; 1.0 where den is 0: neither arm traced anything (every ray of the tiles was decided at the start)."""
+    return num / den if den else 1.0
+
+
 def census(G, config, pf, tiles, zeta=-1.0):
     """The four arms of ARMS on the same tiles.  "wave_steps" is the sum over tiles of the longest lane's attempted steps (what a
     one-wave workgroup costs); "wrongly_decided" counts rays the pass cull decided although the arm without it hits the disc.
@@ -115,10 +120,10 @@ def census(G, config, pf, tiles, zeta=-1.0):
     a = res["arms"]
     res["hit_fraction"] = float(np.mean(runs["start"]["status"] == hit_code))
     # the launch: the pass cull on against off, every other cull on
-    res["pass_wave_steps_ratio"] = a["both+pass"]["wave_steps"] / a["both"]["wave_steps"]
-    res["pass_accepted_steps_ratio"] = a["both+pass"]["accepted_steps"] / a["both"]["accepted_steps"]
+    res["pass_wave_steps_ratio"] = _ratio(a["both+pass"]["wave_steps"], a["both"]["wave_steps"])
+    res["pass_accepted_steps_ratio"] = _ratio(a["both+pass"]["accepted_steps"], a["both"]["accepted_steps"])
     # what tests/test_gpu_escape_cull.py brackets: accepted steps with GRADUS_MI355X_ESCAPE_CULL unset over =0, the decisions at
     # the start on in both arms
-    res["escape_switch_bracket_ratio"] = a["both+pass"]["accepted_steps"] / a["start+pass"]["accepted_steps"]
-    res["escape_switch_bracket_ratio_pass_off"] = a["both"]["accepted_steps"] / a["start"]["accepted_steps"]
+    res["escape_switch_bracket_ratio"] = _ratio(a["both+pass"]["accepted_steps"], a["start+pass"]["accepted_steps"])
+    res["escape_switch_bracket_ratio_pass_off"] = _ratio(a["both"]["accepted_steps"], a["start"]["accepted_steps"])
     return res, runs
