@@ -275,6 +275,13 @@ class DilatonAxion(AbstractStaticAxisSymmetric):
     b: float = 1.0
     metric_id = GR_METRIC_DILATON_AXION
 
+    def __post_init__(self):
+        # The reference forms β / b, β / a and β / (a b) whenever β != 0 (dilaton-axion-ad.jl:25-27): with b = 0 or a = 0 they are
+        # Inf, every component is Inf or NaN and nothing it then computes means anything.  Refused here, where Python's
+        # division would otherwise raise ZeroDivisionError from inside isco() or a render.
+        if self.β != 0.0 and (self.b == 0.0 or self.a == 0.0):
+            raise ValueError("DilatonAxion: β != 0 needs b != 0 and a != 0 (the metric divides β by both)")
+
     def abi_params(self):
         return [self.M, self.a, self.β, self.b]
 

@@ -743,6 +743,7 @@ typedef struct {
     double *r, *vt, *vr, *vphi;
     int64_t cap, n;
     double *t;      /* optional: affine time of every saved state */
+    double *th, *vth;   /* optional: θ and v^θ of every saved state */
 } save_t;
 
 static void save_state(save_t* s, const double u[8], double t)
@@ -750,6 +751,8 @@ static void save_state(save_t* s, const double u[8], double t)
     if (!s || s->n >= s->cap) return;
     s->r[s->n] = u[1]; s->vt[s->n] = u[4]; s->vr[s->n] = u[5]; s->vphi[s->n] = u[7];
     if (s->t) s->t[s->n] = t;
+    if (s->th) s->th[s->n] = u[2];
+    if (s->vth) s->vth[s->n] = u[6];
     s->n++;
 }
 
@@ -1157,6 +1160,8 @@ static double generic_isco(const orc_config* c)
 double orc_isco(const orc_config* c)
 {
     if (c->metric_id == ORC_METRIC_KERR) return kerr_isco(c->params[0], c->params[1]);
+    /* isco(m::KerrRefractive) = Kerr's closed form, kerr-refractive-ad.jl:62 */
+    if (c->metric_id == ORC_METRIC_KERR_REFRACTIVE) return kerr_isco(c->params[0], c->params[1]);
     return generic_isco(c);
 }
 
@@ -1279,8 +1284,24 @@ void orc_apply_pf(const orc_config* c, const orc_pf* pf, const orc_point* pts, i
 
 /* plunging_fourvelocity, circular-orbits.jl:128-146 ; interpolate_plunging_velocities,
  * orbit-solving.jl:137-167 */
-int64_t orc_plunging_table(const orc_config* c, double r_isco, double* r, double* vt, double* vr,
-                           double* vphi, int64_t cap)
+/* inner_radius(m): M + sqrt(M^2 - a^2) (kerr-metric.jl:72) unless the metric defines its own */
+static double metric_inner_radius(const orc_config* c)
+{
+    const double M = c->params[0], a = c->params[1];
+    if (c->metric_id == ORC_METRIC_KERR_NEWMAN) {            /* kerr-newman-ad.jl:62 */
+        const double Q = c->params[2];
+        return M + sqrt(M * M - a * a - Q * Q);
+    }
+    if (c->metric_id == ORC_METRIC_DILATON_AXION) {          /* dilaton-axion-ad.jl:71-74 */
+        const double be = c->params[2], b = c->params[3];
+        const double bb = (be == 0.0) ? 0.0 : be / b;
+        return M + b + sqrt((M + b) * (M + b) - a * a + be * be - (M - 2.0 * b) * M * bb * bb);
+    }
+    return M + sqrt(M * M - a * a);
+}
+
+int64_t orc_plunging_table_ex(const orc_config* c, double r_isco, double* r, double* vt, double* vr,
+                              double* vphi, double* theta, double* vtheta, int64_t cap)
 {
     orc_config cc = *c;
     const double reltol = 1e-9, dr = reltol * 10.0;
@@ -1291,9 +1312,8 @@ int64_t orc_plunging_table(const orc_config* c, double r_isco, double* r, double
     cc.lambda1 = 50000.0;
     cc.disc_id = ORC_DISC_NONE;
     cc.upper_hemisphere = 0;
-    /* chart_for_metric(m; closest_approach = 1.000001): inner_radius(m) = M + sqrt(M^2 - a^2) */
-    const double M = c->params[0], a = c->params[1];
-    cc.r_inner = (M + sqrt(M * M - a * a)) * 1.000001;
+    /* chart_for_metric(m; closest_approach = 1.000001) */
+    cc.r_inner = metric_inner_radius(c) * 1.000001;
     cc.r_outer = 12000.0;
 
     double g[5], dg[5], dth[5], gi[5], ut, up;
@@ -1306,10 +1326,16 @@ int64_t orc_plunging_table(const orc_config* c, double r_isco, double* r, double
     const double den = -g[1];
     double u0[8] = { 0.0, r_isco - dr, M_PI / 2.0, 0.0, vtt, -sqrt(fabs(nom / den)), 0.0, vpp };
     u0[4] = orc_constrain_time(&cc, u0, u0 + 4);
-    save_t sv = { r, vt, vr, vphi, cap, 0, NULL };
+    save_t sv = { r, vt, vr, vphi, cap, 0, NULL, theta, vtheta };
     orc_point pt;
     integrate(&cc, u0, &pt, NULL, &sv);
     return sv.n;
+}
+
+int64_t orc_plunging_table(const orc_config* c, double r_isco, double* r, double* vt, double* vr,
+                           double* vphi, int64_t cap)
+{
+    return orc_plunging_table_ex(c, r_isco, r, vt, vr, vphi, NULL, NULL, cap);
 }
 
 /* debugging aid for the tests: every accepted step (t, r) of one ray */
@@ -1321,7 +1347,7 @@ int64_t orc_trace_steps(const orc_config* c, const double x[4], const double v[4
     memcpy(u0 + 4, v, 4 * sizeof(double));
     u0[4] = orc_constrain_time(c, x, v);
     double* scratch = (double*)malloc(sizeof(double) * 3 * (size_t)cap);
-    save_t sv = { r, scratch, scratch + cap, scratch + 2 * cap, cap, 0, t };
+    save_t sv = { r, scratch, scratch + cap, scratch + 2 * cap, cap, 0, t, NULL, NULL };
     integrate(c, u0, out, NULL, &sv);
     free(scratch);
     return sv.n;

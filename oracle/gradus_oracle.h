@@ -161,6 +161,9 @@ void orc_apply_pf(const orc_config* c, const orc_pf* pf, const orc_point* pts, i
  * number of rows written (<= cap). rows: r, vt, vr, vphi (unsorted, in step order) */
 int64_t orc_plunging_table(const orc_config* c, double r_isco, double* r, double* vt, double* vr,
                            double* vphi, int64_t cap);
+/* the same with theta and v^theta of every row (either may be NULL): does the plunge stay in the equatorial plane? */
+int64_t orc_plunging_table_ex(const orc_config* c, double r_isco, double* r, double* vt, double* vr,
+                              double* vphi, double* theta, double* vtheta, int64_t cap);
 
 int64_t orc_trace_steps(const orc_config* c, const double x[4], const double v[4], orc_point* out,
                         double* t, double* r, int64_t cap);

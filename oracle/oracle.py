@@ -133,17 +133,40 @@ class user_metric_library:
     """`with oracle.user_metric_library(): ...` -- every call inside goes to libgradus_oracle_usermetric.so, the build that
     knows the metric "test-bump"; outside, the main oracle is untouched (and bit for bit what it was before that metric existed)."""
 
+    _path = _USER_LIB_PATH
+    _build = staticmethod(build_usermetric)
+
     def __enter__(self):
         global _lib, _LIB_PATH
         self._saved = (_lib, _LIB_PATH)
-        build_usermetric()
-        _lib, _LIB_PATH = None, _USER_LIB_PATH
+        self._build()
+        _lib, _LIB_PATH = None, self._path
         return lib()
 
     def __exit__(self, *exc):
         global _lib, _LIB_PATH
         _lib, _LIB_PATH = self._saved
         return False
+
+
+_NOFMA_LIB_PATH = os.path.join(_HERE, "libgradus_oracle_nofma.so")
+
+
+def build_nofma(force: bool = False) -> str:
+    """The oracle with FMA contraction off (oracle/Makefile `nofma`): a second rounding of the same algorithm."""
+    if force or not os.path.exists(_NOFMA_LIB_PATH) or any(
+        os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(_NOFMA_LIB_PATH)
+        for f in ("gradus_oracle.c", "gradus_oracle.h", "metrics_tmpl.h")
+    ):
+        subprocess.check_call(["make", "-s", "-C", _HERE, "nofma"])
+    return _NOFMA_LIB_PATH
+
+
+class nofma_library(user_metric_library):
+    """`with oracle.nofma_library(): ...` -- every call inside goes to libgradus_oracle_nofma.so."""
+
+    _path = _NOFMA_LIB_PATH
+    _build = staticmethod(build_nofma)
 
 
 def lib():
@@ -171,6 +194,8 @@ def lib():
         L.orc_apply_pf.argtypes = [cp, C.POINTER(PF), C.c_void_p, C.c_int64, C.c_double, dp, C.c_int]
         L.orc_plunging_table.argtypes = [cp, C.c_double, dp, dp, dp, dp, C.c_int64]
         L.orc_plunging_table.restype = C.c_int64
+        L.orc_plunging_table_ex.argtypes = [cp, C.c_double, dp, dp, dp, dp, dp, dp, C.c_int64]
+        L.orc_plunging_table_ex.restype = C.c_int64
         L.orc_tsit5_tableau.argtypes = [dp, dp, dp, dp]
         L.orc_max_threads.restype = C.c_int
         L.orc_trace_steps.argtypes = [cp, dp, dp, C.c_void_p, dp, dp, C.c_int64]
@@ -416,6 +441,13 @@ def plunging_table(cfg, r_isco, cap=100000):
     n = lib().orc_plunging_table(C.byref(cfg), r_isco, _dp(r), _dp(vt), _dp(vr), _dp(vp), cap)
     idx = np.argsort(r[:n], kind="stable")[1:]
     return tuple(np.ascontiguousarray(a[:n][idx]) for a in (r, vt, vr, vp))
+
+
+def plunging_path(cfg, r_isco, cap=100000):
+    """The plunge behind `plunging_table` as it was traced: (r, vt, vr, vphi, θ, v^θ) of every accepted step, in step order."""
+    a = [np.zeros(cap) for _ in range(6)]
+    n = lib().orc_plunging_table_ex(C.byref(cfg), r_isco, *(_dp(x) for x in a), cap)
+    return tuple(x[:n].copy() for x in a)
 
 
 def apply_pf(cfg, points, max_time, pf_id=PF_AFFINE_TIME, filter_id=FILTER_NONE, fill=float("nan"), r_isco=0.0,
