@@ -26,7 +26,7 @@ def kernel_source_sha16() -> str:
     h = hashlib.sha256()
     root = os.path.dirname(_HERE)
     for rel in ("gradus.jl_amd/csrc/gr_device.hpp", "gradus.jl_amd/csrc/gr_kernels.hpp", "gradus.jl_amd/csrc/gr_tangent.hpp",
-                "gradus.jl_amd/csrc/gr_tabmetric.hpp", "gradus.jl_amd/csrc/gr_lagbin.hpp", "gradus.jl_amd/csrc/gr_tfint.hpp", "gradus.jl_amd/csrc/gr_tftd.hpp", "gradus.jl_amd/csrc/gr_stats_fold.hpp", "gradus.jl_amd/csrc/metric_table.hip",
+                "gradus.jl_amd/csrc/gr_tabmetric.hpp", "gradus.jl_amd/csrc/gr_lagbin.hpp", "gradus.jl_amd/csrc/gr_tfint.hpp", "gradus.jl_amd/csrc/gr_tftd.hpp", "gradus.jl_amd/csrc/gr_stats_fold.hpp", "gradus.jl_amd/csrc/gr_tile_order.hpp", "gradus.jl_amd/csrc/metric_table.hip",
                 "gradus.jl_amd/csrc/kernels_tu.hip",
                 "gradus.jl_amd/csrc/gradus_mi355x.hip",
                 "include/gradus_mi355x.h"):

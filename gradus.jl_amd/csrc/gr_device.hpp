@@ -2562,8 +2562,9 @@ struct Cold {
     double* image;            // device
     gr_point* points;         // device
     PfDev pf;
-    // longest-first scheduling of 8x8 tiles: `tile_perm` (may be null) maps queue order -> tile;
-    // `tile_cost` (may be null) receives the step count of one representative ray per tile (the lane kernel of a tabulated
+    // the order of the pixel tiles: `tile_perm` (may be null) maps queue order -> tile -- longest first, learned from the previous
+    // render of the same plane (lpt_prepare), or live tiles first and decided tiles last, built ahead of this launch on its own
+    // stream (gr_tile_order.hpp); `tile_cost` (may be null) receives the step count of one representative ray per tile (the lane kernel of a tabulated
     // metric: the wave's lifetime in 160 ns units, which its step count does not predict -- gr_kernels.hpp) so
     // the host can build the permutation for the next render of the same plane
     const uint32_t* tile_perm;
@@ -2756,17 +2757,21 @@ GR_DEV int64_t idx_div(const Cold& p, int64_t a, int64_t b)
 // `swizzle` = log2 of the tile's ROWS (consecutive pixels of a column, i.e. consecutive doubles of the image): 3 = 8 x 8
 // tiles, 4 = 16 rows x 4 columns -- a wave's stores are then four whole 128-byte lines instead of eight half lines
 // (gr_ctx_set "tile_rows").  0 = no tiling.
-GR_DEV int64_t tile_swizzle(const Cold& p, int64_t j)
+// the local ray index of lane `lane` of tile `tile` (tiles count down the columns of tiles, then across)
+GR_DEV int64_t tile_lane_index(const Cold& p, int64_t tile, int lane)
 {
-    if (!p.swizzle) return j;
     const int tr = p.swizzle, tc = 6 - tr;
     const int64_t H = p.plane.height;
-    int64_t tile = j >> 6;
-    if (p.tile_perm) tile = p.tile_perm[tile];
-    const int lane = (int)(j & 63);
     const int64_t tiles_per_col = H >> tr;
     const int64_t tx = idx_div(p, tile, tiles_per_col), ty = tile - tx * tiles_per_col;
     return ((tx << tc) + (lane >> tr)) * H + (ty << tr) + (lane & ((1 << tr) - 1));
+}
+GR_DEV int64_t tile_swizzle(const Cold& p, int64_t j)
+{
+    if (!p.swizzle) return j;
+    int64_t tile = j >> 6;
+    if (p.tile_perm) tile = p.tile_perm[tile];
+    return tile_lane_index(p, tile, (int)(j & 63));
 }
 
 GR_DEV int64_t range_map(const Cold& p, int64_t j)
@@ -3500,6 +3505,18 @@ struct Ray {
         }
         const real reach = GR_FMA(m.radial_speed_bound(r_min, E, L), (real)p.cfg.lambda1 - (real)p.cfg.lambda0, x[1]);
         return reach * (1.0 + 1e-6) < (real)p.cfg.r_outer ? decided : 0;
+    }
+
+    // init()'s start decision alone, for the live-first tile order (k_tile_classify, gr_tile_order.hpp): true exactly where init()
+    // returns true for local ray jl -- the same constrained_u0, the same gate, the same start_decided, so every switch of the
+    // culls is honoured; a ray left to the defer cull (2) is traced.  Fills x and v and nothing else of the ray.
+    GR_DEV bool decided_at_start(const Metric& m, const Params& p, int64_t jl)
+    {
+        constrained_u0(m, p, jl, x, v);
+        if constexpr (kEscapeCull) {
+            if (x[1] > (real)p.r_cull_start) return start_decided(m, p) == 1;
+        }
+        return false;
     }
 
     // reinit! + auto_dt_reset! (tracing.jl:234-243; App. A.4).  Returns true when the ray is decided without a step (the start

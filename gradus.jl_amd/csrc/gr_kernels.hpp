@@ -5,6 +5,7 @@
 
 #include "gr_device.hpp"
 #include "gr_stats_fold.hpp"
+#include "gr_tile_order.hpp"
 #include <type_traits>
 
 namespace GR_NS {
@@ -456,6 +457,46 @@ __global__ void __launch_bounds__(64) k_trace_path(const Params p, double* path,
     save();
     n_rows[j] = (unsigned long long)n;
 }
+
+// ---- the live-first tile order's flags (gr_tile_order.hpp): kClassLanes neighbouring threads per tile, one corner ray each;
+// flags[tile] = 1 where Ray::init would decide all of them at the start.  Reads the launch's own Params and cold block (its
+// tile_perm is not followed: the flags are per TILE).  The fp64 kernels of a metric and disc with the start cull only.
+#if !defined(GR_REAL_IS_FLOAT) && !defined(GR_REAL_IS_TAN2)
+template <class Metric, int DISC>
+__global__ void __launch_bounds__(256) k_tile_classify(const Params p, uint8_t* flags, int64_t tiles)
+{
+    static_assert(Ray<Metric, DISC>::kEscapeCull, "no start decision to classify by");
+    constexpr int K = gr_order::kClassLanes;
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t tile = g / K;
+    const int k = (int)(g % K);
+    bool decided = false;
+    if (tile < tiles) {
+        Metric m;
+        m.load(p.cfg);
+        const Cold& cd = cold_of(p);
+        Ray<Metric, DISC> ray;
+        decided = ray.decided_at_start(m, p, tile_lane_index(cd, tile, gr_order::class_lane(cd.swizzle, k)));
+    }
+    // every lane of the wave is here: the tile's K lanes are neighbours inside one wave (256 and 64 are multiples of K)
+    const unsigned long long all = __ballot(decided);
+    const int first = (int)(threadIdx.x & 63u) & ~(K - 1);
+    if (tile < tiles && k == 0) flags[tile] = ((all >> first) & ((1ull << K) - 1ull)) == ((1ull << K) - 1ull) ? 1 : 0;
+}
+
+template <class Metric>
+hipError_t launch_classify_metric(const Params& p, uint8_t* flags, int64_t tiles, hipStream_t stream)
+{
+    if constexpr (Ray<Metric, GR_DISC_THIN>::kEscapeCull) {
+        if (p.cfg.disc_id == GR_DISC_THIN && tiles > 0 && tiles * gr_order::kClassLanes <= (int64_t)0x7fffffff) {
+            const int64_t grid = (tiles * gr_order::kClassLanes + 255) / 256;
+            hipLaunchKernelGGL((k_tile_classify<Metric, GR_DISC_THIN>), dim3((unsigned)grid), dim3(256), 0, stream, p, flags, tiles);
+            return hipGetLastError();
+        }
+    }
+    return hipErrorInvalidValue;      // no such kernel: the host unit asks only where the start cull is on (launch_trace)
+}
+#endif
 
 // ---- apply(pf, points) ----
 template <class Metric>

@@ -27,6 +27,7 @@
 #define GR_NS gr
 #include "gr_device.hpp"
 #include "gr_stats_fold.hpp"
+#include "gr_tile_order.hpp"
 #include "gr_mesh_grid.hpp"
 #include "gr_lagbin.hpp"
 #include "gr_tfint.hpp"
@@ -42,7 +43,8 @@ using namespace gr;
     hipError_t grt_launch_trace_m##ID(int, int, int, int, unsigned long long*, const void*, hipStream_t);              \
     hipError_t grt1_launch_trace_m##ID(int, int, int, int, unsigned long long*, const void*, hipStream_t);             \
     hipError_t gr64_launch_path_m##ID(const void*, double*, int64_t, unsigned long long*, hipStream_t);                \
-    hipError_t gr64_launch_apply_m##ID(const void*, const gr_point*, double, double*, hipStream_t);
+    hipError_t gr64_launch_apply_m##ID(const void*, const gr_point*, double, double*, hipStream_t);                     \
+    hipError_t gr64_launch_classify_m##ID(const void*, uint8_t*, int64_t, hipStream_t);
 GR_DECLARE_METRIC(0) GR_DECLARE_METRIC(1) GR_DECLARE_METRIC(2) GR_DECLARE_METRIC(3) GR_DECLARE_METRIC(4) GR_DECLARE_METRIC(5)
 GR_DECLARE_METRIC(6) GR_DECLARE_METRIC(7) GR_DECLARE_METRIC(8) GR_DECLARE_METRIC(9) GR_DECLARE_METRIC(10)
 #undef GR_DECLARE_METRIC
@@ -53,6 +55,7 @@ hipError_t grt_launch_trace_m11(int, int, int, int, unsigned long long*, const v
 hipError_t grt1_launch_trace_m11(int, int, int, int, unsigned long long*, const void*, hipStream_t);
 hipError_t gr64_launch_path_m11(const void*, double*, int64_t, unsigned long long*, hipStream_t);
 hipError_t gr64_launch_apply_m11(const void*, const gr_point*, double, double*, hipStream_t);
+hipError_t gr64_launch_classify_m11(const void*, uint8_t*, int64_t, hipStream_t);
 static_assert(GR_METRIC_NOZ == 10 && GR_METRIC_TABULATED == 11, "one kernel object per metric id 0..11: extend the tables below with the catalogue");
 
 namespace {
@@ -66,6 +69,7 @@ struct LaunchKnobs {
 typedef hipError_t (*trace_fn)(int, int, int, int, unsigned long long*, const void*, hipStream_t);
 typedef hipError_t (*path_fn)(const void*, double*, int64_t, unsigned long long*, hipStream_t);
 typedef hipError_t (*apply_fn)(const void*, const gr_point*, double, double*, hipStream_t);
+typedef hipError_t (*classify_fn)(const void*, uint8_t*, int64_t, hipStream_t);
 #define GR_ROW(F, LAST) { F##0, F##1, F##2, F##3, F##4, F##5, F##6, F##7, F##8, F##9, F##10, LAST }
 const trace_fn kTrace64[12] = GR_ROW(gr64_launch_trace_m, gr64_launch_trace_m11);
 const trace_fn kTrace32[12] = GR_ROW(gr32_launch_trace_m, gr32_launch_trace_m11);
@@ -73,6 +77,7 @@ const trace_fn kTraceTan[12] = GR_ROW(grt_launch_trace_m, grt_launch_trace_m11);
 const trace_fn kTraceTan1[12] = GR_ROW(grt1_launch_trace_m, grt1_launch_trace_m11);   // the same with a PAIR of lanes per ray (kernels_tu.hip)
 const path_fn kPath64[12] = GR_ROW(gr64_launch_path_m, gr64_launch_path_m11);
 const apply_fn kApply64[12] = GR_ROW(gr64_launch_apply_m, gr64_launch_apply_m11);
+const classify_fn kClassify64[12] = GR_ROW(gr64_launch_classify_m, gr64_launch_classify_m11);      // the live-first tile order's flags (gr_tile_order.hpp)
 #undef GR_ROW
 // Metric::kEscapeRadiusM per metric id, in units of params[0] (escape_cull_radius)
 #define GR_ESC(ID) MetricOf<ID>::type::kEscapeRadiusM
@@ -182,6 +187,15 @@ struct gr_ctx {
     int64_t lpt_tiles = 0, lpt_cap = 0;
     bool lpt_have_perm = false, lpt_cost_pending = false;
     hipEvent_t ev_cost = nullptr;
+    // live-first tile order (gr_tile_order.hpp): a ring of permutations (live_cap + 1 words each: the live count behind the tiles)
+    // and of flag blocks (live_cap bytes each), one per in-flight launch like the cold blocks, written and read under stream order
+    int64_t live_first = 1;                // 0 off, 1 auto (launch_trace), 2 always (tests)
+    uint32_t* d_live_perm = nullptr;
+    uint8_t* d_live_flags = nullptr;
+    int64_t live_cap = 0;                  // tiles per slot, a multiple of 8
+    int live_next = 0;
+    const uint32_t* live_last = nullptr;   // the permutation of the last trace launch (null: it kept its order) and its tiles
+    int64_t live_last_tiles = 0;
     // The staged tables (plunging table, disc profile, chart) are single ctx-owned buffers.  A launch that reads
     // them records `ev_tables` on its stream; the next staging on a DIFFERENT stream first waits for that event,
     // so a table is never overwritten under a kernel that is still reading it (launches without tables -- Kerr
@@ -424,9 +438,12 @@ int32_t lpt_prepare(gr_ctx* ctx, const Params& p, Cold& cold, hipStream_t stream
     const bool tab = p.cfg.metric_id == GR_METRIC_TABULATED;
     if (!ctx->lpt || ctx->lpt_suspend || (kern != 1 && !ctx->lpt_lane && !tab) || !cold.swizzle || cold.src_mode != 0) return GR_OK;
     const int64_t tiles = p.n >> 6;
-    // Measured on MI355X: longest-first pays when a launch is only a few tiles per
-    // resident wave deep (the 1/8 shard of a 2048² image: 4.0 -> 3.7 ms on the rank holding the
-    // α≈0 columns, whose rays take up to 430 steps) and costs 2-4 % on deep launches.  lpt = 2 forces it.
+    // Measured on MI355X before the miss culls (DESIGN_measurements.md §M14): longest-first paid when a launch was only a few
+    // tiles per resident wave deep (the 1/8 shard of a 2048² image: 4.0 -> 3.7 ms on the rank holding the α≈0 columns, whose
+    // rays take up to 430 steps) and cost 2-4 % on deep launches (2048²: 17.3 -> 17.8 ms).  Those launches are four times
+    // shorter now and the thresholds below have not been measured again; lpt = 2 forces it.  The order is learned from the
+    // previous render of the SAME (config, plane, range) with host synchronisations, so it serves repeated renders only; a
+    // launch it leaves alone may get the live-first order made on the device from its own inputs (launch_trace).
     const int64_t resident_waves = (int64_t)ctx->n_cu * 8;
     if (tiles < resident_waves) return GR_OK;
     if (ctx->lpt == 1 && tiles >= (tab ? 24 : 6) * resident_waves) return GR_OK;
@@ -756,6 +773,49 @@ __global__ void __launch_bounds__(64) k_stats_fold(unsigned long long* part, uns
     for (int i = t; i < gr_fold::kStatWords; i += 64) part[i] = 0;
 }
 
+// The live-first tile order (gr_tile_order.hpp): the stable partition of the tiles by their flags.  Workgroup b places the tiles
+// [1024 b, 1024 b + 1024), one per thread.  It counts for itself how many flags are set before its tiles and in all -- every
+// workgroup reads the whole flag block, 64 KB for the 2048² bench render, eight bytes per load -- so no workgroup waits for
+// another and nothing is placed by an atomic: the order is the same at every launch.  perm[tiles] receives the number of live
+// tiles (gr_debug_tile_order).  (One workgroup of 1024 threads with 64 tiles each took 42 µs: 65 536 single-word stores to
+// 65 536 cache lines from one CU.)
+__global__ void __launch_bounds__(gr_order::kPartitionThreads) k_tile_partition(const uint8_t* flags, int64_t tiles, uint32_t* perm)
+{
+    constexpr int T = gr_order::kPartitionThreads, W = T / 64;
+    __shared__ uint32_t s_before[W], s_total[W], s_wave[W];
+    const int t = (int)threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t base = (int64_t)blockIdx.x * T;          // a multiple of 8: a word of eight flags lies before it or behind it
+    uint32_t before = 0, total = 0;
+    const int64_t words = tiles >> 3;
+    for (int64_t k = t; k < words; k += T) {
+        const uint32_t c = gr_order::chunk_ones(flags, 8 * k, 8 * k + 8);
+        total += c;
+        if (8 * k < base) before += c;
+    }
+    for (int64_t i = 8 * words + t; i < tiles; i += T) total += gr_order::chunk_ones(flags, i, i + 1);      // (behind every base)
+    // this thread's tile among its wave's
+    const int64_t i = base + t;
+    const bool in = i < tiles;
+    const unsigned long long set = __ballot(in && flags[in ? i : 0] != 0);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        before += (uint32_t)__shfl_xor((int)before, off, 64);
+        total += (uint32_t)__shfl_xor((int)total, off, 64);
+    }
+    if (lane == 0) { s_before[w] = before; s_total[w] = total; s_wave[w] = (uint32_t)__popcll(set); }
+    __syncthreads();
+    uint32_t ones_before = 0, ones_total = 0;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        ones_before += s_before[k] + (k < w ? s_wave[k] : 0u);
+        ones_total += s_total[k];
+    }
+    ones_before += (uint32_t)__popcll(set & ((1ull << lane) - 1ull));
+    const uint32_t zeros_total = (uint32_t)tiles - ones_total;
+    if (in) gr_order::chunk_place(flags, i, i + 1, ones_before, zeros_total, perm);
+    if (blockIdx.x == 0 && t == 0) perm[tiles] = zeros_total;
+}
+
 static bool cull_switched_off(const char* name)
 {
     const char* sw = std::getenv(name);
@@ -798,10 +858,9 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
         const int32_t trc = stage_disc_table(ctx, p, stream);
         if (trc != GR_OK) return trc;
     }
-    // stage the cold block into the next ring slot (stream-ordered before the kernel)
+    // the cold block goes into the next ring slot (staged below, once the tile order is settled: stream-ordered before the kernel)
     Cold* slot = ctx->d_cold + ctx->cold_next;
     ctx->cold_next = (ctx->cold_next + 1) % ctx->queue_slots;
-    GR_HIP(hipMemcpyAsync(slot, &cold, sizeof(Cold), hipMemcpyHostToDevice, stream));
     p.cold = slot;
     // (fp32 line profile, 4096² rays: 21.2 ms at 32 against 22.3 at 16 and 24.2 at 8; fp64: 50.8 either way -- profiles/r5n_c5f32_knobs.log)
     p.refill_threshold = (int32_t)(ctx->refill_threshold ? ctx->refill_threshold : (ctx->precision == 32 ? 32 : 16));
@@ -838,6 +897,52 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
         p.r_pass = cull_switched_off("GRADUS_MI355X_PASS_CULL") ? HUGE_VAL : pass_cull_radius(p.r_cull_start);
         p.entry_cull = cull_switched_off("GRADUS_MI355X_ENTRY_CULL") ? 0 : 1;
         p.defer_cull = cull_switched_off("GRADUS_MI355X_DEFER_CULL") ? 0 : 1;
+    }
+    // LIVE-FIRST TILE ORDER (gr_tile_order.hpp): an image launch of the one-ray-per-lane kernel under the start cull
+    // takes its live tiles first and the tiles decided at the start last.  The order is made on the device from this launch's own
+    // parameters by two small kernels ahead of the trace kernel on its stream -- no host synchronisation, no host copy -- so it
+    // serves a configuration that changes from call to call, which the learned order (lpt_prepare) does not; where that one is
+    // in use or being recorded it stays.  gr_ctx_set "live_first": 0 = off, 1 [default] = launches of at
+    // least as many tiles as the device holds waves (below that every wave is resident at once and the order decides nothing)
+    // and at most 2^20, 2 = any size; GRADUS_MI355X_LIVE_FIRST=0 | 1 | 2 in the environment, read at every launch
+    // like the culls' switches, takes the knob's place (A/B of one build through a program that does not set the knob).
+    const int64_t tiles = p.n >> 6;
+    uint8_t* live_flags = nullptr;
+    ctx->live_last = nullptr;
+    ctx->live_last_tiles = 0;
+    int64_t live_mode = ctx->live_first;
+    if (const char* sw = std::getenv("GRADUS_MI355X_LIVE_FIRST"))
+        if ((sw[0] == '0' || sw[0] == '1' || sw[0] == '2') && sw[1] == 0) live_mode = sw[0] - '0';
+    if (live_mode && kern_sel == 0 && cold.src_mode == 0 && cold.swizzle && p.r_cull_start < HUGE_VAL && !cold.tile_perm && !lpt_record
+        && tiles > 0 && tiles < ((int64_t)1 << 29)
+        && (live_mode == 2 || (tiles >= (int64_t)ctx->n_cu * 8 && tiles <= ((int64_t)1 << 20)))) {
+        if (ctx->live_cap < tiles) {
+            // (a smaller ring may still be read by launches in flight: hipFree waits for the device)
+            if (ctx->d_live_perm) (void)hipFree(ctx->d_live_perm);
+            if (ctx->d_live_flags) (void)hipFree(ctx->d_live_flags);
+            ctx->d_live_perm = nullptr;
+            ctx->d_live_flags = nullptr;
+            ctx->live_cap = 0;
+            const int64_t cap = (tiles + 7) & ~(int64_t)7;
+            GR_HIP(hipMalloc((void**)&ctx->d_live_perm, sizeof(uint32_t) * (size_t)(cap + 1) * (size_t)ctx->queue_slots));
+            GR_HIP(hipMalloc((void**)&ctx->d_live_flags, (size_t)cap * (size_t)ctx->queue_slots));
+            ctx->live_cap = cap;
+        }
+        uint32_t* const perm = ctx->d_live_perm + (size_t)ctx->live_next * (size_t)(ctx->live_cap + 1);
+        live_flags = ctx->d_live_flags + (size_t)ctx->live_next * (size_t)ctx->live_cap;
+        ctx->live_next = (ctx->live_next + 1) % ctx->queue_slots;
+        cold.tile_perm = perm;
+        ctx->live_last = perm;
+        ctx->live_last_tiles = tiles;
+    }
+    GR_HIP(hipMemcpyAsync(slot, &cold, sizeof(Cold), hipMemcpyHostToDevice, stream));
+    if (live_flags) {
+        const hipError_t ce = kClassify64[p.cfg.metric_id](&p, live_flags, tiles, stream);
+        if (ce != hipSuccess) return fail(GR_ERR_HIP, std::string("tile classification launch: ") + hipGetErrorString(ce));
+        hipLaunchKernelGGL(k_tile_partition, dim3((unsigned)((tiles + gr_order::kPartitionThreads - 1) / gr_order::kPartitionThreads)),
+                           dim3(gr_order::kPartitionThreads), 0, stream, live_flags, tiles,
+                           const_cast<uint32_t*>(cold.tile_perm));
+        GR_HIP(hipGetLastError());
     }
     LaunchKnobs knobs{ kern_sel, block_sel, ctx->n_cu, (int)ctx->waves_per_simd,
                        ctx->d_queue + ctx->queue_next };
@@ -976,6 +1081,26 @@ int32_t gr_abi_version(void) { return GR_ABI_VERSION; }
 void gr_debug_set_timeline(void* device_buffer) { g_debug_timeline = (unsigned long long*)device_buffer; }
 #endif
 
+// For the tests (not in the header): the live-first tile order of the context's last trace launch as the device built it
+// (gr_tile_order.hpp).  *tiles = 0: that launch kept its order.  Else min(*tiles, cap) entries of the permutation (queue position
+// -> tile) go to `perm` and the number of tiles in the live class to *live.  Waits for the device.
+int32_t gr_debug_tile_order(gr_ctx* c, uint32_t* perm, int64_t cap, int64_t* tiles, int64_t* live)
+{
+    if (!c || !tiles || !live) return fail(GR_ERR_INVALID_ARGUMENT, "ctx/tiles/live is null");
+    *tiles = 0;
+    *live = 0;
+    if (!c->live_last) return GR_OK;
+    GR_HIP(hipSetDevice(c->device));
+    GR_HIP(hipDeviceSynchronize());
+    uint32_t n_live = 0;
+    GR_HIP(hipMemcpy(&n_live, c->live_last + c->live_last_tiles, sizeof n_live, hipMemcpyDeviceToHost));
+    const int64_t n = cap < c->live_last_tiles ? cap : c->live_last_tiles;
+    if (perm && n > 0) GR_HIP(hipMemcpy(perm, c->live_last, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    *tiles = c->live_last_tiles;
+    *live = (int64_t)n_live;
+    return GR_OK;
+}
+
 const char* gr_last_error(void) { return g_last_error.c_str(); }
 
 int32_t gr_ctx_create(int32_t device, gr_ctx** out)
@@ -1046,6 +1171,8 @@ int32_t gr_ctx_destroy(gr_ctx* c)
     if (c->d_sky_table) (void)hipFree(c->d_sky_table);
     if (c->d_tile_cost) (void)hipFree(c->d_tile_cost);
     if (c->d_tile_perm) (void)hipFree(c->d_tile_perm);
+    if (c->d_live_perm) (void)hipFree(c->d_live_perm);
+    if (c->d_live_flags) (void)hipFree(c->d_live_flags);
     if (c->ev_cost) (void)hipEventDestroy(c->ev_cost);
     if (c->ev_tables) (void)hipEventDestroy(c->ev_tables);
     if (c->d_plunge) (void)hipFree(c->d_plunge);
@@ -1192,6 +1319,9 @@ int32_t gr_ctx_set(gr_ctx* c, const char* key, int64_t value)
         if (value < 0 || value > 2) return fail(GR_ERR_INVALID_ARGUMENT, "lpt must be 0 (off), 1 (auto) or 2 (always)");
         c->lpt = value;
         c->lpt_key.clear();
+    } else if (k == "live_first") {
+        if (value < 0 || value > 2) return fail(GR_ERR_INVALID_ARGUMENT, "live_first must be 0 (off), 1 (auto) or 2 (always)");
+        c->live_first = value;
     } else if (k == "hugepages") {
         c->hugepages = value ? 1 : 0;
     } else if (k == "tangent_norm") {

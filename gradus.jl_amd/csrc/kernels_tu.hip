@@ -13,7 +13,7 @@
 //
 // Exports (plain signatures: the host unit, gradus_mi355x.hip, passes its gr::Params by address -- gr32::Params has the
 // same layout, its fields are double / integer / pointers only):
-//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>
+//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>
 #ifndef GR_TU_METRIC
 #error "compile with -DGR_TU_METRIC=<metric id>"
 #endif
@@ -80,5 +80,11 @@ hipError_t GR_TU_NAME(_launch_path_m)(const void* params, double* d_path, int64_
 hipError_t GR_TU_NAME(_launch_apply_m)(const void* params, const gr_point* pts, double max_time, double* out, hipStream_t stream)
 {
     return GR_NS::launch_apply_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), pts, max_time, out, stream);
+}
+
+// the live-first tile order's flags for the launch `params` describes (gr_tile_order.hpp); an error for a metric without the start cull
+hipError_t GR_TU_NAME(_launch_classify_m)(const void* params, uint8_t* flags, int64_t tiles, hipStream_t stream)
+{
+    return GR_NS::launch_classify_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), flags, tiles, stream);
 }
 #endif

@@ -291,6 +291,11 @@ int32_t gr_ctx_destroy(gr_ctx* ctx);
  * ("xcd_spread", 1 [default] = rays in caller order on the one-ray-per-lane kernel are dealt to the 8 XCDs by the digit sum of
  * their chunk index instead of round-robin -- a periodic pattern in the rays, such as the polar-axis column of a 1024-wide grid of
  * impact parameters, otherwise lands on one or two XCDs (38 against 21 ms) --, 0 = chunk b to workgroup b);
+ * ("live_first", the order of an image launch's pixel tiles on the one-ray-per-lane kernel where rays are decided at their start
+ * (one thin disc around the Kerr metric, misses ignored): 1 [default] = launches of at least as many tiles as the device holds
+ * waves take the tiles with a corner ray that is traced first and the tiles decided at the start last -- the order is built on
+ * the device ahead of each launch from that launch's own parameters --, 2 = launches of any size, 0 = tile order; same pixels
+ * and statistics either way; GRADUS_MI355X_LIVE_FIRST=0, 1 or 2 in the environment takes the knob's place);
  * ("sky_deal", 1 [default] = gr_corona_trace deals the rays of a sky source to the waves by what they will cost -- a counting sort
  * by a step count predicted from each ray's initial position and direction (its passage round the polar axis), the longest class
  * first, traced by the one-ray-per-lane kernel in 256-thread workgroups: a wave's rays take nearly the same number of steps and the

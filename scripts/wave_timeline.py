@@ -102,6 +102,13 @@ print(f"last wave starts at {st.max():.2f} ms, last wave ends at {en.max():.2f} 
 edges = np.linspace(0, en.max(), 21)
 res = [(int(((st < hi) & (en > lo)).sum())) for lo, hi in zip(edges[:-1], edges[1:])]
 print("waves resident per 5 % slice of the launch:", res)
+alive = steps > 0          # a dead wave takes no step: every ray of its tile was decided at the start
+if alive.any() and not alive.all():
+    res_dead = [(int(((st < hi) & (en > lo) & ~alive).sum())) for lo, hi in zip(edges[:-1], edges[1:])]
+    print(f"live waves {int(alive.sum())}, dead waves {int((~alive).sum())} (lifetime µs: median {np.median(life[~alive]) * 1e3:.1f} mean {life[~alive].mean() * 1e3:.1f}); "
+          f"first live wave starts at {st[alive].min():.3f} ms, last live wave starts at {st[alive].max():.3f} ms = {en.max() - st[alive].max():.3f} ms before the launch's end; "
+          f"last live wave ends at {en[alive].max():.3f} ms")
+    print("dead waves resident per 5 % slice of the launch:", res_dead)
 late = np.argsort(en)[-8:]
 print("the waves that end last (start, end, steps of longest ray):", [(round(float(st[i]), 2), round(float(en[i]), 2), int(steps[i])) for i in late])
 if os.environ.get("WT_TAB"):
