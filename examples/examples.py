@@ -179,3 +179,31 @@ for name, d in (("WarpedThinDisc", G.WarpedThinDisc(lambda ρ: 1.5 * math.sin(ρ
     _, _, img = G.rendergeodesics(m, x, d, 2000.0, image_width=600, image_height=400, alpha_lims=(-45, 45), beta_lims=(-30, 30),
                                   pf=CPF.redshift(m, x) @ CPF.filter_intersected(), ensemble=ens)
     print(f"geometry {name}: {np.isfinite(img).sum()} pixels, g in [{np.nanmin(img):.3f}, {np.nanmax(img):.3f}]")
+
+# ## Adaptive tracing: the illumination pattern of the disc under an off-axis source
+m = G.KerrMetric(1.0, 0.998)
+d = G.ThinDisc(0.0, float("inf"))
+corona = G.RingCorona(r=10.0, h=4.0)
+sky = G.AdaptiveSky(m, corona, d, ensemble=ens)
+_, dt = timed(lambda: G.trace_initial(sky))
+print(f"adaptive sky: {len(sky.grid)} cells after trace_initial ({dt:.2f} s)")
+
+
+def refine_distant(sky, i1, i2):
+    """refine where the radii of two neighbouring cells differ by more than 10 %; leave pairs that both miss the disc alone"""
+    r1, r2 = sky.values["r"][i1], sky.values["r"][i2]
+    both_miss = np.isnan(r1) & np.isnan(r2)
+    with np.errstate(invalid="ignore"):
+        close = np.abs(r1 - r2) <= 0.1 * np.maximum(np.abs(r1), np.abs(r2))
+    return ~both_miss & ~close
+
+
+for i in range(3):
+    _, dt = timed(lambda: G.trace_step(sky, check_refine=refine_distant))
+    print(f"adaptive sky: trace_step {i + 1} traced {sky.tracer['launches'][-1][0]} cells in one launch, {len(sky.grid)} cells ({dt:.2f} s)")
+ϕ_sky, θ_sky, dense = G.fill_sky_values(sky, 256)
+print(f"fill_sky_values: {np.isfinite(dense['r']).sum()} of {dense.size} sky points land on the disc, log10 r in "
+      f"[{np.nanmin(np.log10(dense['r'])):.2f}, {np.nanmax(np.log10(dense['r'])):.2f}]")
+r_bins, ϕ_bins = np.geomspace(m.isco(), 100.0, 100), np.linspace(0.0, 2 * math.pi, 100)
+ε = G.bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky)
+print(f"bin_emissivity_grid: {np.count_nonzero(ε)} of {ε.size} (r, ϕ) bins lit, ε at r ≈ 10 between {ε[50][ε[50] > 0].min():.3g} and {ε[50].max():.3g}")

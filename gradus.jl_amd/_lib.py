@@ -303,6 +303,18 @@ class gr_ringset(C.Structure):
     ]
 
 
+class gr_skycells(C.Structure):
+    """The cells of a source's adaptive sky (gr_sky_cells): the source's position and sky frame, per cell cos θ and ϕ"""
+
+    _fields_ = [
+        ("x_src", C.c_double * 4),
+        ("Mx", C.c_double * 16),
+        ("cos_theta", C.c_void_p),
+        ("phi", C.c_void_p),
+        ("n", C.c_int64),
+    ]
+
+
 class gr_stats(C.Structure):
     _fields_ = [
         ("rays", C.c_int64),
@@ -389,6 +401,9 @@ EXPORTS = [
     "gr_tf_lagtransfer_td",
     "gr_ring_rays",
     "gr_ring_arms",
+    "gr_sky_cells",
+    "gr_sky_cells_device",
+    "gr_sky_cells_multi",
     "gr_render_endpoints_multi",
     "gr_trace_endpoints_multi",
     "gr_rayset_endpoints_multi",
@@ -466,7 +481,11 @@ def load():
     L.gr_tf_lagtransfer_td.argtypes = [vp, tsp, C.POINTER(gr_tfprofile), tqp, vp, i64, vp, i64, i64, i64, C.c_double, vp, vp]
     L.gr_ring_rays.argtypes = [vp, cfgp, C.POINTER(gr_ringset), pfp, i64, vp, vp, vp, vp, stp]
     L.gr_ring_arms.argtypes = [vp, cfgp, C.POINTER(gr_ringset), pfp, vp, vp, stp]
+    scp = C.POINTER(gr_skycells)
+    L.gr_sky_cells.argtypes = [vp, cfgp, scp, pfp, vp, stp]
+    L.gr_sky_cells_device.argtypes = [vp, cfgp, scp, pfp, vp, vp, vp]
     ctxa = C.POINTER(vp)
+    L.gr_sky_cells_multi.argtypes = [ctxa, i32, cfgp, scp, pfp, vp, vp]
     L.gr_render_endpoints_multi.argtypes = [ctxa, i32, cfgp, plp, i64, vp, vp]
     L.gr_trace_endpoints_multi.argtypes = [ctxa, i32, cfgp, vp, i64, vp, i64, vp, vp]
     L.gr_rayset_endpoints_multi.argtypes = [ctxa, i32, cfgp, rsp, vp, vp]

@@ -2551,7 +2551,8 @@ struct PfDev {
 struct Cold {
     int32_t src_mode;         // 0 = image plane, 1 = (x, v) arrays, 2 = impact-parameter arrays (3 = a source's sky, gr_rayset.sky_*: on the host side only --
                               // launch_trace has a small kernel write the sky's velocities and hands the trace kernels src_mode 1)
-    int32_t out_mode;         // 0 = fused point function image, 1 = endpoint records, 2 = binned line profile, 3 = (g, ρ) pairs, 4 = (g, ρ, t, status), 5 = the same with ∂/∂α, ∂/∂β (tangent build only)
+    int32_t out_mode;         // 0 = fused point function image, 1 = endpoint records, 2 = binned line profile, 3 = (g, ρ) pairs, 4 = (g, ρ, t, status), 5 = the same with ∂/∂α, ∂/∂β (tangent build only),
+                              // 6 = a sky cell's (t, r, ϕ, g, J, status) with J from ∂/∂θ, ∂/∂ϕ of the source's sky angles (tangent build with GR_SKYCELL only)
     int32_t swizzle;          // log2 rows of the pixel tile a wave owns: 3 = 8 x 8, 4 = 16 x 4 (0 = none)
     int32_t idx32;            // 1 = every ray / pixel index fits 31 bits: 32-bit divisions in the index maps
     gr_plane plane;
@@ -2604,7 +2605,14 @@ struct Cold {
     int32_t sky_sampler, sky_both, sky_generator, sky_reserved;
     double sky_resolution;
     const double* sky_i;      // device, n (sky_generator 2) or null
+    // src_mode 1, the sky-cell instantiation of the tangent build (GR_SKYCELL, kernels_tu.hip: the branches that read this are
+    // compiled into kernels of their own, the other tangent kernels keep their registers): the rays are the cells of a source's sky
+    // (gr_sky_cells) and each brings GR_SKYCELL_SEED doubles -- ∂v/∂θ[4], ∂v/∂ϕ[4] of its unconstrained velocity, then sin θ -- or
+    // null: rays without a seed.  (Last: nothing before it moves.)
+    const double* v_tan;
 };
+constexpr int GR_SKYCELL_SEED = 9;     // doubles per ray behind Cold::v_tan
+constexpr int GR_SKYCELL_ROW = 6;      // doubles per ray of out_mode 6: (t, r, ϕ, g, J, status), the reference's CoronaGridValues
 
 // the error norm's scaled residuals in single precision: the fp64 device kernels only (see Ray::step)
 #if !defined(GR_REAL_IS_FLOAT) && !defined(GR_REAL_IS_TAN2)
@@ -3427,6 +3435,21 @@ struct Ray {
             const double* vs = p.v + jl * 4;
 #pragma unroll
             for (int q = 0; q < 4; ++q) { x0[q] = xs[q]; v0[q] = vs[q]; }
+#if defined(GR_REAL_IS_TAN2) && defined(GR_SKYCELL)
+            // the cells of a source's sky: the directions of this build are ∂/∂θ and ∂/∂ϕ of the sky angles (GR_TAN_W = 1: this
+            // lane's one), seeded on the velocity -- the position carries none, and constrained_u0 takes them through v^t
+            if (p.v_tan) {
+                const double* ts = p.v_tan + jl * GR_SKYCELL_SEED;
+#if GR_TAN_W == 1
+                const double* tm = ts + 4 * tan_dir();
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v0[q].a = tm[q];
+#else
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { v0[q].a = ts[q]; v0[q].b = ts[4 + q]; }
+#endif
+            }
+#endif
         }
     }
 
@@ -4468,6 +4491,37 @@ struct Ray {
                 g = redshift_pf(m, p, cd, lds, x0, v0, x, v);
             }
 #ifdef GR_REAL_IS_TAN2
+#ifdef GR_SKYCELL
+            if (cd.out_mode == 6) {
+                // a sky cell's row (t, r, ϕ, g, J, status): CoronaGridValues of _emissivity_jacobian! (adaptive-sample.jl:43-81),
+                // J = |∂(r, ϕ)/∂(θ, ϕ_s)| / sin θ read off the tangents, ϕ unwrapped as integrated; NaN but for the status
+                // where the ray does not hit (adaptive-sample.jl:56-58); the status as _tmp_status_to_float codes it
+                double det;
+#if GR_TAN_W == 1 && !defined(GR_HOST_HARNESS)
+                // a pair of lanes per ray, one column of the Jacobian each: the partner's column crosses the pair (both lanes
+                // are here together: they hold the same values and took the same branches)
+                const double r_o = __shfl_xor(rho.a, 1, 64), p_o = __shfl_xor(x[3].a, 1, 64);
+                det = rho.a * p_o - r_o * x[3].a;          // the even lane's: its own column is ∂/∂θ
+                if (tan_dir() != 0) return;
+#elif GR_TAN_W == 1
+                det = 0.0;
+#else
+                det = rho.a * x[3].b - rho.b * x[3].a;
+#endif
+                const double nan = __builtin_nan("");
+                const double sin_sky = cd.v_tan ? cd.v_tan[GR_SKYCELL_SEED * j + 8] : 1.0;
+                double* o = cd.lp_pairs + GR_SKYCELL_ROW * j;
+                o[0] = in ? x[0].v : nan;
+                o[1] = in ? rho.v : nan;
+                o[2] = in ? x[3].v : nan;
+                o[3] = in ? g.v : nan;
+                o[4] = in ? ::fabs(det) / sin_sky : nan;
+                o[5] = status == GR_STATUS_INTERSECTED_WITH_GEOMETRY ? 1.0
+                       : status == GR_STATUS_WITHIN_INNER_BOUNDARY  ? -3.0
+                       : status == GR_STATUS_OUT_OF_DOMAIN          ? 7.0
+                                                                    : 0.0;
+            } else
+#endif
             if (cd.out_mode == 5) {
                 // ray summary with tangents: (g, ρ, ∂g/∂α, ∂g/∂β, ∂ρ/∂α, ∂ρ/∂β, t, status) -- what
                 // jacobian_∂αβ_∂gr reads off its dual numbers (precision-solvers.jl:401-451)

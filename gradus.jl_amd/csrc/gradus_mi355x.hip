@@ -42,6 +42,8 @@ using namespace gr;
     hipError_t gr32_launch_trace_m##ID(int, int, int, int, unsigned long long*, const void*, hipStream_t);             \
     hipError_t grt_launch_trace_m##ID(int, int, int, int, unsigned long long*, const void*, hipStream_t);              \
     hipError_t grt1_launch_trace_m##ID(int, int, int, int, unsigned long long*, const void*, hipStream_t);             \
+    hipError_t grts_launch_trace_m##ID(int, int, int, int, unsigned long long*, const void*, hipStream_t);             \
+    hipError_t grts1_launch_trace_m##ID(int, int, int, int, unsigned long long*, const void*, hipStream_t);            \
     hipError_t gr64_launch_path_m##ID(const void*, double*, int64_t, unsigned long long*, hipStream_t);                \
     hipError_t gr64_launch_apply_m##ID(const void*, const gr_point*, double, double*, hipStream_t);                     \
     hipError_t gr64_launch_classify_m##ID(const void*, uint8_t*, int64_t, hipStream_t);
@@ -53,6 +55,8 @@ hipError_t gr64_launch_trace_m11(int, int, int, int, unsigned long long*, const 
 hipError_t gr32_launch_trace_m11(int, int, int, int, unsigned long long*, const void*, hipStream_t);
 hipError_t grt_launch_trace_m11(int, int, int, int, unsigned long long*, const void*, hipStream_t);
 hipError_t grt1_launch_trace_m11(int, int, int, int, unsigned long long*, const void*, hipStream_t);
+hipError_t grts_launch_trace_m11(int, int, int, int, unsigned long long*, const void*, hipStream_t);
+hipError_t grts1_launch_trace_m11(int, int, int, int, unsigned long long*, const void*, hipStream_t);
 hipError_t gr64_launch_path_m11(const void*, double*, int64_t, unsigned long long*, hipStream_t);
 hipError_t gr64_launch_apply_m11(const void*, const gr_point*, double, double*, hipStream_t);
 hipError_t gr64_launch_classify_m11(const void*, uint8_t*, int64_t, hipStream_t);
@@ -75,6 +79,8 @@ const trace_fn kTrace64[12] = GR_ROW(gr64_launch_trace_m, gr64_launch_trace_m11)
 const trace_fn kTrace32[12] = GR_ROW(gr32_launch_trace_m, gr32_launch_trace_m11);
 const trace_fn kTraceTan[12] = GR_ROW(grt_launch_trace_m, grt_launch_trace_m11);      // value + ∂/∂α + ∂/∂β (out_mode 5): one lane per ray
 const trace_fn kTraceTan1[12] = GR_ROW(grt1_launch_trace_m, grt1_launch_trace_m11);   // the same with a PAIR of lanes per ray (kernels_tu.hip)
+const trace_fn kTraceSky[12] = GR_ROW(grts_launch_trace_m, grts_launch_trace_m11);     // the same two shapes with the sky-cell branches (out_mode 6,
+const trace_fn kTraceSky1[12] = GR_ROW(grts1_launch_trace_m, grts1_launch_trace_m11);  // gr_sky_cells): instantiations of their own (kernels_tu.hip)
 const path_fn kPath64[12] = GR_ROW(gr64_launch_path_m, gr64_launch_path_m11);
 const apply_fn kApply64[12] = GR_ROW(gr64_launch_apply_m, gr64_launch_apply_m11);
 const classify_fn kClassify64[12] = GR_ROW(gr64_launch_classify_m, gr64_launch_classify_m11);      // the live-first tile order's flags (gr_tile_order.hpp)
@@ -590,6 +596,38 @@ __global__ void __launch_bounds__(256) k_sky_scale_g(double* rows, const double*
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) rows[4 * j] *= f[j];
 }
+// The cells of a source's adaptive sky (gr_sky_cells; AdaptiveSky, adaptive-sample.jl:43-81): cell j is the direction
+// (θ = acos(cos θ_j), ϕ_j), v = Mx (1, -k̂) with k̂ = (sin θ cos ϕ, sin θ sin ϕ, cos θ) (sky_angles_to_velocity, samplers.jl:75-97),
+// and next to it the seed of the tangent kernels (Cold::v_tan): ∂v/∂θ = -Mx (0, ∂k̂/∂θ), ∂v/∂ϕ = -Mx (0, ∂k̂/∂ϕ), then sin θ.
+// out: x_src[4], v[n][4], seed[n][GR_SKYCELL_SEED]
+struct SkyCellParams {
+    double x_src[4], Mx[16];
+    const double* cos_theta;   // device, n
+    const double* phi;         // device, n
+    int64_t n;
+};
+__global__ void __launch_bounds__(256) k_skycell_velocities(const SkyCellParams p, double* out)
+{
+    const int64_t jl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (jl == 0)
+        for (int q = 0; q < 4; ++q) out[q] = p.x_src[q];
+    if (jl >= p.n) return;
+    const double ct = p.cos_theta[jl], th = ::acos(ct), ph = p.phi[jl];
+    const double st = ::sin(th), sp = ::sin(ph), cp = ::cos(ph);
+    const double k[3] = { st * cp, st * sp, ct };
+    const double kt[3] = { ct * cp, ct * sp, -st };
+    const double kp[3] = { -st * sp, st * cp, 0.0 };
+    double* v = out + 4 + 4 * jl;
+    double* seed = out + 4 + 4 * p.n + GR_SKYCELL_SEED * jl;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const double* row = p.Mx + 4 * q;
+        v[q] = row[0] - (row[1] * k[0] + row[2] * k[1] + row[3] * k[2]);
+        seed[q] = -(row[1] * kt[0] + row[2] * kt[1] + row[3] * kt[2]);
+        seed[4 + q] = -(row[1] * kp[0] + row[2] * kp[1] + row[3] * kp[2]);
+    }
+    seed[8] = st;
+}
 // The same rays DEALT BY WHAT THEY WILL COST (gr_corona_trace: the order of its rows is free -- min / max and integer bins do not
 // know it).  How many steps a ray takes is known, to a constant per polar angle of emission, BEFORE it is traced: the integrator
 // resolves the ray's passage round the polar axis of the coordinates, and along the flat-space straight line from the source the
@@ -865,7 +903,7 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
     // (fp32 line profile, 4096² rays: 21.2 ms at 32 against 22.3 at 16 and 24.2 at 8; fp64: 50.8 either way -- profiles/r5n_c5f32_knobs.log)
     p.refill_threshold = (int32_t)(ctx->refill_threshold ? ctx->refill_threshold : (ctx->precision == 32 ? 32 : 16));
     // the tangent objects carry the one-ray-per-lane kernel only: settle kernel and block BEFORE anything is sized by them
-    const bool tangent = cold.out_mode == 5;
+    const bool tangent = cold.out_mode == 5 || cold.out_mode == 6;
     if (p.cfg.disc_id == GR_DISC_MESH && (tangent || ctx->precision == 32))
         return fail(GR_ERR_UNSUPPORTED, "a mesh geometry is traced by the fp64 kernels only (not with \"precision\" 32, not by the tangent entry points)");
     // A sky source whose rays were dealt by predicted cost (sky_prepare): a wave's 64 rays take nearly the same number of steps
@@ -952,7 +990,8 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
     // per ray does less work in all (throughput).  A launch whose pairs fit the machine at one wave per SIMD -- 2 n / 64 waves
     // on 4 SIMDs per CU -- cannot keep the SIMDs busy either way and is as long as its longest ray: it takes the pairs.
     const bool pairs = tangent && (ctx->tangent_pairs == 1 || (ctx->tangent_pairs == 2 && 2 * p.n <= (int64_t)ctx->n_cu * 4 * 64));
-    const trace_fn fn = (tangent ? (pairs ? kTraceTan1 : kTraceTan) : ctx->precision == 32 ? kTrace32 : kTrace64)[p.cfg.metric_id];
+    const bool skycell = cold.out_mode == 6;
+    const trace_fn fn = (skycell ? (pairs ? kTraceSky1 : kTraceSky) : tangent ? (pairs ? kTraceTan1 : kTraceTan) : ctx->precision == 32 ? kTrace32 : kTrace64)[p.cfg.metric_id];
     p.tangent_norm = (tangent && ctx->tangent_norm) ? 1 : 0;
 #ifdef GR_WAVE_TIMELINE
     p.queue = g_debug_timeline;      // debug builds: 4 x u64 per wave of a one-ray-per-lane launch (gr_kernels.hpp)
@@ -971,7 +1010,7 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
         p.stats = caller_stats;
     }
     if (stream == ctx->stream) GR_HIP(hipEventRecord(ctx->ev_k, stream));      // host variants: where the kernel ends
-    if (p.disc_table || p.chart_table || cold.pf.n_plunge > 0 || p.cfg.metric_id == GR_METRIC_TABULATED || sky) {
+    if (p.disc_table || p.chart_table || cold.pf.n_plunge > 0 || p.cfg.metric_id == GR_METRIC_TABULATED || sky || cold.v_tan) {
         const int32_t trc = tables_release(ctx, stream);
         if (trc != GR_OK) return trc;
     }
@@ -1783,6 +1822,77 @@ int32_t gr_ray_tangent_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset
     if (!pf || pf->pf_id != GR_PF_REDSHIFT) return fail(GR_ERR_INVALID_ARGUMENT, "needs the redshift point function");
     if ((rc = stage_pf(ctx, cfg, pf, cd.pf, stream)) != GR_OK) return rc;
     cd.out_mode = 5;
+    cd.lp_rmin = 0.0;
+    cd.lp_rmax = INFINITY;
+    cd.lp_pairs = d_out;
+    p.stats = (unsigned long long*)d_stats;
+    return launch_trace(ctx, p, cd, stream);
+}
+
+// ---- the cells of a source's adaptive sky (AdaptiveSky, adaptive-sample.jl:43-81): gr_sky_cells ----
+
+// what every gr_sky_cells* refuses before anything touches the device; `host_angles`: cos_theta / phi can be read here
+static int32_t skycells_check(const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf, bool host_angles)
+{
+    int32_t rc;
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if (!cells) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_cells: cells is null");
+    if (cells->n < 0 || cells->n > (int64_t)INT32_MAX) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_cells: n in 0 ... 2^31 - 1");
+    if (cells->n > 0 && (!cells->cos_theta || !cells->phi)) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_cells: cos_theta / phi is null");
+    if (cfg->disc_id == GR_DISC_NONE) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_cells: the Jacobian is taken where the ray meets the geometry: none given");
+    if (!pf || pf->pf_id != GR_PF_REDSHIFT) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_cells: needs the redshift point function");
+    if (!pf->has_u_src) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_cells: g is the energy ratio against the source's velocity: pf->has_u_src must be 1");
+    if (cfg->metric_id == GR_METRIC_TABULATED) {
+        const double r = cells->x_src[1], t_min = cfg->metric_table[gr_tab::H_RMIN], t_max = cfg->metric_table[gr_tab::H_RMAX];
+        if (!(r >= t_min - 1e-9 * std::fabs(t_min) - 1e-12) || !(r <= t_max + 1e-9 * std::fabs(t_max)))
+            return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_cells: the source at r = " + std::to_string(r) + " lies outside the radial range of the metric table ["
+                                                 + std::to_string(t_min) + ", " + std::to_string(t_max) + "]");
+    }
+    if (host_angles)
+        for (int64_t j = 0; j < cells->n; ++j)
+            if (!(std::fabs(cells->cos_theta[j]) < 1.0))
+                return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_cells: |cos θ| must lie below 1 (cell " + std::to_string(j) + "): J divides by sin θ");
+    return GR_OK;
+}
+
+int32_t gr_sky_cells_device(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf,
+                            double* d_out, gr_stats* d_stats, void* hip_stream)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc;
+    if ((rc = skycells_check(cfg, cells, pf, false)) != GR_OK) return rc;
+    if (cells->n > 0 && !d_out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
+    GR_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int64_t n = cells->n;
+    Params p;
+    Cold cd;
+    std::memset(&p, 0, sizeof p);
+    std::memset(&cd, 0, sizeof cd);
+    p.cfg = *cfg;
+    p.n = n;
+    if ((rc = stage_pf(ctx, cfg, pf, cd.pf, stream)) != GR_OK) return rc;
+    if (n == 0) return GR_OK;
+    // the rays and their seeds go into the context's sky buffer (ordered against earlier launches that read it: sky_prepare)
+    if ((rc = tables_acquire(ctx, stream)) != GR_OK) return rc;
+    if ((rc = ensure((void**)&ctx->d_sky, &ctx->sky_bytes, sizeof(double) * (4 + (size_t)(4 + GR_SKYCELL_SEED) * (size_t)n))) != GR_OK) return rc;
+    SkyCellParams sp;
+    std::memcpy(sp.x_src, cells->x_src, sizeof sp.x_src);
+    std::memcpy(sp.Mx, cells->Mx, sizeof sp.Mx);
+    sp.cos_theta = cells->cos_theta;
+    sp.phi = cells->phi;
+    sp.n = n;
+    hipLaunchKernelGGL(k_skycell_velocities, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sp, ctx->d_sky);
+    GR_HIP(hipGetLastError());
+    cd.src_mode = 1;
+    cd.out_mode = 6;
+    cd.x = ctx->d_sky;
+    cd.x_stride = 0;
+    cd.v = ctx->d_sky + 4;
+    cd.v_tan = ctx->d_sky + 4 + 4 * n;
+    std::memcpy(cd.plane.x_obs, cells->x_src, sizeof cd.plane.x_obs);
+    cd.range = gr_range{ 0, n, n, 1 };
+    cd.swizzle = 0;
     cd.lp_rmin = 0.0;
     cd.lp_rmax = INFINITY;
     cd.lp_pairs = d_out;
@@ -4244,3 +4354,79 @@ int32_t gr_lineprofile_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
 }
 
 }  // extern "C"
+
+// ---- gr_sky_cells: host buffers; one context, or contiguous shares of the cells over several ----
+
+extern "C++" {
+namespace {
+// cells [off, off + cnt) of a host cell set -> the context's input buffer; `dev` receives the device pointers
+int32_t stage_skycells(gr_ctx* c, const gr_skycells* cells, int64_t off, int64_t cnt, gr_skycells& dev)
+{
+    int32_t rc;
+    if ((rc = ensure(&c->d_in, &c->in_bytes, sizeof(double) * 2 * (size_t)cnt + 64)) != GR_OK) return rc;
+    double* b = (double*)c->d_in;
+    dev = *cells;
+    dev.n = cnt;
+    dev.cos_theta = b;
+    dev.phi = b + cnt;
+    if (cnt > 0) {
+        GR_HIP(hipMemcpyAsync(b, cells->cos_theta + off, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+        GR_HIP(hipMemcpyAsync(b + cnt, cells->phi + off, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+    }
+    return GR_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t gr_sky_cells(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf, double* out,
+                     gr_stats* stats)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc;
+    if ((rc = skycells_check(cfg, cells, pf, true)) != GR_OK) return rc;
+    if (cells->n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
+    GR_HIP(hipSetDevice(ctx->device));
+    gr_skycells dev;
+    if ((rc = stage_skycells(ctx, cells, 0, cells->n, dev)) != GR_OK) return rc;
+    const size_t bytes = sizeof(double) * GR_SKYCELL_ROW * (size_t)cells->n;
+    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
+    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
+    if ((rc = gr_sky_cells_device(ctx, cfg, &dev, pf, (double*)ctx->d_scratch, stats ? (gr_stats*)ctx->d_stats : nullptr,
+                                  ctx->stream)) != GR_OK) return rc;
+    if (bytes) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return end_host_call(ctx, stats);
+}
+
+int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf,
+                           double* out, gr_stats* stats)
+{
+    int32_t rc;
+    if ((rc = validate_ctxs(ctxs, n)) != GR_OK) return rc;
+    if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
+    if ((rc = skycells_check(cfg, cells, pf, true)) != GR_OK) return rc;
+    if (cells->n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
+    const size_t row_bytes = sizeof(double) * GR_SKYCELL_ROW;
+    auto enq = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        int64_t off, cnt;
+        contiguous_share(cells->n, n, k, &off, &cnt);
+        int32_t r;
+        GR_HIP(hipSetDevice(c->device));
+        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;      // (before the staging, see rayset_rows_multi)
+        gr_skycells dev;
+        if ((r = stage_skycells(c, cells, off, cnt, dev)) != GR_OK) return r;
+        if ((r = ensure(&c->d_scratch, &c->scratch_bytes, cnt ? row_bytes * (size_t)cnt : 8)) != GR_OK) return r;
+        if (cnt == 0) return GR_OK;
+        return gr_sky_cells_device(c, cfg, &dev, pf, (double*)c->d_scratch, stats ? (gr_stats*)c->d_stats : nullptr, c->stream);
+    };
+    auto copy = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        int64_t off, cnt;
+        contiguous_share(cells->n, n, k, &off, &cnt);
+        if (cnt == 0) return GR_OK;
+        GR_HIP(hipSetDevice(c->device));
+        GR_HIP(hipMemcpyAsync((char*)out + row_bytes * (size_t)off, c->d_scratch, row_bytes * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        return GR_OK;
+    };
+    return multi_drive(ctxs, n, stats, enq, copy);
+}

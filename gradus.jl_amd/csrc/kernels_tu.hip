@@ -4,6 +4,7 @@
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_F32 -Xclang -cl-single-precision-constant ... -o kernels32_m<id>.o   (fp32)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN -c kernels_tu.hip -o kernelstan_m<id>.o                     (tangent, one lane per ray)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN1 -c kernels_tu.hip -o kernelstan1_m<id>.o                   (tangent, a pair of lanes per ray)
+//     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN[1] -DGR_TU_SKY -c kernels_tu.hip -o kernelssky[1]_m<id>.o    (the two tangent shapes for sky cells)
 //
 // so that every metric's kernels hold only that metric's component function (gr_device.hpp, GenericMetricT) and the
 // library builds on all cores at once (__graft_entry__.build_hip).  The fp32 objects are the same source with
@@ -13,7 +14,7 @@
 //
 // Exports (plain signatures: the host unit, gradus_mi355x.hip, passes its gr::Params by address -- gr32::Params has the
 // same layout, its fields are double / integer / pointers only):
-//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>
+//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>      grts_launch_trace_m<ID>      grts1_launch_trace_m<ID>
 #ifndef GR_TU_METRIC
 #error "compile with -DGR_TU_METRIC=<metric id>"
 #endif
@@ -31,15 +32,33 @@
 // The host unit picks per launch (gr_ctx_set "tangent_pairs": launches that cannot fill the SIMDs anyway take the pairs).
 // A 256-register variant of the pair shape (two waves per SIMD, stage accelerations parked in LDS) was measured and lost
 // to both (24.5 ms; 1.31 s).
+// Both shapes once more with -DGR_TU_SKY (namespaces grts, grts1): the same kernels with the sky-cell branches of gr_device.hpp
+// compiled in (GR_SKYCELL: the (θ, ϕ) seed of src_mode 1, the row of out_mode 6) for gr_sky_cells.  An instantiation of their own
+// because the two branches, though outside the step loop, move the register allocation of the kernels above (Kerr, one lane per
+// ray: -6 ... +8 VGPRs over the disc types, 439 -> 447 for the datum plane; a tabulated metric's pairs: -32 ... +32 bytes of
+// scratch -- DESIGN_measurements.md §M31), which stay as they were.
 #define GR_REAL_IS_TAN2 1
+#if defined(GR_TU_SKY)
+#define GR_SKYCELL 1
+#endif
 #if defined(GR_TU_TAN1)
 #define GR_TAN_W 1
+#if defined(GR_TU_SKY)
+#define GR_NS grts1
+#define GR_TU_PREFIX grts1
+#else
 #define GR_NS grt1
 #define GR_TU_PREFIX grt1
+#endif
 #else
 #define GR_TAN_W 2
+#if defined(GR_TU_SKY)
+#define GR_NS grts
+#define GR_TU_PREFIX grts
+#else
 #define GR_NS grt
 #define GR_TU_PREFIX grt
+#endif
 #endif
 #define GR_LANE_ONLY 1
 #define GR_LANE_MIN_WAVES 1  // waves per SIMD the tangent kernels are compiled for

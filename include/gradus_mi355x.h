@@ -741,6 +741,33 @@ int32_t gr_ring_arms(gr_ctx* ctx, const gr_config* cfg, const gr_ringset* rings,
                      double* rows_out /* host, n_rings x n_slices x (n_base + 2 extrema_iter) x 5 */,
                      int64_t* counts_out /* host, n_rings x n_slices x 3 */, gr_stats* stats);
 
+/* ---- the cells of a source's adaptive sky (added within ABI 8; AdaptiveSky, src/corona/adaptive-sample.jl:43-81) ----
+ * Cell j is the direction (θ_j = acos(cos_theta[j]), ϕ_j = phi[j]) on the local sky of a source at x_src with the sky frame
+ * Mx = T diag(1, J) (the matrix a gr_rayset's sky source carries): v = Mx (1, -k̂), k̂ = (sin θ cos ϕ, sin θ sin ϕ, cos θ).  The
+ * TANGENT kernels trace it with ∂/∂θ and ∂/∂ϕ of the sky angles seeded on that velocity (closed form, formed on the device) --
+ * the reference's dual numbers through the integrator -- and write one CoronaGridValues row of 6 doubles per cell:
+ *     t, r = x^r |sin x^θ|, ϕ = x^ϕ (unwrapped, as integrated), g, J = |∂(r, ϕ)/∂(θ, ϕ_sky)| / sin θ, status
+ * with g the redshift point function's energy ratio against pf->u_src and status the reference's float code: 1 = the ray met
+ * the geometry, -3 = within the inner boundary, 7 = out of the domain, 0 = anything else.  A cell whose ray does not meet the
+ * geometry has NaN in t, r, ϕ, g and J.  gr_ctx_set "tangent_pairs" / "tangent_norm" apply as for gr_ray_tangent.
+ * GR_ERR_INVALID_ARGUMENT, before anything touches the device, for: a null pointer, cfg->disc_id == GR_DISC_NONE, a point
+ * function other than the redshift or without has_u_src, a source outside the radial range of a GR_METRIC_TABULATED table and
+ * (where the angles are host arrays: not gr_sky_cells_device) |cos θ| >= 1.
+ * gr_sky_cells_multi: contiguous shares of the cells, one per context, the rows of one context bit for bit. */
+typedef struct gr_skycells {
+    double x_src[4];          /* the source's position                                                       */
+    double Mx[16];            /* row-major 4 x 4: tetrad of the source times diag(1, Cartesian -> spherical) */
+    const double* cos_theta;  /* n (gr_sky_cells_device: device memory)                                      */
+    const double* phi;        /* n (gr_sky_cells_device: device memory)                                      */
+    int64_t n;
+} gr_skycells;
+int32_t gr_sky_cells(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf,
+                     double* out /* host, n x 6 */, gr_stats* stats);
+int32_t gr_sky_cells_device(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf,
+                            double* d_out /* device, n x 6 */, gr_stats* d_stats, void* hip_stream);
+int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_skycells* cells,
+                           const gr_pointfunction* pf, double* out /* host, n x 6 */, gr_stats* stats /* n, or NULL */);
+
 /* ---- tabulated metrics (ABI 7; segments, axis terms: ABI 8; GR_METRIC_TABULATED): the AbstractMetric plugin interface on the device ----
  * Host-only functions (no context, no device): plan a grid, learn its nodes, fit, check.
  *
