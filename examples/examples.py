@@ -207,3 +207,12 @@ print(f"fill_sky_values: {np.isfinite(dense['r']).sum()} of {dense.size} sky poi
 r_bins, ϕ_bins = np.geomspace(m.isco(), 100.0, 100), np.linspace(0.0, 2 * math.pi, 100)
 ε = G.bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky)
 print(f"bin_emissivity_grid: {np.count_nonzero(ε)} of {ε.size} (r, ϕ) bins lit, ε at r ≈ 10 between {ε[50][ε[50] > 0].min():.3g} and {ε[50].max():.3g}")
+
+# ## adaptive_solve: the illumination map solved to convergence, the tree and the rows resident on the device
+sky = G.AdaptiveSky(m, corona, d, ensemble=ens, resident=True)
+iterations, dt = timed(lambda: G.adaptive_solve(m, d, sky, verbose=False))
+r_bins, ϕ_bins = np.geomspace(m.isco(), 1000.0, 500), np.linspace(0.0, 2 * math.pi, 500)
+lit = sky.device_occupancy(r_bins, ϕ_bins) != 0
+print(f"adaptive_solve: {iterations} iterations, {sky.n_cells} cells, {lit.mean():.1%} of 500 x 500 (r, ϕ) bins lit ({dt:.2f} s)")
+ε = G.bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky)          # (reads the host mirror, brought up to date here)
+print(f"bin_emissivity_grid on the solved sky: {np.count_nonzero(ε)} bins lit")

@@ -315,6 +315,40 @@ class gr_skycells(C.Structure):
     ]
 
 
+GR_SKY_MAX_BOXES = 8
+GR_SKY_CRIT_DEFAULT, GR_SKY_CRIT_FUNCTION, GR_SKY_CRIT_FINE, GR_SKY_CRIT_LEVEL = 0, 1, 2, 3
+
+
+class gr_sky_box(C.Structure):
+    """An r interval and zero, one or two intervals of mod(ϕ, 2π), every bound open or closed (gr_sky_criterion)"""
+
+    _fields_ = [
+        ("r_lo", C.c_double),
+        ("r_hi", C.c_double),
+        ("phi_lo", C.c_double * 2),
+        ("phi_hi", C.c_double * 2),
+        ("r_open_lo", C.c_int32),
+        ("r_open_hi", C.c_int32),
+        ("phi_open_lo", C.c_int32),
+        ("phi_open_hi", C.c_int32),
+        ("n_phi", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class gr_sky_criterion(C.Structure):
+    """A pair criterion of a resident adaptive sky (gr_sky_find_need_refine)"""
+
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("level", C.c_int32),
+        ("rtol", C.c_double),
+        ("n_boxes", C.c_int32),
+        ("reserved", C.c_int32),
+        ("boxes", gr_sky_box * GR_SKY_MAX_BOXES),
+    ]
+
+
 class gr_stats(C.Structure):
     _fields_ = [
         ("rays", C.c_int64),
@@ -404,6 +438,16 @@ EXPORTS = [
     "gr_sky_cells",
     "gr_sky_cells_device",
     "gr_sky_cells_multi",
+    "gr_sky_create",
+    "gr_sky_destroy",
+    "gr_sky_size",
+    "gr_sky_trace_initial",
+    "gr_sky_find_need_refine",
+    "gr_sky_need_refine_list",
+    "gr_sky_pairs",
+    "gr_sky_refine_and_trace",
+    "gr_sky_occupancy",
+    "gr_sky_download",
     "gr_render_endpoints_multi",
     "gr_trace_endpoints_multi",
     "gr_rayset_endpoints_multi",
@@ -486,6 +530,17 @@ def load():
     L.gr_sky_cells_device.argtypes = [vp, cfgp, scp, pfp, vp, vp, vp]
     ctxa = C.POINTER(vp)
     L.gr_sky_cells_multi.argtypes = [ctxa, i32, cfgp, scp, pfp, vp, vp]
+    i64p = C.POINTER(i64)
+    L.gr_sky_create.argtypes = [vp, cfgp, scp, pfp, vp, i32, C.POINTER(vp)]
+    L.gr_sky_destroy.argtypes = [vp]
+    L.gr_sky_size.argtypes = [vp, i64p]
+    L.gr_sky_trace_initial.argtypes = [vp, i32, vp]
+    L.gr_sky_find_need_refine.argtypes = [vp, C.POINTER(gr_sky_criterion), i64p]
+    L.gr_sky_need_refine_list.argtypes = [vp, vp]
+    L.gr_sky_pairs.argtypes = [vp, vp, vp, i64, i64p]
+    L.gr_sky_refine_and_trace.argtypes = [vp, vp, i64, i64p, stp]
+    L.gr_sky_occupancy.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    L.gr_sky_download.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gr_render_endpoints_multi.argtypes = [ctxa, i32, cfgp, plp, i64, vp, vp]
     L.gr_trace_endpoints_multi.argtypes = [ctxa, i32, cfgp, vp, i64, vp, i64, vp, vp]
     L.gr_rayset_endpoints_multi.argtypes = [ctxa, i32, cfgp, rsp, vp, vp]

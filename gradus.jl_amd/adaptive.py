@@ -11,10 +11,22 @@ inherits the parent's row.
 
 `check_refine(sky, i1, i2)` receives index ARRAYS and returns a bool array, so the reference's criteria read the same
 with `np.isnan(sky.values["r"][i1])`.
+
+`AdaptiveSky(m, corona, d, resident=True)` keeps the tree and the rows on the device (`gr_sky_*`): the pair search, the
+refinement and the census of the (r, ϕ) bins run there, `sky.grid` and `sky.values` are host mirrors brought up to date on
+first read after a change.  The criteria of this module carry a `gr_sky_criterion` where they can be written as one (the
+default criterion, `refine_to_level`, `refine_function` / `fine_refine_function` over `RadialBox`es); any other callable is
+evaluated on the mirror against the pair list the device returns.
+
+The drivers of adaptive-sample.jl:486-842 -- `empty_fraction`, `evaluate_refinement_metric`, `step_block`,
+`adaptive_solve` -- work on both kinds of sky.
 """
 from __future__ import annotations
 
+import enum
 import math
+import sys
+import time
 
 import numpy as np
 
@@ -39,6 +51,71 @@ def _isapprox(a, b, rtol):
         return (a == b) | (np.abs(a - b) <= rtol * np.maximum(np.abs(a), np.abs(b)))
 
 
+class RadialBox:
+    """RadialBox(r_min, r_max, ϕ=None, open=True, ϕ_open=False): a region of the disc as a predicate over rows, the `f` of
+    `refine_function` / `fine_refine_function` -- r in an interval and, if ϕ is given, mod(ϕ, 2π) in one interval `(lo, hi)` or
+    in either of two `((lo, hi), (lo, hi))` (a block that wraps around ϕ = 0).  `open` / `ϕ_open`: a bool or a pair (lower,
+    upper) -- is the bound itself outside?  `v.r > 800` is RadialBox(800, inf, open=(True, False)); the block test of
+    step_block! (`_is_in`) is closed.  A NaN r lies in no box."""
+
+    def __init__(self, r_min, r_max, ϕ=None, open=True, ϕ_open=False):
+        self.r = (float(r_min), float(r_max))
+        self.open = (bool(open),) * 2 if isinstance(open, (bool, np.bool_)) else tuple(bool(o) for o in open)
+        self.ϕ_open = (bool(ϕ_open),) * 2 if isinstance(ϕ_open, (bool, np.bool_)) else tuple(bool(o) for o in ϕ_open)
+        if ϕ is None:
+            self.ϕ = ()
+        elif np.ndim(ϕ) == 1:
+            self.ϕ = ((float(ϕ[0]), float(ϕ[1])),)
+        else:
+            self.ϕ = tuple((float(lo), float(hi)) for lo, hi in ϕ)
+        if len(self.open) != 2 or len(self.ϕ_open) != 2 or len(self.ϕ) > 2:
+            raise ValueError("RadialBox: open / ϕ_open are a bool or a pair, ϕ is one or two intervals")
+
+    def __repr__(self):
+        return f"RadialBox(r={self.r}, ϕ={self.ϕ}, open={self.open}, ϕ_open={self.ϕ_open})"
+
+    @staticmethod
+    def _inside(x, lo, hi, open_):
+        return (x > lo if open_[0] else x >= lo) & (x < hi if open_[1] else x <= hi)
+
+    def __call__(self, v):
+        with np.errstate(invalid="ignore"):
+            inside = self._inside(v["r"], self.r[0], self.r[1], self.open)
+            if self.ϕ:
+                folded = np.mod(v["ϕ"], TWO_PI)
+                in_ϕ = np.zeros(np.shape(folded), dtype=bool)
+                for lo, hi in self.ϕ:
+                    in_ϕ |= self._inside(folded, lo, hi, self.ϕ_open)
+                inside = inside & in_ϕ
+        return inside
+
+
+def _boxes_of(f):
+    """the RadialBoxes `f` stands for (one, or a list of up to 8), or None for any other callable"""
+    if isinstance(f, RadialBox):
+        return [f]
+    if isinstance(f, (list, tuple)) and f and all(isinstance(b, RadialBox) for b in f):
+        return list(f)
+    return None
+
+
+def _any_box(boxes):
+    def f(v):
+        out = np.zeros(np.shape(v["r"]), dtype=bool)
+        for b in boxes:
+            out |= b(v)
+        return out
+
+    return f
+
+
+def _criterion(kind, percentage=2, level=0, boxes=()):
+    """what a resident sky marshals into a gr_sky_criterion; None if the boxes do not fit"""
+    if len(boxes) > 8:
+        return None
+    return {"kind": kind, "rtol": percentage / 100, "level": int(level), "boxes": list(boxes)}
+
+
 def check_refine(sky, i1, i2, percentage=2):
     """The default criterion (adaptive-sample.jl:123-140): g or J differ by more than `percentage` per cent between the two
     cells; a pair of cells that both miss the disc is left alone."""
@@ -49,25 +126,39 @@ def check_refine(sky, i1, i2, percentage=2):
     return ~both_miss & (g_too_coarse | J_too_coarse)
 
 
+check_refine.gr_criterion = _criterion(0)
+
+
 def refine_function(f):
     """refine_function(f) (adaptive-sample.jl:682-691): `f(values)` is given the rows of an index array's cells and returns a
-    bool array; a pair is refined where f holds for either cell, unless both miss."""
+    bool array; a pair is refined where f holds for either cell, unless both miss.  `f` may be a RadialBox or a list of them."""
+    boxes = _boxes_of(f)
+    if boxes is not None:
+        f = _any_box(boxes)
 
     def _refine(sky, i1, i2):
         v1, v2 = sky.values[np.asarray(i1)], sky.values[np.asarray(i2)]
         both_miss = np.isnan(v1["r"]) & np.isnan(v2["r"])
         return ~both_miss & (np.asarray(f(v1), dtype=bool) | np.asarray(f(v2), dtype=bool))
 
+    if boxes is not None:
+        _refine.gr_criterion = _criterion(1, boxes=boxes)
     return _refine
 
 
 def fine_refine_function(f, **kwargs):
-    """fine_refine_function(f; kwargs...) (adaptive-sample.jl:700-710): the default criterion AND f on either cell"""
+    """fine_refine_function(f; kwargs...) (adaptive-sample.jl:700-710): the default criterion AND f on either cell.  `f` may be
+    a RadialBox or a list of them."""
+    boxes = _boxes_of(f)
+    if boxes is not None:
+        f = _any_box(boxes)
 
     def _refine(sky, i1, i2):
         v1, v2 = sky.values[np.asarray(i1)], sky.values[np.asarray(i2)]
         return check_refine(sky, i1, i2, **kwargs) & (np.asarray(f(v1), dtype=bool) | np.asarray(f(v2), dtype=bool))
 
+    if boxes is not None and set(kwargs) <= {"percentage"}:
+        _refine.gr_criterion = _criterion(2, boxes=boxes, **kwargs)
     return _refine
 
 
@@ -79,20 +170,51 @@ def refine_to_level(n):
         both_miss = np.isnan(sky.values["r"][i1]) & np.isnan(sky.values["r"][i2])
         return ~both_miss & (sky.grid.level[i2] < n)
 
+    refiner.gr_criterion = _criterion(3, level=n)
     return refiner
+
+
+def gr_criterion_of(check_refine):
+    """the gr_sky_criterion a criterion of this module carries (what a resident sky hands to the device), or None for a plain
+    callable"""
+    from . import _lib
+
+    spec = getattr(check_refine, "gr_criterion", None)
+    if spec is None:
+        return None
+    cr = _lib.gr_sky_criterion()
+    cr.kind, cr.level, cr.rtol, cr.n_boxes = spec["kind"], spec["level"], spec["rtol"], len(spec["boxes"])
+    for k, box in enumerate(spec["boxes"]):
+        b = cr.boxes[k]
+        b.r_lo, b.r_hi = box.r
+        b.r_open_lo, b.r_open_hi = (int(o) for o in box.open)
+        b.phi_open_lo, b.phi_open_hi = (int(o) for o in box.ϕ_open)
+        b.n_phi = len(box.ϕ)
+        for q, (lo, hi) in enumerate(box.ϕ):
+            b.phi_lo[q], b.phi_hi[q] = lo, hi
+    return cr
 
 
 class AdaptiveSky:
     """AdaptiveSky(calc_values, check_refine; pole_offset = 1e-6) -- the generic form, adaptive-sky.jl:26-46: `calc_values(cos θ[],
     ϕ[])` returns a structured array of SKY_DTYPE -- or AdaptiveSky(m, corona, d; ensemble, t_max, solver_opts...)
-    (adaptive-sample.jl:156-178), whose `calc_values` is one `gr_sky_cells` launch per call."""
+    (adaptive-sample.jl:156-178), whose `calc_values` is one `gr_sky_cells` launch per call.  With `resident=True` the tree and
+    the rows of the latter live on the device (one context), and `grid` / `values` are mirrors of them."""
 
     def __init__(self, *args, check_refine=None, pole_offset=1e-6, **kwargs):
+        self._dev = None
+        resident = bool(kwargs.pop("resident", False))
         if len(args) == 3 and not callable(args[0]):
             if check_refine is not None:
                 raise TypeError("AdaptiveSky(m, corona, d) brings the default criterion; pass another to trace_step")
+            ensemble = kwargs.get("ensemble")
+            if resident and ensemble is not None and ensemble.multi:
+                raise ValueError("AdaptiveSky(resident=True) keeps the sky on ONE context: pass an ensemble of one device, "
+                                 "or resident=False to share every step's cells among the contexts")
             calc_values, self.tracer = _make_emissivity_tracer(*args, **kwargs)
             criterion = globals()["check_refine"]
+        elif resident:
+            raise TypeError("resident=True needs AdaptiveSky(m, corona, d): the device traces the cells")
         else:
             if kwargs:
                 raise TypeError(f"unexpected keyword arguments {sorted(kwargs)}")
@@ -103,19 +225,187 @@ class AdaptiveSky:
             else:
                 raise TypeError("AdaptiveSky(calc_values, check_refine) or AdaptiveSky(m, corona, d)")
             self.tracer = None
-        self.grid = AdaptiveGrid(math.cos(pole_offset), math.cos(math.pi - pole_offset), -math.pi, math.pi)
+        self._grid = AdaptiveGrid(math.cos(pole_offset), math.cos(math.pi - pole_offset), -math.pi, math.pi)
         self.calculate_value = calc_values
         self.check_refine = criterion
         self._values = make_null(1)
-        self.n_values = 0
+        self._n_values = 0
+        if resident:
+            self._make_resident()
 
     def __repr__(self):
         return f"AdaptiveSky[N={self.n_values}]"
 
     @property
+    def resident(self):
+        return self._dev is not None
+
+    @property
+    def n_cells(self):
+        """the number of cells (on a resident sky: asked of the device, the mirrors stay as they are)"""
+        return self._device_size() if self._dev is not None else self._grid.n
+
+    @property
+    def grid(self):
+        self._sync()
+        return self._grid
+
+    @grid.setter
+    def grid(self, value):
+        self._grid = value
+
+    @property
+    def n_values(self):
+        self._sync()
+        return self._n_values
+
+    @n_values.setter
+    def n_values(self, value):
+        self._n_values = value
+
+    @property
     def values(self):
         """the cells' rows, a view: row i for cell i -- cells count from 1, row 0 is a null row (NaN)"""
-        return self._values[:self.n_values + 1]
+        self._sync()
+        return self._values[:self._n_values + 1]
+
+    # ---- the resident sky: the tree and the rows on the device, grid / values as mirrors ----
+    def _make_resident(self):
+        import ctypes as C
+
+        from . import _lib
+
+        tr = self.tracer
+        if tr["ensemble"].multi:
+            raise ValueError("AdaptiveSky(resident=True) keeps the sky on ONE context")
+        source = _lib.gr_skycells()
+        for q in range(4):
+            source.x_src[q] = tr["x_src"][q]
+        for q, val in enumerate(tr["Mx"].ravel()):
+            source.Mx[q] = val
+        (x1, x2), (y1, y2) = self._grid.limits
+        limits = (C.c_double * 4)(x1, x2, y1, y2)
+        handle = C.c_void_p()
+        self._L = _lib.load()
+        _lib.check(self._L.gr_sky_create(tr["ensemble"].ctx.handle, C.byref(tr["cfg"]), C.byref(source), C.byref(tr["pf"]), limits,
+                                         int(self._grid.x_periodic), C.byref(handle)))
+        self._dev = handle
+        self._stale = False
+
+    def __del__(self):
+        try:
+            if getattr(self, "_dev", None):
+                self._L.gr_sky_destroy(self._dev)
+                self._dev = None
+        except Exception:
+            pass
+
+    def _device_size(self):
+        import ctypes as C
+
+        from . import _lib
+
+        n = C.c_int64(0)
+        _lib.check(self._L.gr_sky_size(self._dev, C.byref(n)))
+        return int(n.value)
+
+    def _sync(self):
+        """bring the mirrors up to date: the cells made since the last read, and the `children` rows of their parents"""
+        if self._dev is None or not self._stale:
+            return
+        import ctypes as C
+
+        from . import _lib
+
+        self._stale = False
+        g, n = self._grid, self._device_size()
+        first = 0 if self._n_values == 0 else self._n_values + 1
+        count = n + 1 - first
+        if count <= 0:
+            return
+        g._reserve(n - g.n)
+        if n + 1 > self._values.size:
+            grown = np.empty(max(n + 1, 2 * self._values.size, 1024), dtype=SKY_DTYPE)
+            grown[:self._n_values + 1] = self._values[:self._n_values + 1]
+            self._values = grown
+        groups = count // 9 if first >= 10 else 0
+        refined = np.empty(groups, dtype=np.int64)
+        kids = np.empty((groups, 9), dtype=np.int64)
+        ptr = lambda a: C.c_void_p(a[first:].ctypes.data)
+        _lib.check(self._L.gr_sky_download(self._dev, first, count, ptr(g.pos), ptr(g.level), ptr(g.children), ptr(g.neighbours), ptr(g.parent),
+                                           ptr(g.location), ptr(self._values), C.c_void_p(refined.ctypes.data) if groups else None,
+                                           C.c_void_p(kids.ctypes.data) if groups else None))
+        if groups:
+            g.children[refined] = kids
+        g.n = n
+        self._n_values = n
+
+    def _device_find(self, check_refine):
+        """gr_sky_find_need_refine: the number of cells it names (they stay in a device list), or None if the criterion is a
+        plain callable"""
+        import ctypes as C
+
+        from . import _lib
+
+        cr = gr_criterion_of(check_refine)
+        if cr is None:
+            return None
+        count = C.c_int64(0)
+        _lib.check(self._L.gr_sky_find_need_refine(self._dev, C.byref(cr), C.byref(count)))
+        return int(count.value)
+
+    def _device_list(self, count):
+        import ctypes as C
+
+        from . import _lib
+
+        cells = np.empty(count, dtype=np.int64)
+        _lib.check(self._L.gr_sky_need_refine_list(self._dev, C.c_void_p(cells.ctypes.data)))
+        return cells
+
+    def _device_refine(self, cells=None):
+        """gr_sky_refine_and_trace of a host list, or (None) of the device list of the last _device_find"""
+        import ctypes as C
+
+        from . import _lib
+
+        traced, st = C.c_int64(0), _lib.gr_stats()
+        if cells is None:
+            rc = self._L.gr_sky_refine_and_trace(self._dev, None, 0, C.byref(traced), C.byref(st))
+        else:
+            cells = np.ascontiguousarray(cells, dtype=np.int64)
+            rc = self._L.gr_sky_refine_and_trace(self._dev, C.c_void_p(cells.ctypes.data), cells.size, C.byref(traced), C.byref(st))
+        if rc == -1:      # GR_ERR_INVALID_ARGUMENT: a cell out of range, refined already or named twice
+            raise ValueError(self._L.gr_last_error().decode("utf-8", "replace"))      # (refine_many raises the same)
+        _lib.check(rc)
+        if traced.value:
+            self._stale = True
+            self.tracer["launches"].append((int(traced.value), float(st.kernel_ms)))
+
+    def device_pairs(self):
+        """gr_sky_pairs: every (leaf, bordering leaf) pair, as grid.bordering_pairs() lists them"""
+        import ctypes as C
+
+        from . import _lib
+
+        n = C.c_int64(0)
+        _lib.check(self._L.gr_sky_pairs(self._dev, None, None, 0, C.byref(n)))
+        i1, i2 = np.empty(n.value, dtype=np.int64), np.empty(n.value, dtype=np.int64)
+        _lib.check(self._L.gr_sky_pairs(self._dev, C.c_void_p(i1.ctypes.data), C.c_void_p(i2.ctypes.data), n.value, C.byref(n)))
+        return i1, i2
+
+    def device_occupancy(self, r_bins, ϕ_bins, Γ=2):
+        """gr_sky_occupancy: per (r, ϕ) bin the leaves that land in it with J g^Γ != 0 -- where bin_emissivity_grid is non-zero"""
+        import ctypes as C
+
+        from . import _lib
+
+        r_bins, ϕ_bins = np.ascontiguousarray(r_bins, dtype=np.float64), np.ascontiguousarray(ϕ_bins, dtype=np.float64)
+        counts = np.zeros((r_bins.size, ϕ_bins.size), dtype=np.int64)
+        gamma = None if Γ is None else C.byref(C.c_double(float(Γ)))
+        _lib.check(self._L.gr_sky_occupancy(self._dev, C.c_void_p(r_bins.ctypes.data), r_bins.size, C.c_void_p(ϕ_bins.ctypes.data), ϕ_bins.size,
+                                            gamma, C.c_void_p(counts.ctypes.data)))
+        return counts
 
     def _append(self, rows):
         need = self.n_values + rows.size
@@ -141,6 +431,16 @@ def trace_initial(sky, level=3):
     one call of calc_values per level."""
     if sky.n_values != 0:
         raise ValueError("the sky has been traced already")
+    if sky.resident:
+        import ctypes as C
+
+        from . import _lib
+
+        sizes = (C.c_int64 * int(level))()
+        _lib.check(sky._L.gr_sky_trace_initial(sky._dev, int(level), sizes))
+        sky._stale = True
+        sky.tracer["launches"].extend((int(n), float("nan")) for n in sizes)
+        return sky
     sky._append(sky._trace(np.arange(1, len(sky.grid) + 1)))
     for _ in range(1, level):
         refine_and_trace(sky, sky.grid.leaves())
@@ -151,7 +451,13 @@ def find_need_refine(sky, check_refine=None):
     """find_need_refine(sky, check_refine) (adaptive-sky.jl:130-152): the sorted cells that `check_refine(sky, leaf, bordering
     leaf)` names -- it is the BORDERING cell of a pair that is refined."""
     check_refine = sky.check_refine if check_refine is None else check_refine
-    i1, i2 = sky.grid.bordering_pairs()
+    if sky.resident:
+        count = sky._device_find(check_refine)
+        if count is not None:
+            return sky._device_list(count)
+        i1, i2 = sky.device_pairs()
+    else:
+        i1, i2 = sky.grid.bordering_pairs()
     if i1.size == 0:
         return np.empty(0, dtype=np.int64)
     need = np.asarray(check_refine(sky, i1, i2), dtype=bool)
@@ -164,6 +470,9 @@ def refine_and_trace(sky, cell_ids):
     cell_ids = np.asarray(cell_ids, dtype=np.int64).reshape(-1)
     if cell_ids.size == 0:
         return sky
+    if sky.resident:
+        sky._device_refine(cell_ids)
+        return sky
     kids = sky.grid.refine_many(cell_ids)
     rows = make_null(kids.size).reshape(kids.shape)
     rows[:, 4] = sky.values[cell_ids]
@@ -175,8 +484,30 @@ def refine_and_trace(sky, cell_ids):
 
 
 def trace_step(sky, check_refine=None):
-    """trace_step!(sky; check_refine = sky.check_refine) (adaptive-sky.jl:210-213)"""
-    return refine_and_trace(sky, find_need_refine(sky, check_refine))
+    """trace_step!(sky; check_refine = sky.check_refine) (adaptive-sky.jl:210-213).  On a resident sky with a criterion of this
+    module the list of cells never leaves the device."""
+    _refine_found(sky, _find(sky, check_refine))
+    return sky
+
+
+def _find(sky, check_refine=None):
+    """find_need_refine as (number of cells, their indices -- or None where they stay in the resident sky's device list)"""
+    if sky.resident:
+        count = sky._device_find(sky.check_refine if check_refine is None else check_refine)
+        if count is not None:
+            return count, None
+    cells = find_need_refine(sky, check_refine)
+    return cells.size, cells
+
+
+def _refine_found(sky, found):
+    count, cells = found
+    if count == 0:
+        return
+    if cells is None:
+        sky._device_refine(None)
+    else:
+        refine_and_trace(sky, cells)
 
 
 def unpack_sky(sky):
@@ -354,3 +685,137 @@ def _make_emissivity_tracer(m, corona, d, *, ensemble=None, t_max=1_000_000.0, *
         return out
 
     return calc_values, keep
+
+
+# ---- the drivers: adaptive-sample.jl:486-842 ----
+
+class AxisLimits:
+    """AxisLimits(l1[, l2]) (adaptive-sample.jl:486-503): one or two ranges of bin indices, 1-based and inclusive as the
+    reference's UnitRanges are"""
+
+    def __init__(self, l1, l2=None):
+        self.l1 = (int(l1[0]), int(l1[1]))
+        self.l2 = None if l2 is None else (int(l2[0]), int(l2[1]))
+
+    def __repr__(self):
+        return f"AxisLimits({self.l1[0]}:{self.l1[1]}" + ("" if self.l2 is None else f", {self.l2[0]}:{self.l2[1]}") + ")"
+
+    def as_index(self):
+        """_as_index, 0-based for numpy"""
+        idx = np.arange(self.l1[0] - 1, self.l1[1])
+        return idx if self.l2 is None else np.concatenate([idx, np.arange(self.l2[0] - 1, self.l2[1])])
+
+    def intervals(self, domain):
+        """the closed intervals of `domain` the ranges span (_is_in)"""
+        spans = [(float(domain[self.l1[0] - 1]), float(domain[self.l1[1] - 1]))]
+        if self.l2 is not None and self.l2[1] >= self.l2[0]:
+            spans.append((float(domain[self.l2[0] - 1]), float(domain[self.l2[1] - 1])))
+        return spans
+
+
+def empty_fraction(r, ϕ, block):
+    """empty_fraction(r, ϕ, block) (adaptive-sample.jl:505-511): count(!=(0), block) / length(block) -- the FILLED fraction,
+    as the reference computes it despite its name"""
+    block = np.asarray(block)
+    return np.count_nonzero(block) / block.size
+
+
+def evaluate_refinement_metric(m, d, sky, r_bins, ϕ_bins, split=6, metric=empty_fraction):
+    """evaluate_refinement_metric(m, d, sky, r_bins, phi_bins; split, metric) (adaptive-sample.jl:532-562): the (r, ϕ) map of the
+    sky in blocks of N ÷ split + 1 bins, every (N ÷ split) ÷ 4 bins, and `metric(r, ϕ, block)` of each.  A list of
+    (r limits, ϕ limits, score) in the reference's order: the blocks that wrap around ϕ = 0 first, then ϕ by ϕ, r fastest.
+    On a resident sky the default metric reads the device's census of the bins (gr_sky_occupancy), which is non-zero exactly
+    where the map is; any other metric is given the map of the mirror."""
+    N = len(r_bins)
+    if len(ϕ_bins) != N:
+        raise ValueError("r_bins and ϕ_bins must have the same length")
+    if sky.resident and metric is empty_fraction:
+        output = sky.device_occupancy(r_bins, ϕ_bins)
+    else:
+        output = bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky)
+    stencil = N // split
+    half = stencil // 2
+
+    def eval_metric(i, j):
+        r = AxisLimits((i, i + stencil))
+        ϕ = AxisLimits((1, half), (N - half, N)) if j == 0 else AxisLimits((j, j + stencil))
+        block = output[np.ix_(r.as_index(), ϕ.as_index())]
+        return r, ϕ, metric(r, ϕ, block)
+
+    axis = range(1, N - stencil + 1, stencil // 4)
+    return [eval_metric(i, 0) for i in axis] + [eval_metric(i, j) for j in axis for i in axis]
+
+
+class StepBlockCodes(enum.Enum):
+    converged = 0
+    not_converged = 1
+    limit_exceeded = 2
+
+
+def step_block(m, d, sky, check_threshold=True, threshold=0.2, N=500, top=3, split=6, percentage=10, limit=200_000,
+               metric=empty_fraction):
+    """step_block!(m, d, sky; ...) (adaptive-sample.jl:603-665): bin the sky into N x N bins of logrange(isco, 1000) x
+    range(0, 2π), score the blocks, and refine -- to `percentage` per cent -- the pairs with a cell in one of the `top`
+    lowest-scoring blocks (those below `threshold` if check_threshold).  StepBlockCodes.converged if no block is left,
+    limit_exceeded (and nothing refined) if more than `limit` cells would be refined, else not_converged."""
+    r_bins = np.geomspace(m.isco(), 1000.0, N)
+    ϕ_bins = np.linspace(0.0, TWO_PI, N)
+    counts = evaluate_refinement_metric(m, d, sky, r_bins, ϕ_bins, split=split, metric=metric)
+    counts = [c for c in counts if c[2] != 0]
+    counts.sort(key=lambda c: c[2])          # (stable, as the reference's sort! of a vector of tuples is)
+    if check_threshold:
+        counts = [c for c in counts if c[2] < threshold]
+        if not counts:
+            return StepBlockCodes.converged
+    boxes = []
+    for r, ϕ, _ in counts[:top]:
+        (r_lo, r_hi), = r.intervals(r_bins)
+        boxes.append(RadialBox(r_lo, r_hi, ϕ=ϕ.intervals(ϕ_bins), open=False, ϕ_open=False))
+    found = _find(sky, fine_refine_function(boxes, percentage=percentage))
+    if found[0] > limit:
+        print(f"Convergence failed. Limit {limit} exceeded: too many cells to refine (N = {found[0]}).", file=sys.stderr)
+        return StepBlockCodes.limit_exceeded
+    _refine_found(sky, found)
+    return StepBlockCodes.not_converged
+
+
+def adaptive_solve(m, d, sky, verbose=True, limit=50, trace_calls=2, **step_block_kwargs):
+    """adaptive_solve!(m, d, sky; verbose, limit, trace_calls, kwargs...) (adaptive-sample.jl:745-842): trace_initial, 1 +
+    trace_calls plain steps, a pass over the far radii (r > 800 at 10 %) and one over the innermost (r_isco < r < 2 at 20 %), then
+    step_block (split = 5, top = 4 unless given) until every block is covered or `limit` iterations are spent, then levels 4
+    and 5.  Returns the number of refinement iterations."""
+    i = 0
+    t0 = time.perf_counter()
+
+    def report(what):
+        if verbose:
+            print(f"adaptive_solve: iteration {i:3d} {what:<14} cells {sky.n_cells:>9}  {time.perf_counter() - t0:8.2f} s", file=sys.stderr)
+
+    trace_initial(sky)
+    trace_step(sky)
+    i += 1
+    report("trace_step")
+    for _ in range(trace_calls):
+        trace_step(sky)
+        i += 1
+        report("trace_step")
+    trace_step(sky, fine_refine_function(RadialBox(800.0, math.inf, open=(True, False)), percentage=10))
+    i += 1
+    report("far")
+    trace_step(sky, fine_refine_function(RadialBox(m.isco(), 2.0, open=True), percentage=20))
+    i += 1
+    report("inner")
+    kwargs = {"split": 5, "top": 4}
+    kwargs.update(step_block_kwargs)
+    status = StepBlockCodes.not_converged
+    while status is StepBlockCodes.not_converged:
+        status = step_block(m, d, sky, **kwargs)
+        i += 1
+        report(status.name)
+        if i >= limit:
+            break
+    for level in (4, 5):
+        trace_step(sky, refine_to_level(level))
+        i += 1
+        report(f"level {level}")
+    return i

@@ -33,6 +33,7 @@
 #include "gr_tfint.hpp"
 #include "gr_tftd.hpp"
 #include "gr_ringarm.hpp"
+#include "gr_skygrid.hpp"
 
 using namespace gr;
 
@@ -1187,6 +1188,7 @@ int32_t gr_ctx_create(int32_t device, gr_ctx** out)
 }
 
 static void pool_drop_all();
+static void sky_drop_ctx(gr_ctx* c);      // the resident skies a context owns go with it (gr_sky_*, at the end of this file)
 
 int32_t gr_ctx_destroy(gr_ctx* c)
 {
@@ -1196,6 +1198,7 @@ int32_t gr_ctx_destroy(gr_ctx* c)
     if (c->counted && g_live_ctx.fetch_sub(1) == 1) pool_drop_all();
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    sky_drop_ctx(c);
     if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_stat_part) (void)hipFree(c->d_stat_part);
@@ -4429,4 +4432,707 @@ int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg,
         return GR_OK;
     };
     return multi_drive(ctxs, n, stats, enq, copy);
+}
+
+// ---- an adaptive sky resident on the device: gr_sky_* (AdaptiveSky, adaptive-sky.jl; the drivers of adaptive-sample.jl:486-842) ----
+// The tree (the arrays of grids.AdaptiveGrid) and the rows stay in device memory between refinement steps; the pair search,
+// the refinement and the census of the (r, ϕ) bins are the kernels below around the functions of gr_skygrid.hpp, and the new
+// cells of a step go to ONE gr_sky_cells_device launch.  What crosses the link per step is a count.
+
+struct gr_sky {
+    gr_ctx* ctx = nullptr;
+    gr_config cfg;
+    gr_pointfunction pf;
+    gr_skycells src;                       // x_src, Mx
+    double lim[4] = { 0, 0, 0, 0 };
+    int64_t n = 0, cap = 0;                // cells; rows the arrays below hold (cap >= n + 1)
+    double* d_pos = nullptr;
+    int32_t* d_level = nullptr;
+    int64_t* d_children = nullptr;
+    int64_t* d_neighbours = nullptr;
+    int64_t* d_parent = nullptr;
+    int8_t* d_location = nullptr;
+    double* d_rows = nullptr;
+    // work buffers of cap elements (off: cap + 1), not kept across a growth
+    uint8_t* d_mark = nullptr;
+    uint32_t* d_cnt = nullptr;
+    int64_t* d_off = nullptr;
+    int64_t* d_part = nullptr;             // SKY_SCAN_BLOCKS + 1 partial sums, then the refusal flag
+    void* d_need = nullptr;                // the list of the last find_need_refine / a host list
+    size_t need_bytes = 0;
+    int64_t need_n = -1;                   // -1: no list
+    void* d_ang = nullptr;                 // (cos θ, ϕ) of the cells of a launch, then their rows
+    size_t ang_bytes = 0;
+    void* d_tmp = nullptr;                 // pairs, bin edges and counts, downloads
+    size_t tmp_bytes = 0;
+    bool traced = false;
+};
+
+namespace {
+
+constexpr int SKY_SCAN_BLOCKS = 1024;
+constexpr int64_t SKY_MAX_GRID = 2048;     // blocks of a grid-stride launch (256 CUs x 8)
+
+std::mutex g_sky_mutex;
+std::vector<gr_sky*> g_skies;              // the skies alive: gr_sky_destroy after the context went is a no-op
+
+gr_skygrid::Grid sky_grid(const gr_sky* s)
+{
+    gr_skygrid::Grid g;
+    g.pos = s->d_pos;
+    g.level = s->d_level;
+    g.children = s->d_children;
+    g.neighbours = s->d_neighbours;
+    g.parent = s->d_parent;
+    g.location = s->d_location;
+    g.n = s->n;
+    g.x1 = s->lim[0];
+    g.x2 = s->lim[1];
+    g.y1 = s->lim[2];
+    g.y2 = s->lim[3];
+    return g;
+}
+
+unsigned sky_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, SKY_MAX_GRID)); }
+
+// ---- an exclusive scan of n counts into n + 1 offsets (off[n] = the sum): block b owns the elements [b per, (b + 1) per) ----
+template <class T>
+__global__ void __launch_bounds__(256) k_sky_scan_partial(const T* __restrict__ v, int64_t n, int64_t per, int64_t* __restrict__ part)
+{
+    __shared__ int64_t s[256];
+    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    int64_t acc = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) acc += (int64_t)v[i];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = s[0];
+}
+// part[0 .. nb) -> their exclusive scan, part[nb] = the sum (one block; nb <= SKY_SCAN_BLOCKS)
+__global__ void __launch_bounds__(256) k_sky_scan_parts(int64_t* part, int nb)
+{
+    __shared__ int64_t s[SKY_SCAN_BLOCKS + 1];
+    for (int i = threadIdx.x; i < nb; i += 256) s[i] = part[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t acc = 0;
+        for (int i = 0; i < nb; ++i) {
+            const int64_t x = s[i];
+            s[i] = acc;
+            acc += x;
+        }
+        s[nb] = acc;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i <= nb; i += 256) part[i] = s[i];
+}
+template <class T>
+__global__ void __launch_bounds__(256) k_sky_scan_apply(const T* __restrict__ v, int64_t n, int64_t per, const int64_t* __restrict__ part,
+                                                        int64_t* __restrict__ off)
+{
+    __shared__ int64_t s[256];
+    __shared__ int64_t base;
+    const int tid = threadIdx.x;
+    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    if (tid == 0) base = part[blockIdx.x];
+    __syncthreads();
+    for (int64_t t = lo; t < hi; t += 256) {       // (uniform over the block)
+        const int64_t i = t + tid;
+        const int64_t x = i < hi ? (int64_t)v[i] : 0;
+        s[tid] = x;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const int64_t y = tid >= d ? s[tid - d] : 0;
+            __syncthreads();
+            s[tid] += y;
+            __syncthreads();
+        }
+        const int64_t incl = s[tid], b = base;
+        if (i < hi) off[i] = b + incl - x;
+        __syncthreads();
+        if (tid == 255) base = b + incl;
+        __syncthreads();
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) off[n] = part[gridDim.x];
+}
+
+// off[0 .. n] = the exclusive scan of v[0 .. n); three launches, nothing allocated, no wait
+template <class T>
+int32_t sky_scan(gr_sky* s, const T* v, int64_t n, hipStream_t stream)
+{
+    int64_t nb = std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, SKY_SCAN_BLOCKS));
+    int64_t per = ((n + nb - 1) / nb + 255) / 256 * 256;
+    if (per < 256) per = 256;
+    nb = std::max<int64_t>(1, (n + per - 1) / per);
+    hipLaunchKernelGGL(k_sky_scan_partial<T>, dim3((unsigned)nb), dim3(256), 0, stream, v, n, per, s->d_part);
+    hipLaunchKernelGGL(k_sky_scan_parts, dim3(1), dim3(256), 0, stream, s->d_part, (int)nb);
+    hipLaunchKernelGGL(k_sky_scan_apply<T>, dim3((unsigned)nb), dim3(256), 0, stream, v, n, per, (const int64_t*)s->d_part, s->d_off);
+    GR_HIP(hipGetLastError());
+    return GR_OK;
+}
+
+// list[off[c]] = c for every marked cell: the marked cells, ascending (np.unique(i2[need]))
+__global__ void __launch_bounds__(256) k_sky_compact(const uint8_t* __restrict__ mark, const int64_t* __restrict__ off, int64_t n_rows,
+                                                     int64_t* __restrict__ list)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < n_rows; c += (int64_t)gridDim.x * 256)
+        if (mark[c]) list[off[c]] = c;
+}
+
+__global__ void __launch_bounds__(256) k_sky_mark_leaves(const gr_skygrid::Grid g, uint8_t* __restrict__ mark)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c <= g.n; c += (int64_t)gridDim.x * 256)
+        mark[c] = (c >= 1 && gr_skygrid::is_leaf(g, c)) ? 1 : 0;
+}
+
+// find_need_refine: one work-item per leaf walks its bordering leaves; a pair the criterion names marks the BORDERING cell with
+// a plain byte store of 1 (idempotent: no atomics, no order).  flag: a walk that ran out of stack.
+__global__ void __launch_bounds__(256) k_sky_mark_need(const gr_skygrid::Grid g, const double* __restrict__ rows, const gr_sky_criterion cr,
+                                                       uint8_t* mark, int32_t* flag)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x + 1; c <= g.n; c += (int64_t)gridDim.x * 256) {
+        if (!gr_skygrid::is_leaf(g, c)) continue;
+        const int k = gr_skygrid::walk_bordering(g, c, [&](int64_t other) {
+            if (gr_skygrid::need_refine(cr, g, rows, c, other)) mark[other] = 1;
+        });
+        if (k < 0) *flag = 5;
+    }
+}
+
+// bordering_pairs: the count pass and the fill pass
+__global__ void __launch_bounds__(256) k_sky_pair_count(const gr_skygrid::Grid g, uint32_t* __restrict__ cnt, int32_t* flag)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c <= g.n; c += (int64_t)gridDim.x * 256) {
+        int k = 0;
+        if (c >= 1 && gr_skygrid::is_leaf(g, c)) k = gr_skygrid::walk_bordering(g, c, [](int64_t) {});
+        if (k < 0) {
+            *flag = 5;
+            k = 0;
+        }
+        cnt[c] = (uint32_t)k;
+    }
+}
+__global__ void __launch_bounds__(256) k_sky_pair_fill(const gr_skygrid::Grid g, const int64_t* __restrict__ off, int64_t total,
+                                                       int64_t* __restrict__ i1, int64_t* __restrict__ i2)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x + 1; c <= g.n; c += (int64_t)gridDim.x * 256) {
+        if (!gr_skygrid::is_leaf(g, c)) continue;
+        int64_t at = off[c];
+        const int64_t end = off[c + 1];
+        (void)gr_skygrid::walk_bordering(g, c, [&](int64_t other) {
+            if (at < end && at < total) {
+                i1[at] = c;
+                i2[at] = other;
+            }
+            ++at;
+        });
+    }
+}
+
+// what refine_many raises on: seen[c] counts how often the list names c (an integer atomic: the old value tells a second naming)
+__global__ void __launch_bounds__(256) k_sky_refusals(const gr_skygrid::Grid g, const int64_t* __restrict__ list, int64_t m, uint32_t* seen,
+                                                      int32_t* flag)
+{
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < m; k += (int64_t)gridDim.x * 256) {
+        const int64_t c = list[k];
+        int why = gr_skygrid::refine_refusal(g, c);
+        if (why == 0 && atomicAdd(&seen[c], 1u) != 0u) why = 4;
+        if (why != 0) atomicMax(flag, why);
+    }
+}
+
+// refine_many on the device: work-item 9 k + c writes child c of the k-th cell of the list into row first + 9 k + c; the middle
+// child takes its parent's row, the eight others leave (cos θ, ϕ) for the launch, in child order per parent
+__global__ void __launch_bounds__(256) k_sky_children(const gr_skygrid::Grid g, const int64_t* __restrict__ list, int64_t m, double* rows,
+                                                      double* __restrict__ cos_theta, double* __restrict__ phi)
+{
+    for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < 9 * m; w += (int64_t)gridDim.x * 256) {
+        const int64_t k = w / 9;
+        const int c = (int)(w - 9 * k);
+        const int64_t cell = list[k], first = g.n + 1 + 9 * k, row = first + c;
+        gr_skygrid::write_child(g, cell, first, c);
+        if (c == 4) {
+            for (int q = 0; q < 6; ++q) rows[6 * row + q] = rows[6 * cell + q];
+        } else {
+            const int64_t j = 8 * k + (c < 4 ? c : c - 1);
+            cos_theta[j] = g.pos[2 * row];
+            phi[j] = g.pos[2 * row + 1];
+        }
+    }
+}
+// the rows of the launch into the children's slots
+__global__ void __launch_bounds__(256) k_sky_scatter(const double* __restrict__ traced, int64_t m, int64_t first, double* __restrict__ rows)
+{
+    for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < 8 * m; w += (int64_t)gridDim.x * 256) {
+        const int64_t k = w / 8;
+        const int j = (int)(w - 8 * k);
+        const int64_t row = first + 9 * k + (j < 4 ? j : j + 1);
+        for (int q = 0; q < 6; ++q) rows[6 * row + q] = traced[6 * w + q];
+    }
+}
+__global__ void __launch_bounds__(256) k_sky_positions(const double* __restrict__ pos, int64_t first, int64_t m, double* __restrict__ cos_theta,
+                                                       double* __restrict__ phi)
+{
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < m; j += (int64_t)gridDim.x * 256) {
+        cos_theta[j] = pos[2 * (first + j)];
+        phi[j] = pos[2 * (first + j) + 1];
+    }
+}
+
+// the census of the (r, ϕ) bins: integer atomics, so the counts do not depend on the order
+__global__ void __launch_bounds__(256) k_sky_occupancy(const gr_skygrid::Grid g, const double* __restrict__ rows, const double* __restrict__ r_bins,
+                                                       int64_t nr, double r_max, const double* __restrict__ phi_bins, int64_t nphi, int has_gamma,
+                                                       double gamma, unsigned int* counts)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x + 1; c <= g.n; c += (int64_t)gridDim.x * 256) {
+        if (!gr_skygrid::is_leaf(g, c)) continue;
+        int64_t ri, pi;
+        if (!gr_skygrid::bin_of(rows + 6 * c, r_bins, nr, r_max, phi_bins, nphi, ri, pi)) continue;
+        if (gr_skygrid::lights(rows + 6 * c, has_gamma != 0, gamma)) atomicAdd(&counts[ri * nphi + pi], 1u);
+    }
+}
+
+// the cells refined since a download and their rows of `children`: every nine cells from `first` on share a parent
+__global__ void __launch_bounds__(256) k_sky_refined(const gr_skygrid::Grid g, int64_t first, int64_t groups, int64_t* __restrict__ refined,
+                                                     int64_t* __restrict__ kids)
+{
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < groups; k += (int64_t)gridDim.x * 256) {
+        const int64_t p = g.parent[first + 9 * k];
+        refined[k] = p;
+        for (int c = 0; c < 9; ++c) kids[9 * k + c] = g.children[9 * p + c];
+    }
+}
+
+// ---- host side ----
+
+template <class T>
+int32_t sky_grow(T** buf, size_t old_count, size_t new_count, hipStream_t stream)
+{
+    T* fresh = nullptr;
+    GR_HIP(hipMalloc((void**)&fresh, sizeof(T) * new_count));
+    if (*buf && old_count) GR_HIP(hipMemcpyAsync(fresh, *buf, sizeof(T) * old_count, hipMemcpyDeviceToDevice, stream));
+    GR_HIP(hipStreamSynchronize(stream));
+    if (*buf) (void)hipFree(*buf);
+    *buf = fresh;
+    return GR_OK;
+}
+template <class T>
+int32_t sky_fresh(T** buf, size_t count)
+{
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    GR_HIP(hipMalloc((void**)buf, sizeof(T) * count));
+    return GR_OK;
+}
+
+// room for `cells` cells: the arrays grow by doubling (outside any launch function); the work buffers follow
+int32_t sky_reserve(gr_sky* s, int64_t cells)
+{
+    if (cells > (int64_t)INT32_MAX - 16) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky: more than 2^31 cells");
+    const size_t need = (size_t)cells + 1;
+    if ((size_t)s->cap >= need) return GR_OK;
+    const size_t cap = std::max<size_t>(need, std::max<size_t>(2 * (size_t)s->cap, 1024));
+    const size_t have = s->cap ? (size_t)s->n + 1 : 0;
+    hipStream_t st = s->ctx->stream;
+    int32_t rc;
+    if ((rc = sky_grow(&s->d_pos, 2 * have, 2 * cap, st)) != GR_OK) return rc;
+    if ((rc = sky_grow(&s->d_level, have, cap, st)) != GR_OK) return rc;
+    if ((rc = sky_grow(&s->d_children, 9 * have, 9 * cap, st)) != GR_OK) return rc;
+    if ((rc = sky_grow(&s->d_neighbours, 4 * have, 4 * cap, st)) != GR_OK) return rc;
+    if ((rc = sky_grow(&s->d_parent, have, cap, st)) != GR_OK) return rc;
+    if ((rc = sky_grow(&s->d_location, have, cap, st)) != GR_OK) return rc;
+    if ((rc = sky_grow(&s->d_rows, 6 * have, 6 * cap, st)) != GR_OK) return rc;
+    if ((rc = sky_fresh(&s->d_mark, cap)) != GR_OK) return rc;
+    if ((rc = sky_fresh(&s->d_cnt, cap)) != GR_OK) return rc;
+    if ((rc = sky_fresh(&s->d_off, cap + 1)) != GR_OK) return rc;
+    if (!s->d_part && (rc = sky_fresh(&s->d_part, (size_t)SKY_SCAN_BLOCKS + 2)) != GR_OK) return rc;
+    s->cap = (int64_t)cap;
+    return GR_OK;
+}
+
+int32_t* sky_flag(gr_sky* s) { return (int32_t*)(s->d_part + SKY_SCAN_BLOCKS + 1); }
+
+void sky_free(gr_sky* s)
+{
+    (void)hipSetDevice(s->ctx->device);
+    if (s->ctx->stream) (void)hipStreamSynchronize(s->ctx->stream);
+    void* bufs[] = { s->d_pos, s->d_level, s->d_children, s->d_neighbours, s->d_parent, s->d_location, s->d_rows, s->d_mark,
+                     s->d_cnt, s->d_off, s->d_part, s->d_need, s->d_ang, s->d_tmp };
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    delete s;
+}
+
+// launch: the cells whose (cos θ, ϕ) lie in d_ang (m each) -> their rows behind them in d_ang; allocates nothing
+int32_t sky_launch_trace(gr_sky* s, int64_t m, gr_stats* stats)
+{
+    gr_skycells cells = s->src;
+    double* ang = (double*)s->d_ang;
+    cells.cos_theta = ang;
+    cells.phi = ang + m;
+    cells.n = m;
+    return gr_sky_cells_device(s->ctx, &s->cfg, &cells, &s->pf, ang + 2 * m, stats ? (gr_stats*)s->ctx->d_stats : nullptr, s->ctx->stream);
+}
+
+// launch: refine the m cells of the device list d_need (checked first) and trace their outer children in one launch.  Room for
+// the 9 m children and the launch's angles and rows is there (sky_refine_list): nothing is allocated here, and the host waits
+// twice -- for the refusal flag, and at the end of the call.
+int32_t sky_refine_launch(gr_sky* s, int64_t m, int64_t* traced, gr_stats* stats)
+{
+    int32_t rc;
+    hipStream_t st = s->ctx->stream;
+    const int64_t* list = (const int64_t*)s->d_need;
+    const gr_skygrid::Grid g = sky_grid(s);
+    // refusals first: nothing has changed when one is found
+    GR_HIP(hipMemsetAsync(s->d_cnt, 0, sizeof(uint32_t) * ((size_t)s->n + 1), st));
+    GR_HIP(hipMemsetAsync(sky_flag(s), 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_sky_refusals, dim3(sky_blocks(m)), dim3(256), 0, st, g, list, m, s->d_cnt, sky_flag(s));
+    GR_HIP(hipGetLastError());
+    int32_t why = 0;
+    GR_HIP(hipMemcpyAsync(&why, sky_flag(s), sizeof why, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    if (why != 0) {
+        static const char* const text[] = { "", "a cell index outside 1 ... n_cells", "a cell is refined already", "a cell at the deepest level (20) cannot be refined",
+                                            "a cell is named twice" };
+        return fail(GR_ERR_INVALID_ARGUMENT, std::string("gr_sky_refine_and_trace: ") + text[why > 4 ? 0 : why]);
+    }
+    if ((rc = begin_host_call(s->ctx, stats)) != GR_OK) return rc;
+    double* ang = (double*)s->d_ang;
+    hipLaunchKernelGGL(k_sky_children, dim3(sky_blocks(9 * m)), dim3(256), 0, st, g, list, m, s->d_rows, ang, ang + 8 * m);
+    GR_HIP(hipGetLastError());
+    if ((rc = sky_launch_trace(s, 8 * m, stats)) != GR_OK) return rc;
+    hipLaunchKernelGGL(k_sky_scatter, dim3(sky_blocks(8 * m)), dim3(256), 0, st, (const double*)(ang + 16 * m), m, s->n + 1, s->d_rows);
+    GR_HIP(hipGetLastError());
+    if ((rc = end_host_call(s->ctx, stats)) != GR_OK) return rc;
+    s->n += 9 * m;
+    s->need_n = -1;
+    if (traced) *traced = 8 * m;
+    return GR_OK;
+}
+
+// room first (the arrays grow by doubling, the work buffers follow), then the launch
+int32_t sky_refine_list(gr_sky* s, int64_t m, int64_t* traced, gr_stats* stats)
+{
+    if (traced) *traced = 0;
+    if (m == 0) return GR_OK;
+    int32_t rc;
+    if ((rc = sky_reserve(s, s->n + 9 * m)) != GR_OK) return rc;
+    if ((rc = ensure(&s->d_ang, &s->ang_bytes, sizeof(double) * 8 * 8 * (size_t)m)) != GR_OK) return rc;
+    return sky_refine_launch(s, m, traced, stats);
+}
+
+int32_t sky_check(gr_sky* sky)
+{
+    if (!sky) return fail(GR_ERR_INVALID_ARGUMENT, "sky is null");
+    GR_HIP(hipSetDevice(sky->ctx->device));
+    return GR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+static void sky_drop_ctx(gr_ctx* c)
+{
+    std::vector<gr_sky*> mine;
+    {
+        std::lock_guard<std::mutex> lock(g_sky_mutex);
+        for (size_t i = 0; i < g_skies.size();)
+            if (g_skies[i]->ctx == c) {
+                mine.push_back(g_skies[i]);
+                g_skies.erase(g_skies.begin() + (long)i);
+            } else
+                ++i;
+    }
+    for (gr_sky* s : mine) sky_free(s);
+}
+}  // extern "C"
+
+int32_t gr_sky_create(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* source, const gr_pointfunction* pf, const double* limits,
+                      int32_t x_periodic, gr_sky** sky)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!sky || !limits) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_create: sky / limits is null");
+    *sky = nullptr;
+    int32_t rc;
+    gr_skycells none;
+    if (source) {
+        none = *source;
+        none.cos_theta = none.phi = nullptr;
+        none.n = 0;
+    }
+    if ((rc = skycells_check(cfg, source ? &none : nullptr, pf, false)) != GR_OK) return rc;
+    for (int q = 0; q < 4; ++q)
+        if (!std::isfinite(limits[q])) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_create: the limits must be finite");
+    GR_HIP(hipSetDevice(ctx->device));
+    gr_sky* s = new (std::nothrow) gr_sky;
+    if (!s) return fail(GR_ERR_OUT_OF_MEMORY, "gr_sky_create: out of memory");
+    s->ctx = ctx;
+    s->cfg = *cfg;
+    s->pf = *pf;
+    s->src = none;
+    s->lim[0] = std::min(limits[0], limits[1]);
+    s->lim[1] = std::max(limits[0], limits[1]);
+    s->lim[2] = std::min(limits[2], limits[3]);
+    s->lim[3] = std::max(limits[2], limits[3]);
+    if ((rc = sky_reserve(s, 9)) != GR_OK) {
+        sky_free(s);
+        return rc;
+    }
+    // the nine top cells, formed here as AdaptiveGrid.__init__ forms them
+    double pos[20];
+    int32_t level[10];
+    int64_t children[90], neighbours[40], parent[10];
+    int8_t location[10];
+    double rows[60];
+    gr_skygrid::Grid g = sky_grid(s);
+    g.pos = pos;
+    g.level = level;
+    g.children = children;
+    g.neighbours = neighbours;
+    g.parent = parent;
+    g.location = location;
+    gr_skygrid::top_cells(g, x_periodic != 0);
+    for (double& v : rows) v = NAN;
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMemcpyAsync(s->d_pos, pos, sizeof pos, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_level, level, sizeof level, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_children, children, sizeof children, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_neighbours, neighbours, sizeof neighbours, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_parent, parent, sizeof parent, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_location, location, sizeof location, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_rows, rows, sizeof rows, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        sky_free(s);
+        return fail(GR_ERR_HIP, std::string("gr_sky_create: ") + hipGetErrorString(e));
+    }
+    s->n = 9;
+    {
+        std::lock_guard<std::mutex> lock(g_sky_mutex);
+        g_skies.push_back(s);
+    }
+    *sky = s;
+    return GR_OK;
+}
+
+int32_t gr_sky_destroy(gr_sky* sky)
+{
+    if (!sky) return GR_OK;
+    {
+        std::lock_guard<std::mutex> lock(g_sky_mutex);
+        auto it = std::find(g_skies.begin(), g_skies.end(), sky);
+        if (it == g_skies.end()) return GR_OK;      // its context took it along
+        g_skies.erase(it);
+    }
+    sky_free(sky);
+    return GR_OK;
+}
+
+int32_t gr_sky_size(gr_sky* sky, int64_t* n_cells)
+{
+    if (!sky || !n_cells) return fail(GR_ERR_INVALID_ARGUMENT, "sky / n_cells is null");
+    *n_cells = sky->n;
+    return GR_OK;
+}
+
+int32_t gr_sky_trace_initial(gr_sky* sky, int32_t level, int64_t* launch_sizes)
+{
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (sky->traced || sky->n != 9) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_trace_initial: the sky has been traced already");
+    if (level < 1 || level > GR_SKY_MAX_LEVEL) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_trace_initial: level in 1 ... 20");
+    hipStream_t st = sky->ctx->stream;
+    if ((rc = ensure(&sky->d_ang, &sky->ang_bytes, sizeof(double) * 8 * 9)) != GR_OK) return rc;
+    double* ang = (double*)sky->d_ang;
+    hipLaunchKernelGGL(k_sky_positions, dim3(1), dim3(256), 0, st, (const double*)sky->d_pos, (int64_t)1, (int64_t)9, ang, ang + 9);
+    GR_HIP(hipGetLastError());
+    if ((rc = sky_launch_trace(sky, 9, nullptr)) != GR_OK) return rc;
+    GR_HIP(hipMemcpyAsync(sky->d_rows + 6, ang + 18, sizeof(double) * 6 * 9, hipMemcpyDeviceToDevice, st));
+    GR_HIP(hipStreamSynchronize(st));
+    sky->traced = true;
+    if (launch_sizes) launch_sizes[0] = 9;
+    for (int32_t l = 1; l < level; ++l) {
+        // every leaf: the cells of the last level, ascending
+        const int64_t n_rows = sky->n + 1;
+        if ((rc = ensure(&sky->d_need, &sky->need_bytes, sizeof(int64_t) * (size_t)n_rows)) != GR_OK) return rc;
+        hipLaunchKernelGGL(k_sky_mark_leaves, dim3(sky_blocks(n_rows)), dim3(256), 0, st, sky_grid(sky), sky->d_mark);
+        GR_HIP(hipGetLastError());
+        if ((rc = sky_scan(sky, (const uint8_t*)sky->d_mark, n_rows, st)) != GR_OK) return rc;
+        hipLaunchKernelGGL(k_sky_compact, dim3(sky_blocks(n_rows)), dim3(256), 0, st, (const uint8_t*)sky->d_mark, (const int64_t*)sky->d_off, n_rows,
+                           (int64_t*)sky->d_need);
+        GR_HIP(hipGetLastError());
+        int64_t m = 0;
+        GR_HIP(hipMemcpyAsync(&m, sky->d_off + n_rows, sizeof m, hipMemcpyDeviceToHost, st));
+        GR_HIP(hipStreamSynchronize(st));
+        int64_t traced = 0;
+        if ((rc = sky_refine_list(sky, m, &traced, nullptr)) != GR_OK) return rc;
+        if (launch_sizes) launch_sizes[l] = traced;
+    }
+    return GR_OK;
+}
+
+int32_t gr_sky_find_need_refine(gr_sky* sky, const gr_sky_criterion* criterion, int64_t* count)
+{
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (!criterion || !count) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: criterion / count is null");
+    if (criterion->kind < GR_SKY_CRIT_DEFAULT || criterion->kind > GR_SKY_CRIT_LEVEL)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: unknown criterion kind");
+    if (criterion->n_boxes < 0 || criterion->n_boxes > GR_SKY_MAX_BOXES)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: n_boxes in 0 ... 8");
+    for (int k = 0; k < criterion->n_boxes; ++k)
+        if (criterion->boxes[k].n_phi < 0 || criterion->boxes[k].n_phi > 2)
+            return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: a box has zero, one or two ϕ intervals");
+    *count = 0;
+    sky->need_n = -1;
+    hipStream_t st = sky->ctx->stream;
+    const int64_t n_rows = sky->n + 1;
+    if ((rc = ensure(&sky->d_need, &sky->need_bytes, sizeof(int64_t) * (size_t)n_rows)) != GR_OK) return rc;
+    GR_HIP(hipMemsetAsync(sky->d_mark, 0, (size_t)n_rows, st));
+    GR_HIP(hipMemsetAsync(sky_flag(sky), 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_sky_mark_need, dim3(sky_blocks(sky->n)), dim3(256), 0, st, sky_grid(sky), (const double*)sky->d_rows, *criterion, sky->d_mark,
+                       sky_flag(sky));
+    GR_HIP(hipGetLastError());
+    int32_t why = 0;
+    GR_HIP(hipMemcpyAsync(&why, sky_flag(sky), sizeof why, hipMemcpyDeviceToHost, st));
+    if ((rc = sky_scan(sky, (const uint8_t*)sky->d_mark, n_rows, st)) != GR_OK) return rc;
+    hipLaunchKernelGGL(k_sky_compact, dim3(sky_blocks(n_rows)), dim3(256), 0, st, (const uint8_t*)sky->d_mark, (const int64_t*)sky->d_off, n_rows,
+                       (int64_t*)sky->d_need);
+    GR_HIP(hipGetLastError());
+    int64_t m = 0;
+    GR_HIP(hipMemcpyAsync(&m, sky->d_off + n_rows, sizeof m, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    if (why != 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: the tree is deeper than the bordering walk's stack");
+    sky->need_n = m;
+    *count = m;
+    return GR_OK;
+}
+
+int32_t gr_sky_need_refine_list(gr_sky* sky, int64_t* cells)
+{
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (sky->need_n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_need_refine_list: no list (gr_sky_find_need_refine comes first)");
+    if (sky->need_n == 0) return GR_OK;
+    if (!cells) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_need_refine_list: cells is null");
+    GR_HIP(hipMemcpyAsync(cells, sky->d_need, sizeof(int64_t) * (size_t)sky->need_n, hipMemcpyDeviceToHost, sky->ctx->stream));
+    GR_HIP(hipStreamSynchronize(sky->ctx->stream));
+    return GR_OK;
+}
+
+int32_t gr_sky_pairs(gr_sky* sky, int64_t* i1, int64_t* i2, int64_t cap, int64_t* n)
+{
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (!n) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_pairs: n is null");
+    hipStream_t st = sky->ctx->stream;
+    const int64_t n_rows = sky->n + 1;
+    const gr_skygrid::Grid g = sky_grid(sky);
+    GR_HIP(hipMemsetAsync(sky_flag(sky), 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_sky_pair_count, dim3(sky_blocks(n_rows)), dim3(256), 0, st, g, sky->d_cnt, sky_flag(sky));
+    GR_HIP(hipGetLastError());
+    if ((rc = sky_scan(sky, (const uint32_t*)sky->d_cnt, n_rows, st)) != GR_OK) return rc;
+    int64_t total = 0;
+    int32_t why = 0;
+    GR_HIP(hipMemcpyAsync(&total, sky->d_off + n_rows, sizeof total, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipMemcpyAsync(&why, sky_flag(sky), sizeof why, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    if (why != 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_pairs: the tree is deeper than the bordering walk's stack");
+    *n = total;
+    if (!i1 || !i2 || cap < total || total == 0) return GR_OK;
+    if ((rc = ensure(&sky->d_tmp, &sky->tmp_bytes, sizeof(int64_t) * 2 * (size_t)total)) != GR_OK) return rc;
+    int64_t* d1 = (int64_t*)sky->d_tmp;
+    hipLaunchKernelGGL(k_sky_pair_fill, dim3(sky_blocks(sky->n)), dim3(256), 0, st, g, (const int64_t*)sky->d_off, total, d1, d1 + total);
+    GR_HIP(hipGetLastError());
+    GR_HIP(hipMemcpyAsync(i1, d1, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipMemcpyAsync(i2, d1 + total, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    return GR_OK;
+}
+
+int32_t gr_sky_refine_and_trace(gr_sky* sky, const int64_t* cells, int64_t n, int64_t* traced, gr_stats* stats)
+{
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (traced) *traced = 0;
+    if (!sky->traced) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_refine_and_trace: gr_sky_trace_initial comes first (the middle children inherit rows)");
+    if (!cells) {
+        if (sky->need_n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_refine_and_trace: no list (gr_sky_find_need_refine comes first)");
+        return sky_refine_list(sky, sky->need_n, traced, stats);
+    }
+    if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_refine_and_trace: n must be non-negative");
+    sky->need_n = -1;
+    if (n == 0) return GR_OK;
+    if ((rc = ensure(&sky->d_need, &sky->need_bytes, sizeof(int64_t) * (size_t)n)) != GR_OK) return rc;
+    GR_HIP(hipMemcpyAsync(sky->d_need, cells, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, sky->ctx->stream));
+    return sky_refine_list(sky, n, traced, stats);
+}
+
+int32_t gr_sky_occupancy(gr_sky* sky, const double* r_bins, int64_t n_r, const double* phi_bins, int64_t n_phi, const double* gamma,
+                         int64_t* counts)
+{
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (!r_bins || !phi_bins || !counts || n_r < 1 || n_phi < 1 || n_r > 46340 || n_phi > 46340)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_occupancy: r_bins / phi_bins / counts is null, or a count outside 1 ... 46340");
+    hipStream_t st = sky->ctx->stream;
+    const size_t cells = (size_t)n_r * (size_t)n_phi;
+    if ((rc = ensure(&sky->d_tmp, &sky->tmp_bytes, sizeof(double) * (size_t)(n_r + n_phi) + sizeof(unsigned int) * cells)) != GR_OK) return rc;
+    double* d_r = (double*)sky->d_tmp;
+    double* d_p = d_r + n_r;
+    unsigned int* d_c = (unsigned int*)(d_p + n_phi);
+    double r_max = r_bins[0];
+    for (int64_t k = 1; k < n_r; ++k) r_max = r_bins[k] > r_max ? r_bins[k] : r_max;
+    GR_HIP(hipMemcpyAsync(d_r, r_bins, sizeof(double) * (size_t)n_r, hipMemcpyHostToDevice, st));
+    GR_HIP(hipMemcpyAsync(d_p, phi_bins, sizeof(double) * (size_t)n_phi, hipMemcpyHostToDevice, st));
+    GR_HIP(hipMemsetAsync(d_c, 0, sizeof(unsigned int) * cells, st));
+    hipLaunchKernelGGL(k_sky_occupancy, dim3(sky_blocks(sky->n)), dim3(256), 0, st, sky_grid(sky), (const double*)sky->d_rows, (const double*)d_r, n_r,
+                       r_max, (const double*)d_p, n_phi, gamma ? 1 : 0, gamma ? *gamma : 0.0, d_c);
+    GR_HIP(hipGetLastError());
+    std::vector<unsigned int> h;
+    try {
+        h.resize(cells);
+    } catch (...) {
+        return fail(GR_ERR_OUT_OF_MEMORY, "gr_sky_occupancy: out of memory");
+    }
+    GR_HIP(hipMemcpyAsync(h.data(), d_c, sizeof(unsigned int) * cells, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    for (size_t k = 0; k < cells; ++k) counts[k] = (int64_t)h[k];
+    return GR_OK;
+}
+
+int32_t gr_sky_download(gr_sky* sky, int64_t first_cell, int64_t count, double* pos, void* level, int64_t* children, int64_t* neighbours,
+                        int64_t* parent, void* location, double* rows, int64_t* refined, int64_t* refined_children)
+{
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (first_cell < 0 || count < 0 || first_cell + count > sky->n + 1)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_download: cells first_cell ... first_cell + count - 1 must lie in 0 ... n_cells");
+    if (count == 0) return GR_OK;
+    hipStream_t st = sky->ctx->stream;
+    const size_t f = (size_t)first_cell, c = (size_t)count;
+    if (pos) GR_HIP(hipMemcpyAsync(pos, sky->d_pos + 2 * f, sizeof(double) * 2 * c, hipMemcpyDeviceToHost, st));
+    if (level) GR_HIP(hipMemcpyAsync(level, sky->d_level + f, sizeof(int32_t) * c, hipMemcpyDeviceToHost, st));
+    if (children) GR_HIP(hipMemcpyAsync(children, sky->d_children + 9 * f, sizeof(int64_t) * 9 * c, hipMemcpyDeviceToHost, st));
+    if (neighbours) GR_HIP(hipMemcpyAsync(neighbours, sky->d_neighbours + 4 * f, sizeof(int64_t) * 4 * c, hipMemcpyDeviceToHost, st));
+    if (parent) GR_HIP(hipMemcpyAsync(parent, sky->d_parent + f, sizeof(int64_t) * c, hipMemcpyDeviceToHost, st));
+    if (location) GR_HIP(hipMemcpyAsync(location, sky->d_location + f, sizeof(int8_t) * c, hipMemcpyDeviceToHost, st));
+    if (rows) GR_HIP(hipMemcpyAsync(rows, sky->d_rows + 6 * f, sizeof(double) * 6 * c, hipMemcpyDeviceToHost, st));
+    if (refined || refined_children) {
+        if (!refined || !refined_children) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_download: refined and refined_children come together");
+        if (first_cell < 10 || (first_cell - 10) % 9 != 0 || count % 9 != 0)
+            return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_download: the refined cells are told from first_cell = 10 + 9 k on, nine cells at a time");
+        const int64_t groups = count / 9;
+        if ((rc = ensure(&sky->d_tmp, &sky->tmp_bytes, sizeof(int64_t) * 10 * (size_t)groups)) != GR_OK) return rc;
+        int64_t* d_ref = (int64_t*)sky->d_tmp;
+        hipLaunchKernelGGL(k_sky_refined, dim3(sky_blocks(groups)), dim3(256), 0, st, sky_grid(sky), first_cell, groups, d_ref, d_ref + groups);
+        GR_HIP(hipGetLastError());
+        GR_HIP(hipMemcpyAsync(refined, d_ref, sizeof(int64_t) * (size_t)groups, hipMemcpyDeviceToHost, st));
+        GR_HIP(hipMemcpyAsync(refined_children, d_ref + groups, sizeof(int64_t) * 9 * (size_t)groups, hipMemcpyDeviceToHost, st));
+    }
+    GR_HIP(hipStreamSynchronize(st));
+    return GR_OK;
 }

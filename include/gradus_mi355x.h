@@ -768,6 +768,71 @@ int32_t gr_sky_cells_device(gr_ctx* ctx, const gr_config* cfg, const gr_skycells
 int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_skycells* cells,
                            const gr_pointfunction* pf, double* out /* host, n x 6 */, gr_stats* stats /* n, or NULL */);
 
+/* ---- an adaptive sky resident on the device (added within ABI 8; AdaptiveSky, src/image-planes/adaptive-sky.jl, and the
+ * drivers of src/corona/adaptive-sample.jl:486-842) ----
+ * A gr_sky is the 3 x 3 refinement tree of Grids.AdaptiveGrid over (cos θ, ϕ) with one row of 6 doubles per cell, kept in the
+ * context's device memory between refinement steps: cells count from 1 in the order they were made, row 0 is a null cell, the
+ * children of the k-th cell of a refinement list take the indices n + 1 + 9 k ... n + 9 + 9 k (column order; the middle child
+ * inherits its parent's row), neighbours are (top, right, bottom, left).  It keeps COPIES of cfg, cells (x_src, Mx) and pf:
+ * the tables they point to must outlive the sky.  One context; the calls of one sky come from one thread at a time.
+ *
+ * A criterion decides per pair (leaf, bordering leaf) whether the BORDERING leaf is refined.  A pair of cells that both miss
+ * (NaN r) is always left alone.  GR_SKY_CRIT_DEFAULT: g or J of the two rows are not isapprox at rtol (false on NaN);
+ * GR_SKY_CRIT_FUNCTION: either row lies in one of the boxes; GR_SKY_CRIT_FINE: both of these; GR_SKY_CRIT_LEVEL: the bordering
+ * leaf's level is below `level`.  A box is an r interval and zero, one or two intervals of fmod(ϕ, 2π) (+ 2π where negative),
+ * every bound open or closed. */
+#define GR_SKY_MAX_BOXES 8
+enum { GR_SKY_CRIT_DEFAULT = 0, GR_SKY_CRIT_FUNCTION = 1, GR_SKY_CRIT_FINE = 2, GR_SKY_CRIT_LEVEL = 3 };
+typedef struct gr_sky_box {
+    double r_lo, r_hi;
+    double phi_lo[2], phi_hi[2];
+    int32_t r_open_lo, r_open_hi;      /* 1: the bound itself lies outside                                   */
+    int32_t phi_open_lo, phi_open_hi;  /* ... of every ϕ interval                                            */
+    int32_t n_phi;                     /* 0: any ϕ                                                           */
+    int32_t reserved;
+} gr_sky_box;
+typedef struct gr_sky_criterion {
+    int32_t kind;                      /* GR_SKY_CRIT_*                                                      */
+    int32_t level;                     /* GR_SKY_CRIT_LEVEL                                                  */
+    double rtol;                       /* percentage / 100                                                   */
+    int32_t n_boxes;                   /* 0 ... GR_SKY_MAX_BOXES                                             */
+    int32_t reserved;
+    gr_sky_box boxes[GR_SKY_MAX_BOXES];
+} gr_sky_criterion;
+typedef struct gr_sky gr_sky;
+/* The nine top cells over limits = (x1, x2, y1, y2); nothing is traced.  Refused as gr_sky_cells_device refuses. */
+int32_t gr_sky_create(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* source /* x_src, Mx */, const gr_pointfunction* pf,
+                      const double* limits /* 4 */, int32_t x_periodic, gr_sky** sky);
+int32_t gr_sky_destroy(gr_sky* sky);
+int32_t gr_sky_size(gr_sky* sky, int64_t* n_cells);
+/* trace_initial!: the nine cells, then every leaf refined level - 1 times; launch_sizes receives the cells each of the `level`
+ * launches traced (9, 72, 648 for level 3) */
+int32_t gr_sky_trace_initial(gr_sky* sky, int32_t level, int64_t* launch_sizes /* level, or NULL */);
+/* find_need_refine: the bordering leaves the criterion names, ascending, left in a device list; only their number comes back.
+ * gr_sky_need_refine_list copies that list out. */
+int32_t gr_sky_find_need_refine(gr_sky* sky, const gr_sky_criterion* criterion, int64_t* count);
+int32_t gr_sky_need_refine_list(gr_sky* sky, int64_t* cells /* host, count */);
+/* every (leaf, bordering leaf) pair in the reference's visiting order: leaves ascending, each with its bordering leaves top,
+ * right, bottom, left.  n receives their number; the pairs are written if cap >= n (i1, i2 may be NULL to ask for n only). */
+int32_t gr_sky_pairs(gr_sky* sky, int64_t* i1 /* host, cap */, int64_t* i2 /* host, cap */, int64_t cap, int64_t* n);
+/* refine_and_trace!: the list of the last gr_sky_find_need_refine (cells = NULL; n is ignored) or n cells of a host list.  The
+ * eight outer children of every cell are traced in ONE gr_sky_cells_device launch (`traced` receives its size).
+ * GR_ERR_INVALID_ARGUMENT, with the sky as it was, for an index outside 1 ... n_cells, a cell that is refined already, a cell
+ * named twice, a cell at level GR_SKY_MAX_LEVEL (20) and for cells = NULL without a list. */
+int32_t gr_sky_refine_and_trace(gr_sky* sky, const int64_t* cells /* host, n, or NULL */, int64_t n, int64_t* traced,
+                                gr_stats* stats);
+/* per (r, ϕ) bin the number of leaves that land in it (adaptive-sample.jl:337-348: r not NaN and not above the largest edge,
+ * the last edge <= r and <= fmod(ϕ, 2π)) and whose J g^Γ is not ±0; gamma = NULL leaves the redshift out.  bin_emissivity_grid
+ * is non-zero exactly in the bins counted here.  Integer sums: the same counts on every run. */
+int32_t gr_sky_occupancy(gr_sky* sky, const double* r_bins, int64_t n_r, const double* phi_bins, int64_t n_phi,
+                         const double* gamma /* 1, or NULL */, int64_t* counts /* host, n_r x n_phi */);
+/* the arrays of cells first_cell ... first_cell + count - 1 (row 0 included if first_cell = 0), and -- for first_cell >= 10,
+ * where every nine cells are the children of one refined cell -- those cells and their rows of `children` */
+int32_t gr_sky_download(gr_sky* sky, int64_t first_cell, int64_t count, double* pos /* count x 2 */, void* level /* count int32_t */,
+                        int64_t* children /* count x 9 */, int64_t* neighbours /* count x 4 */, int64_t* parent,
+                        void* location /* count int8_t */, double* rows /* count x 6 */, int64_t* refined /* count / 9, or NULL */,
+                        int64_t* refined_children /* count / 9 x 9, or NULL */);
+
 /* ---- tabulated metrics (ABI 7; segments, axis terms: ABI 8; GR_METRIC_TABULATED): the AbstractMetric plugin interface on the device ----
  * Host-only functions (no context, no device): plan a grid, learn its nodes, fit, check.
  *
