@@ -317,6 +317,7 @@ class gr_skycells(C.Structure):
 
 GR_SKY_MAX_BOXES = 8
 GR_SKY_CRIT_DEFAULT, GR_SKY_CRIT_FUNCTION, GR_SKY_CRIT_FINE, GR_SKY_CRIT_LEVEL = 0, 1, 2, 3
+GR_SKY_MAP_EMISSIVITY, GR_SKY_MAP_REDSHIFT, GR_SKY_MAP_TIME = 0, 1, 2
 
 
 class gr_sky_box(C.Structure):
@@ -448,6 +449,10 @@ EXPORTS = [
     "gr_sky_refine_and_trace",
     "gr_sky_occupancy",
     "gr_sky_download",
+    "gr_disc_area_factor_device",
+    "gr_disc_area_factor",
+    "gr_sky_bin_grid",
+    "gr_sky_fill",
     "gr_render_endpoints_multi",
     "gr_trace_endpoints_multi",
     "gr_rayset_endpoints_multi",
@@ -541,6 +546,10 @@ def load():
     L.gr_sky_refine_and_trace.argtypes = [vp, vp, i64, i64p, stp]
     L.gr_sky_occupancy.argtypes = [vp, vp, i64, vp, i64, vp, vp]
     L.gr_sky_download.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gr_disc_area_factor_device.argtypes = [vp, cfgp, pfp, vp, i64, vp, vp]
+    L.gr_disc_area_factor.argtypes = [vp, cfgp, pfp, vp, i64, vp]
+    L.gr_sky_bin_grid.argtypes = [vp, i32, vp, i64, vp, i64, vp, vp, vp]
+    L.gr_sky_fill.argtypes = [vp, vp, i64, vp, i64, vp, vp]
     L.gr_render_endpoints_multi.argtypes = [ctxa, i32, cfgp, plp, i64, vp, vp]
     L.gr_trace_endpoints_multi.argtypes = [ctxa, i32, cfgp, vp, i64, vp, i64, vp, vp]
     L.gr_rayset_endpoints_multi.argtypes = [ctxa, i32, cfgp, rsp, vp, vp]

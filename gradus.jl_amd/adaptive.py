@@ -16,7 +16,8 @@ with `np.isnan(sky.values["r"][i1])`.
 refinement and the census of the (r, ϕ) bins run there, `sky.grid` and `sky.values` are host mirrors brought up to date on
 first read after a change.  The criteria of this module carry a `gr_sky_criterion` where they can be written as one (the
 default criterion, `refine_to_level`, `refine_function` / `fine_refine_function` over `RadialBox`es); any other callable is
-evaluated on the mirror against the pair list the device returns.
+evaluated on the mirror against the pair list the device returns.  The maps and `fill_sky_values` read the mirror unless asked
+for `route="device"`, which forms them from the device's rows (`gr_sky_bin_grid`, `gr_sky_fill`) without a download.
 
 The drivers of adaptive-sample.jl:486-842 -- `empty_fraction`, `evaluate_refinement_metric`, `step_block`,
 `adaptive_solve` -- work on both kinds of sky.
@@ -407,6 +408,37 @@ class AdaptiveSky:
                                             gamma, C.c_void_p(counts.ctypes.data)))
         return counts
 
+    def device_bin_grid(self, what, r_bins, ϕ_bins, Γ=2, solid_angle=False):
+        """gr_sky_bin_grid: the (r, ϕ) map `what` ("emissivity", "redshift" or "time") of the resident sky, formed on the device
+        from its rows: Σ ΔΩ w / Σ ΔΩ per bin in order-independent integer sums -- the same bits on every call.  With
+        `solid_angle` also Σ ΔΩ.  Raises if the terms of a bin vanish below the resolution of the sums."""
+        import ctypes as C
+
+        from . import _lib
+
+        kinds = {"emissivity": _lib.GR_SKY_MAP_EMISSIVITY, "redshift": _lib.GR_SKY_MAP_REDSHIFT, "time": _lib.GR_SKY_MAP_TIME}
+        r_bins, ϕ_bins = np.ascontiguousarray(r_bins, dtype=np.float64), np.ascontiguousarray(ϕ_bins, dtype=np.float64)
+        out = np.zeros((r_bins.size, ϕ_bins.size))
+        ΔΩ = np.zeros_like(out) if solid_angle else None
+        gamma = None if Γ is None else C.byref(C.c_double(float(Γ)))
+        _lib.check(self._L.gr_sky_bin_grid(self._dev, kinds.get(what, what), C.c_void_p(r_bins.ctypes.data), r_bins.size,
+                                           C.c_void_p(ϕ_bins.ctypes.data), ϕ_bins.size, gamma, C.c_void_p(out.ctypes.data),
+                                           None if ΔΩ is None else C.c_void_p(ΔΩ.ctypes.data)))
+        return (out, ΔΩ) if solid_angle else out
+
+    def device_fill(self, ϕ_grid, θ_grid):
+        """gr_sky_fill: (rows[θ, ϕ], lower cell[θ, ϕ], upper cell[θ, ϕ]) of fill_sky_values, one workgroup per column"""
+        import ctypes as C
+
+        from . import _lib
+
+        ϕ_grid, θ_grid = np.ascontiguousarray(ϕ_grid, dtype=np.float64), np.ascontiguousarray(θ_grid, dtype=np.float64)
+        out = np.empty((θ_grid.size, ϕ_grid.size), dtype=SKY_DTYPE)
+        cells = np.empty((θ_grid.size, ϕ_grid.size, 2), dtype=np.int64)
+        _lib.check(self._L.gr_sky_fill(self._dev, C.c_void_p(ϕ_grid.ctypes.data), ϕ_grid.size, C.c_void_p(θ_grid.ctypes.data), θ_grid.size,
+                                       C.c_void_p(out.ctypes.data), C.c_void_p(cells.ctypes.data)))
+        return out, cells[..., 0].copy(), cells[..., 1].copy()
+
     def _append(self, rows):
         need = self.n_values + rows.size
         if need + 1 > self._values.size:
@@ -517,32 +549,53 @@ def unpack_sky(sky):
     return pos[:, 1].copy(), pos[:, 0].copy(), sky.values[leaves].copy()
 
 
-def fill_sky_values(sky, grid):
+def _device_route(sky, route):
+    """route = None / "host": the numpy code on sky.grid / sky.values; "device": the kernels, on a resident sky only"""
+    if route is None or route == "host":
+        return False
+    if route != "device":
+        raise ValueError(f'route must be None, "host" or "device", not {route!r}')
+    if not getattr(sky, "resident", False):
+        raise ValueError('route="device" needs a resident sky: AdaptiveSky(m, corona, d, resident=True)')
+    return True
+
+
+def fill_sky_values(sky, grid, route=None, cells=False):
     """fill_sky_values(sky, N) -> (ϕ grid, θ grid, rows[θ, ϕ]); fill_sky_values(sky, (ϕ grid, θ grid)) -> rows[θ, ϕ]
     (adaptive-sample.jl:196-250): per column of ϕ, the cells that hold the grid's points, sorted by θ and linearly interpolated.
     All six fields are averaged: the reference's _to_vector packs five of the six into a six-vector and so drops the status
-    (adaptive-sample.jl:28); a column with fewer than two cells (the reference indexes out of bounds there) is NaN."""
+    (adaptive-sample.jl:28); a column with fewer than two cells (the reference indexes out of bounds there) is NaN.
+    `cells=True` appends (lower cell[θ, ϕ], upper cell[θ, ϕ]) -- the two cells every point is interpolated between, 0 in a NaN
+    column -- to what is returned.  `route="device"` forms the image on a resident sky's device (gr_sky_fill) instead of
+    reading the mirror.  The θ grid may be in any order on both routes."""
     if np.isscalar(grid):
         ϕ_grid = np.linspace(-math.pi, math.pi, int(grid))
         θ_grid = np.linspace(0.0, math.pi, int(grid))
-        return ϕ_grid, θ_grid, fill_sky_values(sky, (ϕ_grid, θ_grid))
+        filled = fill_sky_values(sky, (ϕ_grid, θ_grid), route=route, cells=cells)
+        return (ϕ_grid, θ_grid) + (filled if cells else (filled,))
     ϕ_grid, θ_grid = (np.asarray(a, dtype=np.float64) for a in grid)
+    if _device_route(sky, route):
+        out, lower, upper = sky.device_fill(ϕ_grid, θ_grid)
+        return (out, (lower, upper)) if cells else out
     out = make_null(θ_grid.size * ϕ_grid.size).reshape(θ_grid.size, ϕ_grid.size)
+    lower, upper = (np.zeros(out.shape, dtype=np.int64) for _ in range(2))
     cosθ = np.cos(θ_grid)
     for k, ph in enumerate(ϕ_grid):
-        cells = {sky.grid.get_parent_index(c, ph) for c in cosθ}
-        cells.discard(0)
-        if len(cells) < 2:
+        held = {sky.grid.get_parent_index(c, ph) for c in cosθ}
+        held.discard(0)
+        if len(held) < 2:
             continue
-        cells = np.fromiter(cells, dtype=np.int64)
-        column = np.arccos(sky.grid.pos[cells, 0])
+        held = np.fromiter(held, dtype=np.int64)
+        column = np.arccos(sky.grid.pos[held, 0])
         order = np.argsort(column, kind="stable")
-        column, vals = column[order], sky.values[cells[order]]
+        column, held = column[order], held[order]
+        vals = sky.values[held]
         idx = np.clip(np.searchsorted(column, θ_grid, side="right"), 1, column.size - 1) - 1
         w = (θ_grid - column[idx]) / (column[idx + 1] - column[idx])
         for f in SKY_FIELDS:
             out[f][:, k] = (1.0 - w) * vals[f][idx] + w * vals[f][idx + 1]
-    return out
+        lower[:, k], upper[:, k] = held[idx], held[idx + 1]
+    return (out, (lower, upper)) if cells else out
 
 
 def _binned_cells(sky, r_bins, ϕ_bins):
@@ -574,9 +627,15 @@ def _bin_grid(sky, r_bins, ϕ_bins, weight):
     return output
 
 
-def bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky, Γ=2, ensemble=None):
+def bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky, Γ=2, ensemble=None, route=None):
     """bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky; Γ = 2) (adaptive-sample.jl:266-362): per (r, ϕ) bin the solid-angle
-    weighted mean of J g^Γ γ(r) A(r) over the leaves that land in it; Γ = None leaves the redshift out."""
+    weighted mean of J g^Γ γ(r) A(r) over the leaves that land in it; Γ = None leaves the redshift out.  `route="device"`: formed
+    on a resident sky's device (gr_sky_bin_grid; γ A by k_disc_area_factor with the sky's own ISCO and plunging table).  The two
+    routes agree to rounding (DESIGN_measurements.md §M33) with one exception: for KerrRefractive, at radii within 1.25 of its
+    corona_radius, the device's γ A carries ∂n/∂r of the refractive index and numpy's (metrics.KerrRefractive._components)
+    does not, so the maps differ by up to 1.6 % in the bins of those radii."""
+    if _device_route(sky, route):
+        return sky.device_bin_grid("emissivity", r_bins, ϕ_bins, Γ=Γ)
     from .corona import _plunging_table, _proper_area, keplerian_velocity_projector, lorentz_factor
 
     tracer = getattr(sky, "tracer", None)
@@ -606,13 +665,19 @@ def bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky, Γ=2, ensemble=None):
     return _bin_grid(sky, r_bins, ϕ_bins, weight)
 
 
-def bin_redshift_grid(r_bins, ϕ_bins, sky):
-    """bin_redshift_grid(r_bins, ϕ_bins, sky) (adaptive-sample.jl:364-406): the solid-angle weighted mean of g per bin"""
+def bin_redshift_grid(r_bins, ϕ_bins, sky, route=None):
+    """bin_redshift_grid(r_bins, ϕ_bins, sky) (adaptive-sample.jl:364-406): the solid-angle weighted mean of g per bin;
+    `route="device"`: on a resident sky's device"""
+    if _device_route(sky, route):
+        return sky.device_bin_grid("redshift", r_bins, ϕ_bins, Γ=None)
     return _bin_grid(sky, r_bins, ϕ_bins, lambda v: v["g"])
 
 
-def bin_time_grid(r_bins, ϕ_bins, sky):
-    """bin_time_grid(r_bins, ϕ_bins, sky) (adaptive-sample.jl:408-450): the solid-angle weighted mean of t per bin"""
+def bin_time_grid(r_bins, ϕ_bins, sky, route=None):
+    """bin_time_grid(r_bins, ϕ_bins, sky) (adaptive-sample.jl:408-450): the solid-angle weighted mean of t per bin;
+    `route="device"`: on a resident sky's device"""
+    if _device_route(sky, route):
+        return sky.device_bin_grid("time", r_bins, ϕ_bins, Γ=None)
     return _bin_grid(sky, r_bins, ϕ_bins, lambda v: v["t"])
 
 

@@ -889,6 +889,34 @@ def _plunging_table(m, ensemble):
     return _PLUNGING_TABLES[key]
 
 
+def disc_area_factor(m, r, *, ensemble=None, plunging="traced", r_isco=None):
+    """γ(r) A(r) of the disc in the equatorial plane on the device (gr_disc_area_factor): `lorentz_factor` of the Keplerian /
+    plunging disc velocity times `_proper_area`, what bin_emissivity_grid weights a leaf by.  `plunging`: the (r, v^t, v^r, v^ϕ)
+    table read inside `r_isco` (default: the traced table of `_plunging_table`, as every corona profile uses it; None: Kerr's
+    analytic plunge); radii inside the table's first row take that row."""
+    import ctypes as C
+
+    from . import _lib
+    from .pointfunctions import GR_PF_REDSHIFT, PointFunction
+    from .rendering import abi_pointfunction
+    from .tracing import tracing_configuration
+
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    config = tracing_configuration(m, np.array([0.0, 1000.0, math.pi / 2, 0.0]), np.zeros((1, 4)), None, (0.0, 1.0), ensemble=ensemble)
+    ens = config.ensemble
+    if isinstance(plunging, str):
+        plunging = _plunging_table(m, ens)
+    rpf = PointFunction(None, device_pf=GR_PF_REDSHIFT, extra={"r_isco": m.isco() if r_isco is None else float(r_isco), "plunge": plunging})
+    pf, keep_pf = abi_pointfunction(rpf)
+    cfg = config.abi_config()
+    out = np.empty(r.shape)
+    ctx = ens.contexts[0] if ens.multi else ens.ctx
+    _lib.check(_lib.load().gr_disc_area_factor(ctx.handle, C.byref(cfg), C.byref(pf), C.c_void_p(r.ctypes.data), r.size,
+                                               C.c_void_p(out.ctypes.data)))
+    del keep_pf
+    return out
+
+
 def device_radial_profile(m, d, model, spectrum=None, *, λmax=10_000.0, sampler=None, n_samples=1000, grid=None, N=100,
                           callback="default", ensemble=None, stats=False, **solver_args):
     """emissivity_profile(m, d, model, spectrum; n_samples, sampler, N, grid) (emissivity.jl:118-168) with the whole

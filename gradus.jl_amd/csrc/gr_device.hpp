@@ -2898,6 +2898,44 @@ GR_DEV real redshift_pf(const Metric& m, const Params& pp, const Cold& p, const 
     return E_obs * rcp_full(E_disc);
 }
 
+// γ(ρ) A(ρ) of the disc at θ = π/2 -- what bin_emissivity_grid weights a leaf by (adaptive-sample.jl:266-362): γ the Lorentz
+// factor of the disc's velocity in the LNRF (lorentz_factor, flux-calculations.jl:20-40: 𝒱^ϕ = √g_ϕϕ (v^ϕ - ω v^t) / (α v^t) with
+// ω = -g_tϕ / g_ϕϕ, α² = -g_tt + g_tϕ² / g_ϕϕ), A = 2π √(g_rr g_ϕϕ).  The velocity is the one redshift_pf above takes, branch by
+// branch: Keplerian from the ISCO out, inside it the plunging table clamped to its ends (or Kerr's analytic plunge when no table
+// came).  v^r does not enter.
+template <class Metric>
+GR_DEV real disc_area_factor(const Metric& m, const Params& pp, const Cold& p, real rho)
+{
+    real vt, vp;
+    const real isco = p.pf.r_isco;
+    if (rho < isco) {
+        if ((pp.cfg.metric_id == GR_METRIC_KERR) && (p.pf.n_plunge == 0)) {
+            const real M = pp.cfg.params[0], a = pp.cfg.params[1];
+            const real Le = kerr_plunge_Le(M, isco, a);
+            const real H = (2.0 * M * rho - a * Le) / (rho * rho - 2.0 * M * rho + a * a);
+            const real ge = GR_SQRT(1.0 - (2.0 * M) / (3.0 * isco));
+            vt = ge * (1.0 + 2.0 * M * (1.0 + H) / rho);
+            vp = ge / (rho * rho) * (Le + a * H);
+        } else {
+            real rb = rho;
+            const int64_t n = p.pf.n_plunge;
+            if (rb < p.pf.plunge_r[0]) rb = p.pf.plunge_r[0];
+            if (rb > p.pf.plunge_r[n - 1]) rb = p.pf.plunge_r[n - 1];
+            vt = nan_linear_interp(p.pf.plunge_r, p.pf.plunge_vt, n, rb);
+            vp = nan_linear_interp(p.pf.plunge_r, p.pf.plunge_vphi, n, rb);
+        }
+    } else {
+        circular_fourvelocity(m, rho, vt, vp);
+    }
+    real g[5];
+    metric_comps(m, rho, (real)1.5707963267948966, (real)1.0, (real)0.0, g);
+    const real om = -g[4] / g[3];
+    const real alpha = GR_SQRT(-g[0] + g[4] * g[4] / g[3]);
+    const real V = GR_SQRT(g[3]) * (vp - om * vt) / (alpha * vt);
+    const real gamma = 1.0 / GR_SQRT(1.0 - V * V);
+    return gamma * (6.283185307179586 * GR_SQRT(g[1] * g[3]));
+}
+
 // ---------------------------------------------------------------------------------------
 // Cold lane storage: LDS as the spill space the compiler does not have.
 //

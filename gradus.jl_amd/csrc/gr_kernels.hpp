@@ -528,6 +528,17 @@ __global__ void __launch_bounds__(256) k_apply_pf(const Params p, const gr_point
     out[i] = val;
 }
 
+// ---- γ(r) A(r) of the disc at n radii (disc_area_factor, gr_device.hpp): the weight of a resident sky's emissivity map ----
+template <class Metric>
+__global__ void __launch_bounds__(256) k_disc_area_factor(const Params p, const double* __restrict__ r, double* __restrict__ out)
+{
+    Metric m;
+    m.load(p.cfg);
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.n) return;
+    const double ri = r[i];
+    out[i] = (ri == ri) ? (double)disc_area_factor(m, p, *p.cold, (real)ri) : ri;      // (a NaN radius -- a miss -- costs nothing)
+}
 
 #ifndef GR_NO_LAUNCHER      // scripts/kernel_probe.sh instantiates single kernels without the dispatch table
 // launch knobs handed over by the host side (gr_ctx is not visible here)
@@ -642,6 +653,15 @@ hipError_t launch_apply_metric(const Params& p, const gr_point* pts, double max_
     const int block = 256;
     const int64_t grid = (p.n + block - 1) / block;
     hipLaunchKernelGGL((k_apply_pf<Metric>), dim3((unsigned)grid), dim3(block), 0, stream, p, pts, max_time, out);
+    return hipGetLastError();
+}
+
+template <class Metric>
+hipError_t launch_areafactor_metric(const Params& p, const double* r, double* out, hipStream_t stream)
+{
+    const int block = 256;
+    const int64_t grid = (p.n + block - 1) / block;
+    hipLaunchKernelGGL((k_disc_area_factor<Metric>), dim3((unsigned)grid), dim3(block), 0, stream, p, r, out);
     return hipGetLastError();
 }
 #endif  // GR_NO_LAUNCHER

@@ -9,10 +9,12 @@
 // has to be the one numpy makes from the same numbers, so nothing may be contracted into an fma (the library is built with
 // -ffp-contract=on): positions, widths and tolerances are formed with one rounding per operation, as numpy forms them.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
 #include "../../include/gradus_mi355x.h"
+#include "gr_lagbin.hpp"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -296,6 +298,134 @@ GR_SKY_DEV bool lights(const double* row, bool has_gamma, double gamma)
 {
     const double w = has_gamma ? row[4] * pow(row[3], gamma) : row[4];
     return !(w == 0.0);
+}
+
+// ---- the (r, ϕ) maps: adaptive._binned_cells / _bin_grid (adaptive-sample.jl:266-450) ----
+
+// ΔΩ of a leaf: wx wy / sin(acos(cos θ))
+GR_SKY_DEV double leaf_solid_angle(const Grid& g, int64_t cell)
+{
+    GR_SKY_NO_CONTRACT
+    double wx, wy;
+    cell_width(g, cell, wx, wy);
+    const double theta = acos(g.pos[2 * cell]);
+    const double a = wx * wy;
+    return a / sin(theta);
+}
+// what a leaf's ΔΩ is multiplied by: J (g^Γ γA) for the emissivity (`area` = γ(r) A(r) of the leaf's r), g, or t
+GR_SKY_DEV double map_weight(int what, const double* row, bool has_gamma, double gamma, double area)
+{
+    GR_SKY_NO_CONTRACT
+    if (what == GR_SKY_MAP_REDSHIFT) return row[3];
+    if (what == GR_SKY_MAP_TIME) return row[0];
+    const double redshift = has_gamma ? pow(row[3], gamma) : 1.0;
+    const double ra = redshift * area;
+    return row[4] * ra;
+}
+struct MapBins { const double* r_bins; int64_t nr; double r_max; const double* phi_bins; int64_t nphi; };
+// the bin of leaf c, its ΔΩ and its term ΔΩ w; false: the leaf is dropped.  area: γA per cell (emissivity only)
+GR_SKY_DEV bool map_term(const Grid& g, const double* rows, int64_t c, const MapBins& b, int what, bool has_gamma, double gamma,
+                         const double* area, int64_t& bin, double& solid, double& term)
+{
+    GR_SKY_NO_CONTRACT
+    int64_t ri, pi;
+    if (!bin_of(rows + 6 * c, b.r_bins, b.nr, b.r_max, b.phi_bins, b.nphi, ri, pi)) return false;
+    bin = ri * b.nphi + pi;
+    solid = leaf_solid_angle(g, c);
+    term = solid * map_weight(what, rows + 6 * c, has_gamma, gamma, what == GR_SKY_MAP_EMISSIVITY ? area[c] : 0.0);
+    return true;
+}
+
+// One leaf's share of its bin, for the kernel (k_sky_map_bin: `add` an integer atomic) and the host harness (a plain +=) alike.
+// acc: 4 x cells integers (Σ ΔΩ w hi / lo, Σ ΔΩ hi / lo) on the grids `st` / `ss`; `count(bin)`: one more non-zero finite term;
+// flag: 4 x cells bytes -- a NaN term, a +∞ term, a -∞ term, a ΔΩ that is not finite -- set by a plain store of 1 (idempotent)
+template <class Add, class Count>
+GR_SKY_DEV void map_accumulate(int64_t bin, double solid, double term, int64_t cells, const gr_lag::CoronaScale& st,
+                               const gr_lag::CoronaScale& ss, uint8_t* flag, Add&& add, Count&& count)
+{
+    if (!(fabs(solid) < INFINITY)) {
+        flag[bin] = 1;
+        flag[3 * cells + bin] = 1;
+        return;
+    }
+    long long hi, lo;
+    gr_lag::corona_split(solid, ss, hi, lo);
+    add(2 * cells + bin, hi);
+    add(3 * cells + bin, lo);
+    if (term != term) flag[bin] = 1;
+    else if (term == INFINITY) flag[cells + bin] = 1;
+    else if (term == -INFINITY) flag[2 * cells + bin] = 1;
+    else if (term != 0.0) {
+        gr_lag::corona_split(term, st, hi, lo);
+        add(bin, hi);
+        add(cells + bin, lo);
+        count(bin);
+    }
+}
+
+// what the sums and the flags of a bin stand for: Σ ΔΩ w / Σ ΔΩ where Σ ΔΩ > 0 -- `output[lit] /= solid_angle[lit]`, a bin
+// without leaves keeps its 0 -- with the NaN and ±∞ np.add.at would have summed to.  Host only (long double, gr_lag::corona_sum).
+inline void map_bin_value(double num, double den, const uint8_t flags[4], double& value, double& solid)
+{
+    if (flags[3]) den = NAN;
+    if (flags[0] || (flags[1] && flags[2])) num = NAN;
+    else if (flags[1]) num = INFINITY;
+    else if (flags[2]) num = -INFINITY;
+    value = den > 0.0 ? num / den : num;
+    solid = den;
+}
+// The last pass of gr_sky_bin_grid over what map_accumulate left: out (and solid_angle, may be null) per bin.  Returns the number
+// of bins that hold non-zero terms, no NaN, and sum to 0: terms below the resolution gt.step * gt.lo_unit of the sums.
+inline int64_t map_finish(const long long* acc, const unsigned int* cnt, const uint8_t* flag, int64_t cells, const gr_lag::CoronaGrid& gt,
+                          const gr_lag::CoronaGrid& gs, double* out, double* solid_angle)
+{
+    int64_t vanished = 0;
+    for (int64_t k = 0; k < cells; ++k) {
+        const uint8_t f[4] = { flag[k], flag[cells + k], flag[2 * cells + k], flag[3 * cells + k] };
+        double v, den;
+        map_bin_value(gr_lag::corona_sum(acc[k], acc[cells + k], gt), gr_lag::corona_sum(acc[2 * cells + k], acc[3 * cells + k], gs), f, v, den);
+        if (cnt[k] > 0 && v == 0.0) ++vanished;
+        out[k] = v;
+        if (solid_angle) solid_angle[k] = den;
+    }
+    return vanished;
+}
+
+// ---- the filled image: adaptive.fill_sky_values (adaptive-sample.jl:196-250), one column ϕ at a time ----
+
+// the scan operator that carries the last non-zero cell along a column
+GR_SKY_DEV int64_t last_nonzero(int64_t a, int64_t b) { return b != 0 ? b : a; }
+// is point j the first of its cell's run -- a cell, and not the one the last non-zero point before it holds?
+GR_SKY_DEV bool first_of_run(int64_t cell, int64_t previous_nonzero) { return cell != 0 && cell != previous_nonzero; }
+
+// The order gr_sky_fill walks a θ grid in: ascending, NaN last, equal values in the caller's order -- a column then meets its cells
+// in ascending θ whatever order the caller's grid has.  perm[k]: the caller's index of the k-th point.  Host only.
+inline void theta_order(const double* theta, int64_t n, int64_t* perm)
+{
+    for (int64_t j = 0; j < n; ++j) perm[j] = j;
+    std::stable_sort(perm, perm + n, [&](int64_t a, int64_t b) {
+        const double x = theta[a], y = theta[b];
+        return (x == x) && (!(y == y) || x < y);
+    });
+}
+
+// point θ of a column of m >= 2 cells (`cells`, their θ ascending in `column`): the interval of np.searchsorted(column, θ,
+// side = "right") clipped to [1, m - 1], the two cells, and the six fields (1 - w) v1 + w v2 as numpy rounds them
+GR_SKY_DEV void fill_point(const double* column, const int64_t* cells, int64_t m, const double* rows, double theta, double* out,
+                           int64_t& lower, int64_t& upper)
+{
+    GR_SKY_NO_CONTRACT
+    int64_t k = count_le(column, m, theta);
+    k = (k < 1 ? 1 : (k > m - 1 ? m - 1 : k)) - 1;
+    lower = cells[k];
+    upper = cells[k + 1];
+    const double num = theta - column[k], den = column[k + 1] - column[k];
+    const double w = num / den, u = 1.0 - w;
+    const double *v1 = rows + 6 * lower, *v2 = rows + 6 * upper;
+    for (int q = 0; q < 6; ++q) {
+        const double a = u * v1[q], b = w * v2[q];
+        out[q] = a + b;
+    }
 }
 
 }  // namespace gr_skygrid

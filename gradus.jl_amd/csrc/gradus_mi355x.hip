@@ -47,7 +47,8 @@ using namespace gr;
     hipError_t grts1_launch_trace_m##ID(int, int, int, int, unsigned long long*, const void*, hipStream_t);            \
     hipError_t gr64_launch_path_m##ID(const void*, double*, int64_t, unsigned long long*, hipStream_t);                \
     hipError_t gr64_launch_apply_m##ID(const void*, const gr_point*, double, double*, hipStream_t);                     \
-    hipError_t gr64_launch_classify_m##ID(const void*, uint8_t*, int64_t, hipStream_t);
+    hipError_t gr64_launch_classify_m##ID(const void*, uint8_t*, int64_t, hipStream_t);                                \
+    hipError_t gr64_launch_areafactor_m##ID(const void*, const double*, double*, hipStream_t);
 GR_DECLARE_METRIC(0) GR_DECLARE_METRIC(1) GR_DECLARE_METRIC(2) GR_DECLARE_METRIC(3) GR_DECLARE_METRIC(4) GR_DECLARE_METRIC(5)
 GR_DECLARE_METRIC(6) GR_DECLARE_METRIC(7) GR_DECLARE_METRIC(8) GR_DECLARE_METRIC(9) GR_DECLARE_METRIC(10)
 #undef GR_DECLARE_METRIC
@@ -61,6 +62,7 @@ hipError_t grts1_launch_trace_m11(int, int, int, int, unsigned long long*, const
 hipError_t gr64_launch_path_m11(const void*, double*, int64_t, unsigned long long*, hipStream_t);
 hipError_t gr64_launch_apply_m11(const void*, const gr_point*, double, double*, hipStream_t);
 hipError_t gr64_launch_classify_m11(const void*, uint8_t*, int64_t, hipStream_t);
+hipError_t gr64_launch_areafactor_m11(const void*, const double*, double*, hipStream_t);
 static_assert(GR_METRIC_NOZ == 10 && GR_METRIC_TABULATED == 11, "one kernel object per metric id 0..11: extend the tables below with the catalogue");
 
 namespace {
@@ -75,6 +77,7 @@ typedef hipError_t (*trace_fn)(int, int, int, int, unsigned long long*, const vo
 typedef hipError_t (*path_fn)(const void*, double*, int64_t, unsigned long long*, hipStream_t);
 typedef hipError_t (*apply_fn)(const void*, const gr_point*, double, double*, hipStream_t);
 typedef hipError_t (*classify_fn)(const void*, uint8_t*, int64_t, hipStream_t);
+typedef hipError_t (*areafactor_fn)(const void*, const double*, double*, hipStream_t);
 #define GR_ROW(F, LAST) { F##0, F##1, F##2, F##3, F##4, F##5, F##6, F##7, F##8, F##9, F##10, LAST }
 const trace_fn kTrace64[12] = GR_ROW(gr64_launch_trace_m, gr64_launch_trace_m11);
 const trace_fn kTrace32[12] = GR_ROW(gr32_launch_trace_m, gr32_launch_trace_m11);
@@ -85,6 +88,7 @@ const trace_fn kTraceSky1[12] = GR_ROW(grts1_launch_trace_m, grts1_launch_trace_
 const path_fn kPath64[12] = GR_ROW(gr64_launch_path_m, gr64_launch_path_m11);
 const apply_fn kApply64[12] = GR_ROW(gr64_launch_apply_m, gr64_launch_apply_m11);
 const classify_fn kClassify64[12] = GR_ROW(gr64_launch_classify_m, gr64_launch_classify_m11);      // the live-first tile order's flags (gr_tile_order.hpp)
+const areafactor_fn kAreaFactor64[12] = GR_ROW(gr64_launch_areafactor_m, gr64_launch_areafactor_m11);      // γ(r) A(r) of the disc (kernelsarea_m<id>.o)
 #undef GR_ROW
 // Metric::kEscapeRadiusM per metric id, in units of params[0] (escape_cull_radius)
 #define GR_ESC(ID) MetricOf<ID>::type::kEscapeRadiusM
@@ -1594,6 +1598,40 @@ int32_t gr_apply_pointfunction_device(gr_ctx* ctx, const gr_config* cfg, const g
     return GR_OK;
 }
 
+// γ(r) A(r) of the disc at n radii (k_disc_area_factor): the velocity branches are those of the REDSHIFT point function, so pf is
+// staged as a launch of it stages it
+int32_t gr_disc_area_factor_device(gr_ctx* ctx, const gr_config* cfg, const gr_pointfunction* pf, const double* d_r, int64_t n,
+                                   double* d_out, void* hip_stream)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc;
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "n must be non-negative");
+    if (n > 0 && (!d_r || !d_out)) return fail(GR_ERR_INVALID_ARGUMENT, "r/out is null");
+    if (!pf || pf->pf_id != GR_PF_REDSHIFT)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_disc_area_factor: the disc's velocity is the redshift point function's: pf->pf_id must be GR_PF_REDSHIFT");
+    GR_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    Params p;
+    Cold cd;
+    std::memset(&p, 0, sizeof p);
+    std::memset(&cd, 0, sizeof cd);
+    p.cfg = *cfg;
+    p.n = n;
+    if ((rc = stage_pf(ctx, cfg, pf, cd.pf, stream)) != GR_OK) return rc;
+    const bool tables = cd.pf.n_plunge > 0 || cfg->metric_id == GR_METRIC_TABULATED;
+    if (n == 0) return GR_OK;
+    if ((rc = stage_metric_table(ctx, p, stream)) != GR_OK) return rc;
+    Cold* slot = ctx->d_cold + ctx->cold_next;
+    ctx->cold_next = (ctx->cold_next + 1) % ctx->queue_slots;
+    GR_HIP(hipMemcpyAsync(slot, &cd, sizeof(Cold), hipMemcpyHostToDevice, stream));
+    p.cold = slot;
+    GR_HIP(kAreaFactor64[cfg->metric_id](&p, d_r, d_out, stream));
+    GR_HIP(hipGetLastError());
+    if (tables && (rc = tables_release(ctx, stream)) != GR_OK) return rc;
+    return GR_OK;
+}
+
 static void prefault_output(void* dst, size_t bytes, bool huge);
 
 int32_t gr_trace_paths(gr_ctx* ctx, const gr_config* cfg, const double* x, int64_t x_stride, const double* v, int64_t n,
@@ -2447,6 +2485,23 @@ int32_t gr_apply_pointfunction(gr_ctx* ctx, const gr_config* cfg, const gr_point
     if ((rc = gr_apply_pointfunction_device(ctx, cfg, pf, (const gr_point*)ctx->d_in, n, max_time,
                                             (double*)ctx->d_scratch, ctx->stream)) != GR_OK) return rc;
     if (n > 0) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
+    return GR_OK;
+}
+
+int32_t gr_disc_area_factor(gr_ctx* ctx, const gr_config* cfg, const gr_pointfunction* pf, const double* r, int64_t n, double* out)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "n must be non-negative");
+    if (n > 0 && (!r || !out)) return fail(GR_ERR_INVALID_ARGUMENT, "r/out is null");
+    int32_t rc;
+    const size_t bytes = sizeof(double) * (size_t)n;
+    GR_HIP(hipSetDevice(ctx->device));
+    if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
+    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
+    if (n > 0) GR_HIP(hipMemcpyAsync(ctx->d_in, r, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = gr_disc_area_factor_device(ctx, cfg, pf, (const double*)ctx->d_in, n, (double*)ctx->d_scratch, ctx->stream)) != GR_OK) return rc;
+    if (n > 0) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
     GR_HIP(hipStreamSynchronize(ctx->stream));
     return GR_OK;
 }
@@ -4695,6 +4750,154 @@ __global__ void __launch_bounds__(256) k_sky_occupancy(const gr_skygrid::Grid g,
     }
 }
 
+// ---- the (r, ϕ) maps: gr_sky_bin_grid.  The arithmetic per leaf is gr_skygrid.hpp (map_term), the sums are the two-integer
+// fixed-point sums of gr_lagbin.hpp: integer atomics, so a map is the same bits on every run and for every grid size ----
+
+// r of every cell, contiguous and indexed by cell, for the γA launch (k_disc_area_factor).  Indexing by cell keeps a compaction
+// (a scan and a wait) out of the call; row 0 and the interior cells are given NaN, which the launch passes through without
+// evaluating the metric, as it does the leaves that missed the disc.
+__global__ void __launch_bounds__(256) k_sky_radii(const gr_skygrid::Grid g, const double* __restrict__ rows, double* __restrict__ r)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c <= g.n; c += (int64_t)gridDim.x * 256)
+        r[c] = (c >= 1 && gr_skygrid::is_leaf(g, c)) ? rows[6 * c + 1] : NAN;
+}
+
+// red[0] = max |ΔΩ w|, red[1] = max ΔΩ over the leaves that land in a bin, as the bits of non-negative doubles (a NaN or an
+// infinite value adds nothing).  Per-wave reduction, then one pair of atomics per workgroup (k_lag_extrema).
+__global__ void __launch_bounds__(256) k_sky_map_extrema(const gr_skygrid::Grid g, const double* __restrict__ rows, const gr_skygrid::MapBins b, int what,
+                                                         int has_gamma, double gamma, const double* __restrict__ area, unsigned long long* red)
+{
+    unsigned long long mt = 0ull, ms = 0ull;
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x + 1; c <= g.n; c += (int64_t)gridDim.x * 256) {
+        if (!gr_skygrid::is_leaf(g, c)) continue;
+        int64_t bin;
+        double solid, term;
+        if (!gr_skygrid::map_term(g, rows, c, b, what, has_gamma != 0, gamma, area, bin, solid, term)) continue;
+        const double at = fabs(term), as = fabs(solid);
+        const unsigned long long bt = at < INFINITY ? (unsigned long long)__double_as_longlong(at) : 0ull;
+        const unsigned long long bs = as < INFINITY ? (unsigned long long)__double_as_longlong(as) : 0ull;
+        mt = bt > mt ? bt : mt;
+        ms = bs > ms ? bs : ms;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long t2 = __shfl_down(mt, off, 64), s2 = __shfl_down(ms, off, 64);
+        mt = t2 > mt ? t2 : mt;
+        ms = s2 > ms ? s2 : ms;
+    }
+    __shared__ unsigned long long part[4][2];
+    if ((threadIdx.x & 63) == 0) {
+        part[threadIdx.x >> 6][0] = mt;
+        part[threadIdx.x >> 6][1] = ms;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            mt = part[k][0] > mt ? part[k][0] : mt;
+            ms = part[k][1] > ms ? part[k][1] : ms;
+        }
+        if (mt) atomicMax(red, mt);
+        if (ms) atomicMax(red + 1, ms);
+    }
+}
+
+// Every kept leaf's share of its bin (gr_skygrid::map_accumulate): acc 4 x cells integers, cnt the non-zero finite terms per bin,
+// flag 4 x cells bytes set by plain stores of 1 (the idiom of k_sky_mark_need)
+__global__ void __launch_bounds__(256) k_sky_map_bin(const gr_skygrid::Grid g, const double* __restrict__ rows, const gr_skygrid::MapBins b, int what,
+                                                     int has_gamma, double gamma, const double* __restrict__ area, gr_lag::CoronaScale st, gr_lag::CoronaScale ss,
+                                                     int64_t cells, unsigned long long* acc, unsigned int* cnt, uint8_t* flag)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x + 1; c <= g.n; c += (int64_t)gridDim.x * 256) {
+        if (!gr_skygrid::is_leaf(g, c)) continue;
+        int64_t bin;
+        double solid, term;
+        if (!gr_skygrid::map_term(g, rows, c, b, what, has_gamma != 0, gamma, area, bin, solid, term)) continue;
+        if (bin < 0 || bin >= cells) continue;
+        gr_skygrid::map_accumulate(bin, solid, term, cells, st, ss, flag,
+                                   [&](int64_t at, long long v) { atomicAdd(acc + at, (unsigned long long)v); },
+                                   [&](int64_t at) { atomicAdd(cnt + at, 1u); });
+    }
+}
+
+// ---- the filled image: gr_sky_fill.  One workgroup per column ϕ_k: the cell of every point (cos θ_j, ϕ_k) into a scratch column,
+// the first point of every run of one cell compacted (two block scans that carry across chunks of 256 points, as k_sky_scan_apply
+// does: the last non-zero cell before a point, then the number of first points before it), then every point searches the
+// compacted column.  A fixed-ϕ line meets the disjoint rectangles of the leaves in contiguous runs, ordered in cos θ, so the
+// compacted column IS the sorted set of the reference; the kernel checks that its θ ascend strictly and raises `flag` if not. ----
+__global__ void __launch_bounds__(256) k_sky_fill(const gr_skygrid::Grid g, const double* __restrict__ rows, const double* __restrict__ phi,
+                                                  const double* __restrict__ theta, const double* __restrict__ cos_theta, int64_t n_theta,
+                                                  int64_t n_phi, const int64_t* __restrict__ perm, int64_t* idx_all, int64_t* comp_all, double* col_all,
+                                                  double* out, int64_t* cells_out, int32_t* flag)
+{
+    __shared__ int64_t s[256];
+    __shared__ int64_t carry_cell, carry_count;
+    const int tid = threadIdx.x;
+    for (int64_t k = blockIdx.x; k < n_phi; k += gridDim.x) {      // (uniform over the block)
+        int64_t* idx = idx_all + k * n_theta;
+        int64_t* comp = comp_all + k * n_theta;
+        double* col = col_all + k * n_theta;
+        const double ph = phi[k];
+        for (int64_t j = tid; j < n_theta; j += 256) idx[j] = gr_skygrid::parent_index(g, cos_theta[j], ph);
+        if (tid == 0) {
+            carry_cell = 0;
+            carry_count = 0;
+        }
+        __syncthreads();
+        for (int64_t t = 0; t < n_theta; t += 256) {
+            const int64_t j = t + tid;
+            const int64_t c = j < n_theta ? idx[j] : 0;
+            s[tid] = c;
+            __syncthreads();
+            for (int d = 1; d < 256; d <<= 1) {
+                const int64_t y = tid >= d ? s[tid - d] : 0;
+                __syncthreads();
+                s[tid] = gr_skygrid::last_nonzero(y, s[tid]);
+                __syncthreads();
+            }
+            const int64_t last = s[tid];
+            const int64_t before = gr_skygrid::last_nonzero(carry_cell, tid > 0 ? s[tid - 1] : 0);
+            const int64_t first = gr_skygrid::first_of_run(c, before) ? 1 : 0;
+            const int64_t base = carry_count;
+            __syncthreads();
+            s[tid] = first;
+            __syncthreads();
+            for (int d = 1; d < 256; d <<= 1) {
+                const int64_t y = tid >= d ? s[tid - d] : 0;
+                __syncthreads();
+                s[tid] += y;
+                __syncthreads();
+            }
+            const int64_t incl = s[tid];
+            if (first) {
+                const int64_t at = base + incl - 1;      // (at < n_theta: at most one first point per point)
+                comp[at] = c;
+                col[at] = acos(g.pos[2 * c]);
+            }
+            __syncthreads();
+            if (tid == 255) {
+                carry_cell = gr_skygrid::last_nonzero(carry_cell, last);
+                carry_count = base + incl;
+            }
+            __syncthreads();
+        }
+        const int64_t m = carry_count;
+        for (int64_t q = tid; q + 1 < m; q += 256)
+            if (!(col[q] < col[q + 1])) *flag = 1;
+        for (int64_t j = tid; j < n_theta; j += 256) {
+            const int64_t at = perm[j] * n_phi + k;      // θ ascends along j (gr_skygrid::theta_order); the point is the caller's perm[j]
+            double* o = out + 6 * at;
+            int64_t lower = 0, upper = 0;
+            if (m < 2) {
+                for (int q = 0; q < 6; ++q) o[q] = NAN;
+            } else {
+                gr_skygrid::fill_point(col, comp, m, rows, theta[j], o, lower, upper);
+            }
+            cells_out[2 * at] = lower;
+            cells_out[2 * at + 1] = upper;
+        }
+        __syncthreads();      // (the carries are reset for the next column)
+    }
+}
+
 // the cells refined since a download and their rows of `children`: every nine cells from `first` on share a parent
 __global__ void __launch_bounds__(256) k_sky_refined(const gr_skygrid::Grid g, int64_t first, int64_t groups, int64_t* __restrict__ refined,
                                                      int64_t* __restrict__ kids)
@@ -5101,6 +5304,144 @@ int32_t gr_sky_occupancy(gr_sky* sky, const double* r_bins, int64_t n_r, const d
     GR_HIP(hipMemcpyAsync(h.data(), d_c, sizeof(unsigned int) * cells, hipMemcpyDeviceToHost, st));
     GR_HIP(hipStreamSynchronize(st));
     for (size_t k = 0; k < cells; ++k) counts[k] = (int64_t)h[k];
+    return GR_OK;
+}
+
+int32_t gr_sky_bin_grid(gr_sky* sky, int32_t what, const double* r_bins, int64_t n_r, const double* phi_bins, int64_t n_phi, const double* gamma,
+                        double* out, double* solid_angle)
+{
+    // refusals first: nothing has touched the device when one is found
+    if (!sky) return fail(GR_ERR_INVALID_ARGUMENT, "sky is null");
+    if (!r_bins || !phi_bins || !out || n_r < 1 || n_phi < 1 || n_r > 46340 || n_phi > 46340)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_bin_grid: r_bins / phi_bins / out is null, or a count outside 1 ... 46340");
+    if (what < GR_SKY_MAP_EMISSIVITY || what > GR_SKY_MAP_TIME) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_bin_grid: unknown map (GR_SKY_MAP_*)");
+    if (!sky->traced) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_bin_grid: the sky has not been traced (gr_sky_trace_initial comes first)");
+    for (int64_t k = 1; k < n_r; ++k)
+        if (!(r_bins[k] >= r_bins[k - 1])) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_bin_grid: the r edges must ascend");
+    for (int64_t k = 1; k < n_phi; ++k)
+        if (!(phi_bins[k] >= phi_bins[k - 1])) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_bin_grid: the ϕ edges must ascend");
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    hipStream_t st = sky->ctx->stream;
+    const size_t cells = (size_t)n_r * (size_t)n_phi, n_rows = (size_t)sky->n + 1;
+    const bool emissivity = what == GR_SKY_MAP_EMISSIVITY;
+    // edges | per-cell r and γA (emissivity) | max |term|, max ΔΩ | 4 x cells sums | cells counts | 4 x cells flags
+    const size_t work = sizeof(unsigned long long) * (2 + 4 * cells) + sizeof(unsigned int) * cells + 4 * cells;
+    if ((rc = ensure(&sky->d_tmp, &sky->tmp_bytes, sizeof(double) * ((size_t)(n_r + n_phi) + (emissivity ? 2 * n_rows : 0)) + work)) != GR_OK) return rc;
+    double* d_r = (double*)sky->d_tmp;
+    double* d_p = d_r + n_r;
+    double* d_rad = d_p + n_phi;
+    double* d_area = emissivity ? d_rad + n_rows : nullptr;
+    unsigned long long* d_red = (unsigned long long*)(d_rad + (emissivity ? 2 * n_rows : 0));
+    unsigned long long* d_acc = d_red + 2;
+    unsigned int* d_cnt = (unsigned int*)(d_acc + 4 * cells);
+    uint8_t* d_flag = (uint8_t*)(d_cnt + cells);
+    gr_skygrid::MapBins b;
+    b.r_bins = d_r;
+    b.nr = n_r;
+    b.r_max = r_bins[0];
+    for (int64_t k = 1; k < n_r; ++k) b.r_max = r_bins[k] > b.r_max ? r_bins[k] : b.r_max;
+    b.phi_bins = d_p;
+    b.nphi = n_phi;
+    GR_HIP(hipMemcpyAsync(d_r, r_bins, sizeof(double) * (size_t)n_r, hipMemcpyHostToDevice, st));
+    GR_HIP(hipMemcpyAsync(d_p, phi_bins, sizeof(double) * (size_t)n_phi, hipMemcpyHostToDevice, st));
+    GR_HIP(hipMemsetAsync(d_red, 0, work, st));
+    const gr_skygrid::Grid g = sky_grid(sky);
+    if (emissivity) {
+        hipLaunchKernelGGL(k_sky_radii, dim3(sky_blocks((int64_t)n_rows)), dim3(256), 0, st, g, (const double*)sky->d_rows, d_rad);
+        GR_HIP(hipGetLastError());
+        if ((rc = gr_disc_area_factor_device(sky->ctx, &sky->cfg, &sky->pf, d_rad, (int64_t)n_rows, d_area, st)) != GR_OK) return rc;
+    }
+    const int has_gamma = gamma ? 1 : 0;
+    const double gam = gamma ? *gamma : 0.0;
+    hipLaunchKernelGGL(k_sky_map_extrema, dim3(sky_blocks(sky->n)), dim3(256), 0, st, g, (const double*)sky->d_rows, b, (int)what, has_gamma, gam,
+                       (const double*)d_area, d_red);
+    GR_HIP(hipGetLastError());
+    unsigned long long red[2] = { 0ull, 0ull };
+    GR_HIP(hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    double vmax[2];
+    std::memcpy(vmax, red, sizeof vmax);
+    const gr_lag::CoronaGrid gt = gr_lag::corona_grid(vmax[0], sky->n), gs = gr_lag::corona_grid(vmax[1], sky->n);
+    hipLaunchKernelGGL(k_sky_map_bin, dim3(sky_blocks(sky->n)), dim3(256), 0, st, g, (const double*)sky->d_rows, b, (int)what, has_gamma, gam,
+                       (const double*)d_area, gt.sc, gs.sc, (int64_t)cells, d_acc, d_cnt, d_flag);
+    GR_HIP(hipGetLastError());
+    std::vector<long long> acc;
+    std::vector<unsigned int> cnt;
+    std::vector<uint8_t> flag;
+    try {
+        acc.resize(4 * cells);
+        cnt.resize(cells);
+        flag.resize(4 * cells);
+    } catch (...) {
+        return fail(GR_ERR_OUT_OF_MEMORY, "gr_sky_bin_grid: out of memory");
+    }
+    GR_HIP(hipMemcpyAsync(acc.data(), d_acc, sizeof(long long) * 4 * cells, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned int) * cells, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipMemcpyAsync(flag.data(), d_flag, 4 * cells, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    const int64_t vanished = gr_skygrid::map_finish(acc.data(), cnt.data(), flag.data(), (int64_t)cells, gt, gs, out, solid_angle);
+    if (vanished) {
+        char text[320];
+        std::snprintf(text, sizeof text, "gr_sky_bin_grid: %lld bins hold non-zero terms that all lie below the resolution %.3g of the fixed-point sums "
+                                         "(the map's largest term is %.3g): the dynamic range of the terms is too wide, and the map would be 0 where "
+                                         "gr_sky_occupancy counts", (long long)vanished, gt.step * gt.lo_unit, vmax[0]);
+        return fail(GR_ERR_UNSUPPORTED, text);
+    }
+    return GR_OK;
+}
+
+int32_t gr_sky_fill(gr_sky* sky, const double* phi_grid, int64_t n_phi, const double* theta_grid, int64_t n_theta, double* out, int64_t* cells)
+{
+    if (!sky) return fail(GR_ERR_INVALID_ARGUMENT, "sky is null");
+    if (!phi_grid || !theta_grid || !out || n_phi < 1 || n_theta < 1 || n_phi > 46340 || n_theta > 46340)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill: phi_grid / theta_grid / out is null, or a count outside 1 ... 46340");
+    if (!sky->traced) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill: the sky has not been traced (gr_sky_trace_initial comes first)");
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    hipStream_t st = sky->ctx->stream;
+    const size_t points = (size_t)n_theta * (size_t)n_phi;
+    std::vector<double> grids;
+    std::vector<int64_t> perm;
+    try {
+        grids.resize((size_t)n_phi + 2 * (size_t)n_theta);
+        perm.resize((size_t)n_theta);
+    } catch (...) {
+        return fail(GR_ERR_OUT_OF_MEMORY, "gr_sky_fill: out of memory");
+    }
+    // ϕ | θ ascending | cos θ (formed here, as the reference forms them on the host) | the caller's index of every θ | out | column θ |
+    // cells of the points | compacted cells | cells out | flag
+    gr_skygrid::theta_order(theta_grid, n_theta, perm.data());
+    std::memcpy(grids.data(), phi_grid, sizeof(double) * (size_t)n_phi);
+    for (int64_t j = 0; j < n_theta; ++j) {
+        const double th = theta_grid[perm[(size_t)j]];
+        grids[(size_t)(n_phi + j)] = th;
+        grids[(size_t)(n_phi + n_theta + j)] = std::cos(th);
+    }
+    const size_t bytes = sizeof(double) * (grids.size() + 7 * points) + sizeof(int64_t) * (perm.size() + 4 * points) + 16;
+    if ((rc = ensure(&sky->d_tmp, &sky->tmp_bytes, bytes)) != GR_OK) return rc;
+    double* d_phi = (double*)sky->d_tmp;
+    double* d_theta = d_phi + n_phi;
+    double* d_cos = d_theta + n_theta;
+    int64_t* d_perm = (int64_t*)(d_cos + n_theta);
+    double* d_out = (double*)(d_perm + n_theta);
+    double* d_col = d_out + 6 * points;
+    int64_t* d_idx = (int64_t*)(d_col + points);
+    int64_t* d_comp = d_idx + points;
+    int64_t* d_cells = d_comp + points;
+    int32_t* d_flag = (int32_t*)(d_cells + 2 * points);
+    GR_HIP(hipMemcpyAsync(d_phi, grids.data(), sizeof(double) * grids.size(), hipMemcpyHostToDevice, st));
+    GR_HIP(hipMemcpyAsync(d_perm, perm.data(), sizeof(int64_t) * perm.size(), hipMemcpyHostToDevice, st));
+    GR_HIP(hipMemsetAsync(d_flag, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_sky_fill, dim3((unsigned)n_phi), dim3(256), 0, st, sky_grid(sky), (const double*)sky->d_rows,
+                       (const double*)d_phi, (const double*)d_theta, (const double*)d_cos, n_theta, n_phi, (const int64_t*)d_perm, d_idx, d_comp, d_col, d_out, d_cells, d_flag);
+    GR_HIP(hipGetLastError());
+    int32_t why = 0;
+    GR_HIP(hipMemcpyAsync(&why, d_flag, sizeof why, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipMemcpyAsync(out, d_out, sizeof(double) * 6 * points, hipMemcpyDeviceToHost, st));
+    if (cells) GR_HIP(hipMemcpyAsync(cells, d_cells, sizeof(int64_t) * 2 * points, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    if (why != 0) return fail(GR_ERR_UNSUPPORTED, "gr_sky_fill: a column does not meet its leaves in ascending θ");
     return GR_OK;
 }
 

@@ -5,6 +5,7 @@
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN -c kernels_tu.hip -o kernelstan_m<id>.o                     (tangent, one lane per ray)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN1 -c kernels_tu.hip -o kernelstan1_m<id>.o                   (tangent, a pair of lanes per ray)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN[1] -DGR_TU_SKY -c kernels_tu.hip -o kernelssky[1]_m<id>.o    (the two tangent shapes for sky cells)
+//     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_AREA -c kernels_tu.hip -o kernelsarea_m<id>.o                   (fp64, k_disc_area_factor alone)
 //
 // so that every metric's kernels hold only that metric's component function (gr_device.hpp, GenericMetricT) and the
 // library builds on all cores at once (__graft_entry__.build_hip).  The fp32 objects are the same source with
@@ -14,7 +15,7 @@
 //
 // Exports (plain signatures: the host unit, gradus_mi355x.hip, passes its gr::Params by address -- gr32::Params has the
 // same layout, its fields are double / integer / pointers only):
-//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>      grts_launch_trace_m<ID>      grts1_launch_trace_m<ID>
+//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>, gr64_launch_areafactor_m<ID> (-DGR_TU_AREA)      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>      grts_launch_trace_m<ID>      grts1_launch_trace_m<ID>
 #ifndef GR_TU_METRIC
 #error "compile with -DGR_TU_METRIC=<metric id>"
 #endif
@@ -82,6 +83,15 @@ namespace {
 typedef GR_NS::MetricOf<GR_TU_METRIC>::type TuMetric;
 }
 
+#if defined(GR_TU_AREA)
+// γ(r) A(r) of the disc at n radii (k_disc_area_factor): the emissivity weight of a resident sky's (r, ϕ) map (gr_sky_bin_grid).
+// An object of its own (the GR_TU_SKY precedent): inside the fp64 object it left every trace kernel as it was but moved the
+// operands of k_tile_classify (47 of 2004 instructions, Kerr; scripts/isa_compare.py).
+hipError_t GR_TU_NAME(_launch_areafactor_m)(const void* params, const double* r, double* out, hipStream_t stream)
+{
+    return GR_NS::launch_areafactor_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), r, out, stream);
+}
+#else
 hipError_t GR_TU_NAME(_launch_trace_m)(int kernel, int block, int n_cu, int waves_per_simd, unsigned long long* queue,
                                        const void* params, hipStream_t stream)
 {
@@ -89,8 +99,9 @@ hipError_t GR_TU_NAME(_launch_trace_m)(int kernel, int block, int n_cu, int wave
     GR_NS::LaunchKnobs k{ kernel, block, n_cu, waves_per_simd, queue };
     return GR_NS::launch_metric<TuMetric>(k, p, stream);
 }
+#endif
 
-#if !defined(GR_TU_F32) && !defined(GR_TU_TAN) && !defined(GR_TU_TAN1)
+#if !defined(GR_TU_F32) && !defined(GR_TU_TAN) && !defined(GR_TU_TAN1) && !defined(GR_TU_AREA)
 hipError_t GR_TU_NAME(_launch_path_m)(const void* params, double* d_path, int64_t cap, unsigned long long* d_n, hipStream_t stream)
 {
     return GR_NS::launch_path_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), d_path, cap, d_n, stream);

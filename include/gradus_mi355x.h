@@ -833,6 +833,39 @@ int32_t gr_sky_download(gr_sky* sky, int64_t first_cell, int64_t count, double* 
                         void* location /* count int8_t */, double* rows /* count x 6 */, int64_t* refined /* count / 9, or NULL */,
                         int64_t* refined_children /* count / 9 x 9, or NULL */);
 
+/* ---- the (r, ϕ) maps and the filled image of a resident sky (added within ABI 8) ----
+ * γ(r) A(r) of the disc in the equatorial plane at n radii: γ the Lorentz factor of the disc's velocity in the LNRF (Keplerian
+ * from pf->r_isco out; inside it the plunging table of pf clamped to its ends, or Kerr's analytic plunge when pf brings no
+ * table -- the branches of the REDSHIFT point function), A = 2π √(g_rr g_ϕϕ).  pf as gr_apply_pointfunction takes it.
+ * gr_disc_area_factor_device: r and out are device memory, nothing is waited for. */
+int32_t gr_disc_area_factor_device(gr_ctx* ctx, const gr_config* cfg, const gr_pointfunction* pf, const double* d_r, int64_t n,
+                                   double* d_out, void* hip_stream);
+int32_t gr_disc_area_factor(gr_ctx* ctx, const gr_config* cfg, const gr_pointfunction* pf, const double* r /* host, n */, int64_t n,
+                            double* out /* host, n */);
+/* bin_emissivity_grid / bin_redshift_grid / bin_time_grid (adaptive-sample.jl:266-450): over the leaves gr_sky_occupancy keeps,
+ * with ΔΩ = wx wy / sin(acos(cos θ)) of a leaf, out = Σ ΔΩ w / Σ ΔΩ per bin (0 where Σ ΔΩ = 0) for w = J g^Γ γ(r) A(r)
+ * (gamma = NULL leaves g^Γ out), w = g or w = t; solid_angle receives Σ ΔΩ.  The sums are integer sums on a fixed-point grid
+ * (two integers per value): the same bits on every run and for every launch shape.  A bin with a NaN term is NaN; an infinite
+ * term makes it ±∞ (NaN for both signs).  An empty sky gives zeros.
+ * GR_ERR_INVALID_ARGUMENT, before anything touches the device, for: r_bins, phi_bins or out null, a bin count outside
+ * 1 ... 46340, a sky that has not been traced, edges that do not ascend, `what` outside the enum.
+ * GR_ERR_UNSUPPORTED if a bin with non-zero terms and no NaN sums to 0: its terms lie below the resolution of the sums (2^(2 en - 124)
+ * of the map's largest term rounded up to a power of two, 2^en >= the cell count: 2^-86 at half a million cells), and a map that
+ * is 0 where gr_sky_occupancy counts would read as unlit. */
+enum { GR_SKY_MAP_EMISSIVITY = 0, GR_SKY_MAP_REDSHIFT = 1, GR_SKY_MAP_TIME = 2 };
+int32_t gr_sky_bin_grid(gr_sky* sky, int32_t what, const double* r_bins, int64_t n_r, const double* phi_bins, int64_t n_phi,
+                        const double* gamma /* 1, or NULL: leave g^Γ out */, double* out /* host, n_r x n_phi */,
+                        double* solid_angle /* host, n_r x n_phi, or NULL */);
+/* fill_sky_values (adaptive-sample.jl:196-250): per column ϕ_k the distinct leaves that hold (cos θ_j, ϕ_k), ordered by
+ * θ = acos(cos θ of the leaf); every point takes the interval of searchsorted(θ_j, side = right) clipped to [1, cells - 1] and
+ * interpolates the six row fields linearly in θ.  The θ grid may come in any order (it is walked in ascending order, the results
+ * land at the caller's indices).  A column with fewer than two leaves is NaN.  `cells`: the lower and the upper
+ * leaf of every point (0, 0 in a NaN column).  GR_ERR_INVALID_ARGUMENT for a null grid or out, a count outside 1 ... 46340, a sky
+ * that has not been traced; GR_ERR_UNSUPPORTED if a column does not meet its leaves in ascending θ (no tree of disjoint
+ * rectangles does that). */
+int32_t gr_sky_fill(gr_sky* sky, const double* phi_grid, int64_t n_phi, const double* theta_grid, int64_t n_theta,
+                    double* out /* host, n_theta x n_phi x 6 */, int64_t* cells /* host, n_theta x n_phi x 2, or NULL */);
+
 /* ---- tabulated metrics (ABI 7; segments, axis terms: ABI 8; GR_METRIC_TABULATED): the AbstractMetric plugin interface on the device ----
  * Host-only functions (no context, no device): plan a grid, learn its nodes, fit, check.
  *
