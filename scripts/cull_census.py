@@ -3,24 +3,25 @@
 
 Random whole 8 x 8 tiles of the 2048² bench image (Kerr a = 0.998, observer r = 1000, θ = 75°, ThinDisc(isco, 50), λ1 = 2000),
 lanes as the one-ray-per-lane kernel lays them out, are stepped through the KERNEL's own logic compiled for the host
-(tests/host_harness_cull.cpp) four times: both mechanisms off, the start cull alone, the step loop's culls alone, both.  Printed:
+(tests/host_harness_culls.cpp) four times: both mechanisms off, the start cull alone, the step loop's culls alone, both.  Printed:
 steps per arm, the sum over tiles of the longest lane's steps (the cost of one wave per tile), how many rays each arm ended early
 and how many of those the full trace says hit the disc (must be 0), whether pixels and statuses are the same bytes in all arms,
 and the ratio of accepted steps that GRADUS_MI355X_ESCAPE_CULL unset / =0 shows on this build.  The step loop's arm here holds the
-escape cull (r > R_cull) and the polar-rate cull together, as the switch does.  CPU only.
+escape cull (r > R_cull) and the polar-rate cull together, as the switch does.  CPU only.  Every arm's record has the keys of
+tests/harness_culls.py census(), whichever mechanism it belongs to.
 
-With --pass-cull the same tiles go through tests/host_harness_pass_cull.cpp as well, the pass cull (Ray::start_decided) on
+With --pass-cull the same tiles are traced with the pass cull (Ray::start_decided) on
 against off under the start cull alone and under all culls, and the result gains a "pass_cull" entry: steps and wave-steps of
 the four arms, how many rays the pass cull decided (and how many of those hit the disc: must be 0), the ratio of wave-steps it
 leaves, and the GRADUS_MI355X_ESCAPE_CULL switch ratio with it on.  --zeta tries another R_pass = ζ R_cull than the library's.
 
-With --entry-cull the same tiles go through tests/host_harness_entry_cull.cpp: the library as shipped ("all"), the entry cull
+With --entry-cull the same tiles are traced by the library as shipped ("all"), the entry cull
 (Ray::step) off alone ("no-entry") and the step loop's culls off ("start"), at the library's ζ or at --zeta.  The result gains an
 "entry_cull" entry: steps and wave-steps of the arms, how many rays ended on entry, at which steps, and how many of those hit
 the disc (must be 0), the ratios the entry cull leaves and the GRADUS_MI355X_ESCAPE_CULL switch ratio.  --ref-zeta Z adds the
 wave-steps and accepted steps relative to a library with R_pass = Z R_cull and no entry cull (0.75: the one before the entry cull).
 
-With --defer-cull the same tiles go through tests/host_harness_defer_cull.cpp: the library as shipped ("all"), the defer cull
+With --defer-cull the same tiles are traced by the library as shipped ("all"), the defer cull
 (Ray::start_decided, Ray::step) off alone ("no-defer"), the step loop's culls off ("start") and every cull off ("full"), at the
 library's ζ and ζ_defer or at --zeta and --defer-zeta (the latter builds the harness with that constant).  The result gains a
 "defer_cull" entry: steps and wave-steps of the arms, how many rays the start marked, how many the defer cull and the entry cull
@@ -36,7 +37,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import math
 import os
 import sys
 
@@ -46,62 +46,47 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-SIZE, ALIMS, BLIMS = 2048, (-60.0, 60.0), (-35.0, 35.0)
-X_OBS = np.array([0.0, 1000.0, math.radians(75.0), 0.0])
 
-
-def bench_scene(G, size=SIZE, x=X_OBS, r_out=50.0, **kw):
-    m = G.KerrMetric(1.0, 0.998)
-    cfg = G.render_configuration(m, x, G.ThinDisc(m.isco(), r_out), 2000.0, image_width=size, image_height=size,
-                                 alpha_lims=ALIMS, beta_lims=BLIMS, **kw)
-    pf = G.ConstPointFunctions.redshift(m, x) @ G.ConstPointFunctions.filter_intersected()
-    return cfg, pf
-
-
-def census(tiles=1000, seed=1):
+def _bench(tiles, seed):
+    """(G, the harness, the bench scene's configuration and point function, `tiles` of its tiles drawn with `seed`)"""
     import gradus_jl_amd as G
-    import harness_cull as Hc
+    import harness_culls as H
+    from cull_scenes import SIZE, bench_scene
 
     cfg, pf = bench_scene(G)
     nt = SIZE // 8
-    picks = np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
-    res, _ = Hc.census(G, cfg, pf, picks)
+    return G, H, cfg, pf, np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
+
+
+def census(tiles=1000, seed=1):
+    G, H, cfg, pf, picks = _bench(tiles, seed)
+    res, _ = H.census(G, cfg, pf, picks, *H.STEP)
     res["seed"] = int(seed)
-    res["r_cull"] = Hc.gate_radius(cfg)
+    res["r_cull"] = H.gate_radius(cfg)
     return res
 
 
 def pass_census(tiles=1000, seed=1, zeta=-1.0):
     """The pass cull's arms on the tiles census() draws for the same arguments (zeta < 0: the library's)."""
-    import gradus_jl_amd as G
-    import harness_pass_cull as Hp
-
-    cfg, pf = bench_scene(G)
-    nt = SIZE // 8
-    picks = np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
-    res, _ = Hp.census(G, cfg, pf, picks, zeta)
+    G, H, cfg, pf, picks = _bench(tiles, seed)
+    res, _ = H.census(G, cfg, pf, picks, *H.PASS, zeta=zeta)
     res["seed"] = int(seed)
-    res["zeta"] = Hp.zeta() if zeta < 0 else float(zeta)
-    res["r_cull"] = Hp.gate_radius(cfg)
+    res["zeta"] = H.zeta() if zeta < 0 else float(zeta)
+    res["r_cull"] = H.gate_radius(cfg)
     res["r_pass"] = res["zeta"] * res["r_cull"]
     return res
 
 
 def entry_census(tiles=1000, seed=1, zeta=-1.0, ref_zeta=None):
     """The entry cull's arms on the tiles census() draws for the same arguments (zeta < 0: the library's)."""
-    import gradus_jl_amd as G
-    import harness_entry_cull as He
-
-    cfg, pf = bench_scene(G)
-    nt = SIZE // 8
-    picks = np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
-    res, _ = He.census(G, cfg, pf, picks, zeta)
+    G, H, cfg, pf, picks = _bench(tiles, seed)
+    res, _ = H.census(G, cfg, pf, picks, *H.ENTRY, zeta=zeta)
     res["seed"] = int(seed)
-    res["zeta"] = He.zeta() if zeta < 0 else float(zeta)
-    res["zeta_dip"] = He.zeta_dip()
-    res["r_cull"] = He.gate_radius(cfg)
+    res["zeta"] = H.zeta() if zeta < 0 else float(zeta)
+    res["zeta_dip"] = H.zeta_dip()
+    res["r_cull"] = H.gate_radius(cfg)
     if ref_zeta is not None:
-        ref = He.render_tiles(G, cfg, pf, picks, 1, 1, 0, ref_zeta)
+        ref = H.render_tiles(G, cfg, pf, picks, entry=0, zeta=ref_zeta)
         att = ref["nacc"].astype(np.int64) + ref["nrej"]
         res["ref_zeta"] = float(ref_zeta)
         res["wave_steps_vs_ref"] = res["arms"]["all"]["wave_steps"] / int(att.max(axis=1).sum())
@@ -112,20 +97,15 @@ def entry_census(tiles=1000, seed=1, zeta=-1.0, ref_zeta=None):
 
 def defer_census(tiles=1000, seed=1, zeta=-1.0, defer_zeta=None, ref_zeta=None):
     """The defer cull's arms on the tiles census() draws for the same arguments (zeta < 0, defer_zeta None: the library's)."""
-    import gradus_jl_amd as G
-    import harness_defer_cull as Hd
-
-    cfg, pf = bench_scene(G)
-    nt = SIZE // 8
-    picks = np.random.default_rng(seed).choice(nt * nt, size=tiles, replace=False)
-    res, _ = Hd.census(G, cfg, pf, picks, zeta, defer_zeta)
+    G, H, cfg, pf, picks = _bench(tiles, seed)
+    res, _ = H.census(G, cfg, pf, picks, *H.DEFER, zeta=zeta, defer_zeta=defer_zeta)
     res["seed"] = int(seed)
-    res["zeta"] = Hd.zeta() if zeta < 0 else float(zeta)
-    res["zeta_defer"] = Hd.zeta_defer(defer_zeta)
-    res["zeta_dip"] = Hd.zeta_dip()
-    res["r_cull"] = Hd.gate_radius(cfg)
+    res["zeta"] = H.zeta() if zeta < 0 else float(zeta)
+    res["zeta_defer"] = H.zeta_defer(defer_zeta)
+    res["zeta_dip"] = H.zeta_dip()
+    res["r_cull"] = H.gate_radius(cfg)
     if ref_zeta is not None:
-        ref = Hd.render_tiles(G, cfg, pf, picks, 1, 1, 1, 0, ref_zeta, defer_zeta)
+        ref = H.render_tiles(G, cfg, pf, picks, defer=0, zeta=ref_zeta, defer_zeta=defer_zeta)
         att = ref["nacc"].astype(np.int64) + ref["nrej"]
         res["ref_zeta"] = float(ref_zeta)
         res["wave_steps_vs_ref"] = res["arms"]["all"]["wave_steps"] / int(att.max(axis=1).sum())

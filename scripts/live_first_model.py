@@ -2,7 +2,7 @@
 """CPU model of the bench launch's schedule: what the order of its tiles is worth (DESIGN_measurements.md §M30).
 
 1. CENSUS.  Every 8 x 8 tile of the 2048² bench image (Kerr a = 0.998, observer r = 1000, θ = 75°, ThinDisc(isco, 50), λ1 = 2000)
-   is stepped through the KERNEL's own logic compiled for the host (tests/host_harness_defer_cull.cpp, every cull on as shipped):
+   is stepped through the KERNEL's own logic compiled for the host (tests/host_harness_culls.cpp, every cull on as shipped):
    per tile the attempted steps of its longest lane (what a one-wave workgroup runs: its wave-steps), the steps of all lanes, the
    step of the last lane that ends as a hit, and three candidate flags for the tile: its four corner rays are all decided at the
    start -- the flag k_tile_classify writes (gr_tile_order.hpp) --, one inner ray (lane 27) is, and the corners with a margin:
@@ -27,7 +27,6 @@ from __future__ import annotations
 import argparse
 import heapq
 import json
-import math
 import multiprocessing as mp
 import os
 import sys
@@ -38,8 +37,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-ALIMS, BLIMS = (-60.0, 60.0), (-35.0, 35.0)
-X_OBS = np.array([0.0, 1000.0, math.radians(75.0), 0.0])
 CORNER_LANES = (0, 7, 56, 63)      # gr_order::class_lane(3, k): the corners of an 8 x 8 tile
 INNER_LANE = 27                    # one inner ray instead: the alternative the model rules out
 SIMDS, SLOTS_PER_SIMD = 1024, 3    # 256 CUs x 4 SIMDs, three waves of the head kernel per SIMD (168 VGPRs)
@@ -51,13 +48,11 @@ DEAD_INSTS, LIVE_INSTS = 300.0, 2500.0      # M26: instructions of a wave outsid
 def _chunk(args):
     size, tiles = args
     import gradus_jl_amd as G
-    import harness_defer_cull as Hd
+    import harness_culls as H
+    from cull_scenes import bench_scene
 
-    m = G.KerrMetric(1.0, 0.998)
-    cfg = G.render_configuration(m, X_OBS, G.ThinDisc(m.isco(), 50.0), 2000.0, image_width=size, image_height=size,
-                                 alpha_lims=ALIMS, beta_lims=BLIMS)
-    pf = G.ConstPointFunctions.redshift(m, X_OBS) @ G.ConstPointFunctions.filter_intersected()
-    r = Hd.render_tiles(G, cfg, pf, tiles, 1, 1, 1, 1)
+    cfg, pf = bench_scene(G, size)
+    r = H.render_tiles(G, cfg, pf, tiles)
     att = r["nacc"].astype(np.int64) + r["nrej"]
     hit = r["status"] == int(G.StatusCodes.IntersectedWithGeometry)
     return (tiles, att.max(axis=1), att.sum(axis=1), r["nacc"].sum(axis=1), np.where(hit, att, 0).max(axis=1),
@@ -65,9 +60,9 @@ def _chunk(args):
 
 
 def census(size, procs):
-    import harness_defer_cull as Hd
+    import harness_culls as H
 
-    Hd.lib()      # build the harness once, before the workers load it
+    H.lib()      # build the harness once, before the workers load it
     nt = (size // 8) ** 2
     chunks = [(size, np.arange(a, min(a + 512, nt), dtype=np.int64)) for a in range(0, nt, 512)]
     out = {k: np.zeros(nt, np.int64) for k in ("wave_steps", "lane_steps", "accepted", "hit_steps", "corners", "flag_inner", "hits")}

@@ -11,6 +11,9 @@ FIRES says which of the four mechanisms must end at least one ray of a named sce
 culls: a ray none of the other three ended that takes fewer steps than in the uncut trace).  It was filled from `python
 tests/cull_scenes.py`, the host build at 64 x 64 over all 64 tiles, the size tests/test_cull_domain_host.py runs -- not from the
 device and not from a larger image.  Where the set is empty the culls must leave every step count alone.
+
+The older host tests of the single culls (tests/test_cull_host.py and the pass, entry and defer cull's) and scripts/cull_census.py
+trace the bench scene itself under the default chart, at 2048² (bench_scene) or at 64² with one parameter changed (bench_variant, SCENES).
 """
 import math
 
@@ -96,6 +99,34 @@ N_RANDOM = 40
 # the culls take steps away
 RANDOM_QUIET = (5, 9, 25)
 ESCAPE_RADIUS_M = 4.0          # KerrMetric::kEscapeRadiusM
+# the bench plane: its edge in pixels, its window and its observer
+SIZE, ALIMS, BLIMS = 2048, (-60.0, 60.0), (-35.0, 35.0)
+X_OBS = np.array([0.0, 1000.0, math.radians(75.0), 0.0])
+# the bench scene at 64² and its variants chosen for where the signs and closed forms of the pass cull can go wrong: a wider wedge,
+# a = 0 (Ω_lo = Ω_hi, the a -> 0 form of μ+), a retrograde hole, an observer nearer the axis, one below the plane (μ0 < 0)
+SCENES = {
+    "bench64": dict(),
+    "gtol0.1": dict(gtol=0.1),
+    "a0": dict(a=0.0),
+    "a-0.998": dict(a=-0.998),
+    "theta30": dict(theta=30.0),
+    "theta105": dict(theta=105.0),
+}
+
+
+def bench_scene(G, size=SIZE, x=X_OBS, r_out=50.0, a=0.998, **kw):
+    """(configuration, point function) of the bench scene at `size`², with another observer, outer edge, spin or render keyword."""
+    m = G.KerrMetric(1.0, a)
+    cfg = G.render_configuration(m, x, G.ThinDisc(m.isco(), r_out), 2000.0, image_width=size, image_height=size,
+                                 alpha_lims=ALIMS, beta_lims=BLIMS, **kw)
+    pf = G.ConstPointFunctions.redshift(m, x) @ G.ConstPointFunctions.filter_intersected()
+    return cfg, pf
+
+
+def bench_variant(G, a=0.998, theta=75.0, size=64, r_obs=1000.0, r_out=50.0, **kw):
+    """(configuration, point function, a) of bench_scene at 64² with the observer given by radius and inclination (degrees):
+    `bench_variant(G, **SCENES[name])`."""
+    return (*bench_scene(G, size, np.array([0.0, r_obs, math.radians(theta), 0.0]), r_out, a, **kw), a)
 
 
 def gate_radius_closed_form(M, r_out, gtol):
@@ -165,24 +196,24 @@ def random_tiles(p, size=64, count=16):
 def configuration(G, built):
     """The TracingConfiguration and the point function of a scene as _build returns it; its gate must be finite: a scene the gate
     switches off compares nothing, and is a bug in this file."""
-    import harness_defer_cull as Hd
+    import harness_culls as H
 
     m, x, d, max_time, kw = built
     cfg = G.render_configuration(m, x, d, max_time, **kw)
-    rc = Hd.gate_radius(cfg)
+    rc = H.gate_radius(cfg)
     assert math.isfinite(rc), ("gated off", m, x, d, kw)
     pf = G.ConstPointFunctions.redshift(m, x) @ G.ConstPointFunctions.filter_intersected()
     return cfg, pf, rc
 
 
 def host_arms(G, built, tiles):
-    """(configuration, R_cull, the library as shipped, every cull off) on the host build: harness_defer_cull.render_tiles with
-    the arms (1, 1, 1, 1, the library's ζ) and (0, 0, 0, 0, ζ = 0)."""
-    import harness_defer_cull as Hd
+    """(configuration, R_cull, the library as shipped, every cull off) on the host build: harness_culls.render_tiles with
+    the arms "all" and "full" of its DEFER table."""
+    import harness_culls as H
 
     cfg, pf, rc = configuration(G, built)
-    on = Hd.render_tiles(G, cfg, pf, tiles, 1, 1, 1, 1, -1.0)
-    off = Hd.render_tiles(G, cfg, pf, tiles, 0, 0, 0, 0, 0.0)
+    on = H.render_tiles(G, cfg, pf, tiles, *H.DEFER[0]["all"][:4], -1.0)
+    off = H.render_tiles(G, cfg, pf, tiles, *H.DEFER[0]["full"])
     return cfg, rc, on, off
 
 

@@ -1,34 +1,16 @@
 """ctypes binding of tests/host_harness.cpp: the HIP integrator compiled for the host (g++)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness.so")
-SRC = [os.path.join(HERE, "host_harness.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_device.hpp"),
-       os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_mesh_grid.hpp"), os.path.join(ROOT, "include", "gradus_mi355x.h"),
-       os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_tabmetric.hpp")]
-
-
-def build():
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, SRC[0]])
-    return SO
-
-
-_lib = None
+import hostbuild
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.hh_step_log.restype = C.c_int64
-    return _lib
+    L = hostbuild.load("host_harness.cpp")
+    L.hh_step_log.restype = C.c_int64
+    return L
 
 
 def render_endpoints(G, config):
@@ -77,19 +59,8 @@ def step_log(G, config, i, cap=100000):
 
 
 # ---- the TANGENT flavour of the integrator (real = value + ∂/∂α + ∂/∂β), tests/host_harness_tangent.cpp ----
-SO_TAN = os.path.join(HERE, "libhost_harness_tangent.so")
-SRC_TAN = [os.path.join(HERE, "host_harness_tangent.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_device.hpp"),
-           os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_tangent.hpp"), os.path.join(ROOT, "include", "gradus_mi355x.h")]
-_lib_tan = None
-
-
 def lib_tangent():
-    global _lib_tan
-    if _lib_tan is None:
-        if not os.path.exists(SO_TAN) or any(os.path.getmtime(s) > os.path.getmtime(SO_TAN) for s in SRC_TAN):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO_TAN, SRC_TAN[0]])
-        _lib_tan = C.CDLL(SO_TAN)
-    return _lib_tan
+    return hostbuild.load("host_harness_tangent.cpp")
 
 
 def ray_tangent_separable(G, config, pf, r, cos_t, sin_t, tiled):

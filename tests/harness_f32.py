@@ -1,21 +1,19 @@
 """ctypes binding of tests/host_harness_f32.cpp: the SINGLE-PRECISION text of the HIP integrator compiled for the host, with
 the clang++ that belongs to hipcc and the flags of the library's kernels32_m*.o objects."""
 import ctypes as C
+import functools
 import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_f32.so")
-SRC = [os.path.join(HERE, "host_harness_f32.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_device.hpp"),
-       os.path.join(ROOT, "include", "gradus_mi355x.h"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_tabmetric.hpp")]
+import hostbuild
+
 # the single-precision flags of __graft_entry__.hip_units / HIP_FLAGS
 F32_FLAGS = ["-DGR_REAL_IS_FLOAT", "-Xclang", "-cl-single-precision-constant", "-ffp-contract=on"]
 LOG_COLS = ("t", "r", "theta", "h", "dt", "e2", "flags")      # host_harness_f32.cpp: HF_LOG_COLS
 
 
+@functools.cache
 def clangxx():
     """The clang++ of the ROCm installation whose hipcc builds the library (g++ ignores ext_vector_type)."""
     import __graft_entry__ as g
@@ -28,21 +26,10 @@ def clangxx():
     raise RuntimeError("no clang++ next to " + g._hipcc())
 
 
-def build():
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call([clangxx(), "-O2", "-std=c++17", "-fPIC", "-shared"] + F32_FLAGS + ["-o", SO, SRC[0]])
-    return SO
-
-
-_lib = None
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.hf_step_log.restype = C.c_int64
-    return _lib
+    L = hostbuild.load("host_harness_f32.cpp", flags=F32_FLAGS, compiler=clangxx())
+    L.hf_step_log.restype = C.c_int64
+    return L
 
 
 def render_endpoints(G, config):

@@ -2,26 +2,14 @@
 lag-energy bins (k_lag_extrema / k_lag_bin) -- compiled for the host with g++, and `binflux` around it exactly as
 reverberation._binflux_device puts it around the library's calls."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_lagbin.so")
-SRC = [os.path.join(HERE, "host_harness_lagbin.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_lagbin.hpp"),
-       os.path.join(ROOT, "include", "gradus_mi355x.h")]
-_lib = None
+import hostbuild
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", SO, SRC[0]])
-        _lib = C.CDLL(SO)
-    return _lib
+    return hostbuild.load("host_harness_lagbin.cpp", flags=["-ffp-contract=off"])
 
 
 def _rows(rows):

@@ -4,31 +4,21 @@ the host with g++ -- and what the CPU and the GPU tests of the ring-arm producer
 import ctypes as C
 import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 
+import hostbuild
 from test_flat_space_exact import cartesian
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_ringarm.so")
-SRC = [os.path.join(HERE, "host_harness_ringarm.cpp")] + [os.path.join(ROOT, "gradus.jl_amd", "csrc", f) for f in ("gr_ringarm.hpp", "gr_lagbin.hpp")]
-_lib = None
 HIT = 2
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", SO, SRC[0]])
-        _lib = C.CDLL(SO)
-        _lib.hring_invphi.restype = C.c_double
-        _lib.hring_bracket.restype = C.c_int
-        _lib.hring_update.restype = C.c_int
-    return _lib
+    L = hostbuild.load("host_harness_ringarm.cpp", flags=["-ffp-contract=off"])
+    L.hring_invphi.restype = C.c_double
+    L.hring_bracket.restype = C.c_int
+    L.hring_update.restype = C.c_int
+    return L
 
 
 def form_rays(frame, β, θ):

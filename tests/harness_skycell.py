@@ -3,27 +3,16 @@ of a source's sky -- seeded (x, v, ∂v/∂θ, ∂v/∂ϕ) -> (t, r, ϕ, g, J, s
 closed form the device kernel uses (k_skycell_velocities), so the harness checks Ray::initial_conditions, the integrator
 and Ray::finalize; the seeding kernel itself is checked against this on the GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_skycell.so")
-SRC = [os.path.join(HERE, "host_harness_skycell.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_device.hpp"),
-       os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_tangent.hpp"), os.path.join(ROOT, "include", "gradus_mi355x.h")]
-_lib = None
+import hostbuild
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, SRC[0]])
-        _lib = C.CDLL(SO)
-        assert _lib.hhs_row_doubles() == 6 and _lib.hhs_seed_doubles() == 9
-    return _lib
+    L = hostbuild.load("host_harness_skycell.cpp")
+    assert L.hhs_row_doubles() == 6 and L.hhs_seed_doubles() == 9
+    return L
 
 
 def seeds(Mx, cosθ, ϕ):

@@ -1,17 +1,10 @@
 """ctypes binding of tests/host_harness_skygrid.cpp: gr_skygrid.hpp -- the tree logic of a resident adaptive sky (the k_sky_*
 kernels call the same functions per cell) -- compiled for the host with g++, on the arrays of a grids.AdaptiveGrid."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_skygrid.so")
-SRC = [os.path.join(HERE, "host_harness_skygrid.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_skygrid.hpp"),
-       os.path.join(ROOT, "include", "gradus_mi355x.h")]
-_lib = None
+import hostbuild
 
 
 class hsg_grid(C.Structure):
@@ -20,13 +13,9 @@ class hsg_grid(C.Structure):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", SO, SRC[0]])
-        _lib = C.CDLL(SO)
-        _lib.hsg_top.restype = _lib.hsg_pairs.restype = _lib.hsg_find_need_refine.restype = _lib.hsg_bins.restype = C.c_int64
-    return _lib
+    L = hostbuild.load("host_harness_skygrid.cpp", flags=["-ffp-contract=off"])
+    L.hsg_top.restype = L.hsg_pairs.restype = L.hsg_find_need_refine.restype = L.hsg_bins.restype = C.c_int64
+    return L
 
 
 class Grid:

@@ -2,20 +2,12 @@
 column and per radius (gr_skygrid.hpp, gr_lagbin.hpp, disc_area_factor of gr_device.hpp), compiled for the host with g++ on the
 arrays of a grids.AdaptiveGrid and the rows of an AdaptiveSky."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "gradus.jl_amd", "csrc")
-SO = os.path.join(HERE, "libhost_harness_skymaps.so")
-SRC = [os.path.join(HERE, "host_harness_skymaps.cpp")] + [os.path.join(CSRC, f) for f in ("gr_skygrid.hpp", "gr_lagbin.hpp", "gr_device.hpp",
-                                                                                       "gr_tabmetric.hpp")]
-SRC.append(os.path.join(ROOT, "include", "gradus_mi355x.h"))
+import hostbuild
+
 MAPS = {"emissivity": 0, "redshift": 1, "time": 2}
-_lib = None
 
 
 class hsm_grid(C.Structure):
@@ -24,13 +16,9 @@ class hsm_grid(C.Structure):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wno-attributes", "-fPIC", "-shared", "-o", SO, SRC[0]])
-        _lib = C.CDLL(SO)
-        _lib.hsm_fill.restype = C.c_int64
-    return _lib
+    L = hostbuild.load("host_harness_skymaps.cpp", flags=["-ffp-contract=off", "-Wno-attributes"])
+    L.hsm_fill.restype = C.c_int64
+    return L
 
 
 class Sky:

@@ -4,30 +4,19 @@ disc profile, an independent scalar restatement of the two integrals, and the co
 import bisect
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_tfint.so")
-SRC = [os.path.join(HERE, "host_harness_tfint.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_tfint.hpp"),
-       os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_lagbin.hpp"), os.path.join(ROOT, "include", "gradus_mi355x.h")]
-_lib = None
+import hostbuild
 
 TOL = 1e-12          # of the peak: the bound of every comparison between two routes of the same integral
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", SO, SRC[0]])
-        _lib = C.CDLL(SO)
-        _lib.htf_lineprofile.restype = _lib.htf_lagtransfer.restype = C.c_int64
-        _lib.htf_bin.restype = C.c_double
-    return _lib
+    L = hostbuild.load("host_harness_tfint.cpp", flags=["-ffp-contract=off"])
+    L.htf_lineprofile.restype = L.htf_lagtransfer.restype = C.c_int64
+    L.htf_bin.restype = C.c_double
+    return L
 
 
 class Calls:

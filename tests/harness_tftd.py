@@ -6,34 +6,22 @@ import bisect
 import ctypes as C
 import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import harness_tfint as H
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_tftd.so")
-SRC = [os.path.join(HERE, "host_harness_tftd.cpp")] + [os.path.join(ROOT, "gradus.jl_amd", "csrc", f) for f in ("gr_tftd.hpp", "gr_tfint.hpp", "gr_lagbin.hpp")] \
-    + [os.path.join(ROOT, "include", "gradus_mi355x.h")]
-_lib = None
+import hostbuild
 
 TOL = H.TOL
 N_RADII = 37                                                  # annuli: neither a multiple of the wave count nor of the chunk
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", SO, SRC[0]])
-        _lib = C.CDLL(SO)
-        _lib.htftd_lagtransfer.restype = C.c_int64
-        _lib.htftd_rank.restype = C.c_int
-        _lib.htftd_time_sample.restype = C.c_double
-    return _lib
+    L = hostbuild.load("host_harness_tftd.cpp", flags=["-ffp-contract=off"])
+    L.htftd_lagtransfer.restype = C.c_int64
+    L.htftd_rank.restype = C.c_int
+    L.htftd_time_sample.restype = C.c_double
+    return L
 
 
 class Call:

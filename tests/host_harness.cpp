@@ -8,6 +8,7 @@
 
 #include "../gradus.jl_amd/csrc/gr_device.hpp"
 #include "../gradus.jl_amd/csrc/gr_mesh_grid.hpp"
+#include "host_harness_common.hpp"
 
 using namespace GR_NS;
 
@@ -26,16 +27,15 @@ static void run(const Params& p, int64_t n, double* tlog, double* hlog, int64_t 
             if (tlog && k < cap) { tlog[k] = ray.t; hlog[k] = ray.x[2]; ++k; }
             if (fin) break;
         }
-        const LdsView no_lds{ nullptr, nullptr, nullptr, nullptr, nullptr };
-        ray.finalize(m, p, no_lds);
+        ray.finalize(m, p, hh::no_lds());
         if (tlog && k < cap) { tlog[k] = -1.0; hlog[k] = ray.dbg_e2; ++k; }
         if (nlog) *nlog = k;
     }
 }
 
+// `p` as hh::fill leaves it (the derived fields included) with the rays' source and output set
 static void dispatch(Params& p, double* tlog, double* hlog, int64_t cap, int64_t* nlog)
 {
-    derive_params(p);
     p.disc_table = p.cfg.disc_table;      // host pointer is directly usable here
     static thread_local std::vector<double> mesh_table;
     if (p.cfg.disc_id == GR_DISC_MESH) {  // ... a mesh goes through the builder the host unit uses (gr_mesh_grid.hpp)
@@ -81,11 +81,8 @@ static void wave_stats(const Params& p, const int64_t* tiles, int64_t n_tiles, d
     for (int64_t t = 0; t < n_tiles; ++t) {
         Ray<Metric, DISC> ray[64];
         bool act[64];
-        const int64_t tiles_per_col = H >> 3;
-        const int64_t tx = tiles[t] / tiles_per_col, ty = tiles[t] - tx * tiles_per_col;
         for (int l = 0; l < 64; ++l) {
-            const int64_t j = ((tx << 3) + (l >> 3)) * H + (ty << 3) + (l & 7);
-            ray[l].init(m, p, j);
+            ray[l].init(m, p, hh::tile_lane_ray(tiles[t], l, H));
             act[l] = true;
         }
         for (;;) {
@@ -118,11 +115,8 @@ extern "C" {
 int hh_wave_stats(const gr_config* cfg, const gr_plane* plane, const int64_t* tiles, int64_t n_tiles, double* out)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
     const int64_t n = plane->width * plane->height;
-    p.cfg = *cfg; p.n = n; p.cold = &c; c.winding_plane = cfg->winding_plane;
-    c.src_mode = 0; c.out_mode = 0; c.plane = *plane; c.range = gr_range{ 0, n, n, 1 };
-    derive_params(p);
+    hh::fill_plane(p, c, cfg, plane, gr_range{ 0, n, n, 1 }, 0, nullptr);
     p.cfg.upper_hemisphere = 0;
     for (int i = 0; i < 34; ++i) out[i] = 0.0;
     if (cfg->metric_id != GR_METRIC_KERR || cfg->disc_id != GR_DISC_THIN) return -1;
@@ -187,9 +181,8 @@ int hh_rhs_both(const gr_config* cfg, double r, double th, const double* v, doub
 int hh_render_endpoints(const gr_config* cfg, const gr_plane* plane, const gr_range* rg, gr_point* out)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = rg->count; p.cold = &c; c.winding_plane = cfg->winding_plane;
-    c.src_mode = 0; c.out_mode = 1; c.plane = *plane; c.range = *rg; c.points = out;
+    hh::fill_plane(p, c, cfg, plane, *rg, 1, nullptr);
+    c.points = out;
     dispatch(p, nullptr, nullptr, 0, nullptr);
     return 0;
 }
@@ -197,12 +190,8 @@ int hh_render_endpoints(const gr_config* cfg, const gr_plane* plane, const gr_ra
 int hh_render(const gr_config* cfg, const gr_plane* plane, const gr_range* rg, const gr_pointfunction* pf, double* image)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = rg->count; p.cold = &c; c.winding_plane = cfg->winding_plane;
-    c.src_mode = 0; c.out_mode = 0; c.plane = *plane; c.range = *rg; c.image = image;
-    c.pf.pf_id = pf->pf_id; c.pf.filter_id = pf->filter_id; c.pf.fill = pf->fill; c.pf.r_isco = pf->r_isco;
-    c.pf.n_plunge = pf->n_plunge; c.pf.plunge_r = pf->plunge_r; c.pf.plunge_vt = pf->plunge_vt;
-    c.pf.plunge_vr = pf->plunge_vr; c.pf.plunge_vphi = pf->plunge_vphi;
+    hh::fill_plane(p, c, cfg, plane, *rg, 0, pf);
+    c.image = image;
     dispatch(p, nullptr, nullptr, 0, nullptr);
     return 0;
 }
@@ -210,8 +199,7 @@ int hh_render(const gr_config* cfg, const gr_plane* plane, const gr_range* rg, c
 int hh_trace_endpoints(const gr_config* cfg, const double* x, int64_t x_stride, const double* v, int64_t n, gr_point* out)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = n; p.cold = &c; c.winding_plane = cfg->winding_plane;
+    hh::fill(p, c, cfg, n, nullptr);
     c.src_mode = 1; c.out_mode = 1; c.x = x; c.x_stride = x_stride; c.v = v; c.points = out;
     c.range = gr_range{ 0, n, n > 0 ? n : 1, 1 };
     dispatch(p, nullptr, nullptr, 0, nullptr);
@@ -222,9 +210,8 @@ int hh_trace_endpoints(const gr_config* cfg, const double* x, int64_t x_stride, 
 int64_t hh_step_log(const gr_config* cfg, const gr_plane* plane, int64_t i, gr_point* out, double* tlog, double* hlog, int64_t cap)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = 1; p.cold = &c; c.winding_plane = cfg->winding_plane;
-    c.src_mode = 0; c.out_mode = 1; c.plane = *plane; c.range = gr_range{ i, 1, 1, 1 }; c.points = out;
+    hh::fill_plane(p, c, cfg, plane, gr_range{ i, 1, 1, 1 }, 1, nullptr);
+    c.points = out;
     int64_t n = 0;
     dispatch(p, tlog, hlog, cap, &n);
     return n;

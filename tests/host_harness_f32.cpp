@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "../gradus.jl_amd/csrc/gr_device.hpp"
+#include "host_harness_common.hpp"
 
 using namespace GR_NS;
 
@@ -43,8 +44,7 @@ static void run(const Params& p, int64_t n, double* log, int64_t cap, int64_t* n
             if (fin) break;
         }
 #undef HF_LOG
-        const LdsView no_lds{ nullptr, nullptr, nullptr, nullptr, nullptr };
-        ray.finalize(m, p, no_lds);
+        ray.finalize(m, p, hh::no_lds());
         if (nlog) *nlog = k;
     }
 }
@@ -57,10 +57,10 @@ static void run_metric(const Params& p, double* log, int64_t cap, int64_t* nlog)
     else run<M, GR_DISC_NONE>(p, p.n, log, cap, nlog);
 }
 
+// `p` as hh::fill leaves it (the derived fields included) with the rays' source and output set
 static int dispatch(Params& p, double* log, int64_t cap, int64_t* nlog)
 {
     if (p.cfg.disc_id != GR_DISC_THIN && p.cfg.disc_id != GR_DISC_NONE) return -1;
-    derive_params(p);
     p.cfg.upper_hemisphere = (p.cfg.upper_hemisphere ? 1 : 0) | (p.cfg.count_windings ? 4 : 0);   // as stage_disc_table does
     switch (p.cfg.metric_id) {
     case 0: run_metric<0>(p, log, cap, nlog); break;
@@ -84,21 +84,16 @@ extern "C" {
 int hf_render_endpoints(const gr_config* cfg, const gr_plane* plane, const gr_range* rg, gr_point* out)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = rg->count; p.cold = &c; c.winding_plane = cfg->winding_plane;
-    c.src_mode = 0; c.out_mode = 1; c.plane = *plane; c.range = *rg; c.points = out;
+    hh::fill_plane(p, c, cfg, plane, *rg, 1, nullptr);
+    c.points = out;
     return dispatch(p, nullptr, 0, nullptr);
 }
 
 int hf_render(const gr_config* cfg, const gr_plane* plane, const gr_range* rg, const gr_pointfunction* pf, double* image)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = rg->count; p.cold = &c; c.winding_plane = cfg->winding_plane;
-    c.src_mode = 0; c.out_mode = 0; c.plane = *plane; c.range = *rg; c.image = image;
-    c.pf.pf_id = pf->pf_id; c.pf.filter_id = pf->filter_id; c.pf.fill = pf->fill; c.pf.r_isco = pf->r_isco;
-    c.pf.n_plunge = pf->n_plunge; c.pf.plunge_r = pf->plunge_r; c.pf.plunge_vt = pf->plunge_vt;
-    c.pf.plunge_vr = pf->plunge_vr; c.pf.plunge_vphi = pf->plunge_vphi;
+    hh::fill_plane(p, c, cfg, plane, *rg, 0, pf);
+    c.image = image;
     return dispatch(p, nullptr, 0, nullptr);
 }
 
@@ -106,9 +101,8 @@ int hf_render(const gr_config* cfg, const gr_plane* plane, const gr_range* rg, c
 int64_t hf_step_log(const gr_config* cfg, const gr_plane* plane, int64_t i, gr_point* out, double* log, int64_t cap)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = 1; p.cold = &c; c.winding_plane = cfg->winding_plane;
-    c.src_mode = 0; c.out_mode = 1; c.plane = *plane; c.range = gr_range{ i, 1, 1, 1 }; c.points = out;
+    hh::fill_plane(p, c, cfg, plane, gr_range{ i, 1, 1, 1 }, 1, nullptr);
+    c.points = out;
     int64_t n = 0;
     if (dispatch(p, log, cap, &n) != 0) return -1;
     return n;

@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "../gradus.jl_amd/csrc/gr_device.hpp"
+#include "host_harness_common.hpp"
 
 using namespace grt;
 
@@ -19,7 +20,7 @@ static void run(const Params& p)
 {
     Metric m;
     m.load(p.cfg);
-    const LdsView no_lds{ nullptr, nullptr, nullptr, nullptr, nullptr };
+    const LdsView no_lds = hh::no_lds();
     for (int64_t j = 0; j < p.n; ++j) {
         Ray<Metric, DISC> ray;
         ray.init(m, p, j);
@@ -38,20 +39,14 @@ int hhs_sky_cells(const gr_config* cfg, const gr_pointfunction* pf, const double
                   int tangent_norm, double* out)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = n; p.cold = &c;
+    hh::fill(p, c, cfg, n, pf);
     c.src_mode = 1; c.out_mode = 6;
     c.x = x_src; c.x_stride = 0; c.v = v; c.v_tan = seed;
     std::memcpy(c.plane.x_obs, x_src, sizeof c.plane.x_obs);
     c.range = gr_range{ 0, n, n > 0 ? n : 1, 1 };
     c.lp_rmin = 0.0; c.lp_rmax = INFINITY; c.lp_pairs = out;
-    c.pf.pf_id = pf->pf_id; c.pf.filter_id = pf->filter_id; c.pf.fill = pf->fill; c.pf.r_isco = pf->r_isco;
-    c.pf.n_plunge = pf->n_plunge; c.pf.plunge_r = pf->plunge_r; c.pf.plunge_vt = pf->plunge_vt;
-    c.pf.plunge_vr = pf->plunge_vr; c.pf.plunge_vphi = pf->plunge_vphi;
     c.pf.has_u_src = pf->has_u_src ? 1 : 0;
     for (int q = 0; q < 4; ++q) c.pf.u_src[q] = pf->has_u_src ? pf->u_src[q] : (q == 0 ? 1.0 : 0.0);
-    c.winding_plane = cfg->winding_plane;
-    derive_params(p);
     p.tangent_norm = tangent_norm ? 1 : 0;
     p.disc_table = p.cfg.disc_table;
     p.cfg.upper_hemisphere = (p.cfg.upper_hemisphere ? 1 : 0);      // (no PoloidalShapeChart, no winding count: as the tangent harness)

@@ -10,6 +10,7 @@
 #include "../gradus.jl_amd/csrc/gr_device.hpp"
 #include "../gradus.jl_amd/csrc/gr_lagbin.hpp"
 #include "../gradus.jl_amd/csrc/gr_skygrid.hpp"
+#include "host_harness_common.hpp"
 
 using namespace gr_skygrid;
 
@@ -152,18 +153,7 @@ int hsm_area_factor(const gr_config* cfg, const gr_pointfunction* pf, const doub
     using namespace GR_NS;
     Params p;
     Cold c;
-    std::memset(&p, 0, sizeof p);
-    std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg;
-    p.n = n;
-    p.cold = &c;
-    c.pf.pf_id = pf->pf_id;
-    c.pf.r_isco = pf->r_isco;
-    c.pf.n_plunge = pf->n_plunge;
-    c.pf.plunge_r = pf->plunge_r;
-    c.pf.plunge_vt = pf->plunge_vt;
-    c.pf.plunge_vr = pf->plunge_vr;
-    c.pf.plunge_vphi = pf->plunge_vphi;
+    hh::fill(p, c, cfg, n, pf);      // (disc_area_factor reads the configuration and the point function's ISCO and plunging table)
     if (cfg->metric_id == GR_METRIC_TABULATED) return -1;
 #define HSM_RUN(M)                                                              \
     do {                                                                        \

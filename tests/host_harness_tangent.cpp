@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "../gradus.jl_amd/csrc/gr_device.hpp"
+#include "host_harness_common.hpp"
 
 using namespace grt;
 
@@ -19,7 +20,7 @@ static void run(const Params& p)
 {
     Metric m;
     m.load(p.cfg);
-    const LdsView no_lds{ nullptr, nullptr, nullptr, nullptr, nullptr };
+    const LdsView no_lds = hh::no_lds();
     for (int64_t j = 0; j < p.n; ++j) {
         Ray<Metric, DISC> ray;
         ray.init(m, p, j);
@@ -43,8 +44,7 @@ void hht_set_tangent_norm(int on) { g_tangent_norm = on ? 1 : 0; }
 int hht_ray_tangent(const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf, double* out)
 {
     Params p; Cold c;
-    std::memset(&p, 0, sizeof p); std::memset(&c, 0, sizeof c);
-    p.cfg = *cfg; p.n = rays->n; p.cold = &c;
+    hh::fill(p, c, cfg, rays->n, pf);
     c.src_mode = 2; c.out_mode = 5;
     std::memcpy(c.plane.x_obs, rays->x_obs, sizeof c.plane.x_obs);
     std::memcpy(c.plane.Mx, rays->Mx, sizeof c.plane.Mx);
@@ -61,11 +61,6 @@ int hht_ray_tangent(const gr_config* cfg, const gr_rayset* rays, const gr_pointf
     }
     c.height = cfg->disc_id == GR_DISC_DATUM ? rays->height : nullptr;
     c.lp_rmin = 0.0; c.lp_rmax = INFINITY; c.lp_pairs = out;
-    c.pf.pf_id = pf->pf_id; c.pf.filter_id = pf->filter_id; c.pf.fill = pf->fill; c.pf.r_isco = pf->r_isco;
-    c.pf.n_plunge = pf->n_plunge; c.pf.plunge_r = pf->plunge_r; c.pf.plunge_vt = pf->plunge_vt;
-    c.pf.plunge_vr = pf->plunge_vr; c.pf.plunge_vphi = pf->plunge_vphi;
-    c.winding_plane = cfg->winding_plane;
-    derive_params(p);
     p.tangent_norm = g_tangent_norm;
     p.disc_table = p.cfg.disc_table;
     p.cfg.upper_hemisphere = (p.cfg.upper_hemisphere ? 1 : 0);

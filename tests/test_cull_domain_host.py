@@ -1,5 +1,5 @@
 """The miss culls (Ray::start_decided, Ray::step) against the uncut trace over the whole domain their gate lets them
-act in, on the kernel logic compiled for the host (tests/host_harness_defer_cull.cpp): the scene table of tests/cull_scenes.py --
+act in, on the kernel logic compiled for the host (tests/host_harness_culls.cpp): the scene table of tests/cull_scenes.py --
 M != 1, |a| = M, observers face-on, edge-on, below the plane, on and just outside R_cull, rings and discs whose R_cull is R_esc,
 gtol near the gate's limit, windows off the centre and off the disc, and both outcomes of "λ1 comes first" -- and 40 scenes
 drawn inside the gate.  The library as shipped (every cull on) against every cull off: pixel bytes (NaN pattern included) and
@@ -11,9 +11,7 @@ import numpy as np
 import pytest
 
 import cull_scenes as CS
-import harness_defer_cull as Hd
-import harness_entry_cull as He
-import harness_pass_cull as Hp
+import harness_culls as H
 
 SIZE = 64
 ALL_TILES = np.arange((SIZE // 8) ** 2)
@@ -94,26 +92,26 @@ def test_lambda1_first_boundary_both_outcomes(G, name):
 
 
 def test_offdisc_every_tile_decided_and_census_ratios(G):
-    """A window off the disc: every ray is decided at the start, no tile is traced, and the census of each harness -- which formed
+    """A window off the disc: every ray is decided at the start, no tile is traced, and the census of each mechanism -- which forms
     its ratios from a denominator of 0 here -- reports 1.0: nothing was traced in either arm."""
     cfg, rc, on, off, c = _arms(G, "offdisc")
     assert c["start"] == 64 * 64 and c["whole_tiles_decided"] == 64 and c["attempted_on"] == 0 and c["hit_share"] == 0.0
     assert np.all(np.isnan(on["image"])) and np.all(on["status"] == int(G.StatusCodes.NoStatus))
     _, pf, _ = CS.configuration(G, CS.scene(G, "offdisc", SIZE))
-    res, _ = Hd.census(G, cfg, pf, ALL_TILES)
+    res, _ = H.census(G, cfg, pf, ALL_TILES, *H.DEFER)
     assert res["arms"]["all"]["wave_steps"] == 0 and res["arms"]["no-defer"]["wave_steps"] == 0
     assert res["defer_wave_steps_ratio"] == 1.0 and res["defer_accepted_steps_ratio"] == 1.0
     assert res["escape_switch_bracket_ratio"] == 1.0
-    assert all(a["same_image"] and a["same_status"] and a["wrongly_ended"] == 0 for a in res["arms"].values())
-    res, _ = Hp.census(G, cfg, pf, ALL_TILES)
+    assert all(a["same_image"] and a["same_status"] and a["wrongly_ended_early"] == 0 for a in res["arms"].values())
+    res, _ = H.census(G, cfg, pf, ALL_TILES, *H.PASS)
     assert res["arms"]["both+pass"]["whole_tiles_decided"] == 64
     assert res["pass_wave_steps_ratio"] == 1.0 and res["pass_accepted_steps_ratio"] == 1.0 and res["escape_switch_bracket_ratio"] == 1.0
-    res, _ = He.census(G, cfg, pf, ALL_TILES[:16])
+    res, _ = H.census(G, cfg, pf, ALL_TILES[:16], *H.ENTRY)
     assert res["entry_wave_steps_ratio"] == 1.0 and res["entry_accepted_steps_ratio"] == 1.0 and res["escape_switch_bracket_ratio"] == 1.0
     # a traced window still gets the quotient itself
     cfg_b, _, on_b, _, c_b = _arms(G, "bench")
     _, pf_b, _ = CS.configuration(G, CS.scene(G, "bench", SIZE))
-    res, _ = Hp.census(G, cfg_b, pf_b, ALL_TILES[:16])
+    res, _ = H.census(G, cfg_b, pf_b, ALL_TILES[:16], *H.PASS)
     a = res["arms"]
     assert res["pass_wave_steps_ratio"] == a["both+pass"]["wave_steps"] / a["both"]["wave_steps"] < 1.0
 

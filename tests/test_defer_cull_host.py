@@ -1,5 +1,5 @@
 """The defer cull (Ray::start_decided, Ray::step) on the kernel logic compiled for the host
-(tests/host_harness_defer_cull.cpp): whole 8 x 8 tiles traced as shipped, with the defer cull off, with the step loop's culls off
+(tests/host_harness_culls.cpp): whole 8 x 8 tiles traced as shipped, with the defer cull off, with the step loop's culls off
 and in full.  Pixel bytes (NaN pattern included) and statuses must be identical in all arms and no ray flagged; every ray the
 defer cull ended started outside R_cull going in, took exactly one accepted step, has NoStatus and a NaN pixel and misses in the
 full trace; the decisions at the start are those of the same ζ without the defer cull; every ray the start marks is ended; the
@@ -7,19 +7,13 @@ GRADUS_MI355X_ESCAPE_CULL switch ratio stays inside the bracket of the older tes
 closed forms themselves are those of the pass cull with a deeper depth limit: tests/test_pass_cull_bounds_host.py and
 tests/test_entry_cull_host.py check them against root finding and quadrature down to ζ_dip.  CPU only."""
 import json
-import os
-import sys
 
 import numpy as np
 import pytest
 
-import harness_defer_cull as Hd
-import harness_entry_cull as He
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
-
-import cull_census  # noqa: E402
-from harness_pass_cull import SCENES, scene  # noqa: E402
+import cull_scenes
+import harness_culls as H
+from cull_scenes import SCENES, bench_variant as scene
 
 
 def _check_exact(G, cfg, res, runs):
@@ -28,7 +22,7 @@ def _check_exact(G, cfg, res, runs):
         assert a["same_image"], arm
         assert a["same_status"], arm
         assert a["flagged"] == 0, arm
-        assert a["wrongly_ended"] == 0, arm
+        assert a["wrongly_ended_early"] == 0, arm
     on, off, start, full = runs["all"], runs["no-defer"], runs["start"], runs["full"]
     assert np.all(full["at_start"] == 0) and not np.any(full["marked"]) and not np.any(full["entry_step"] > 0)
     # the defer cull marks only as shipped: off alone and with the step loop's culls off no ray carries the bit
@@ -40,7 +34,7 @@ def _check_exact(G, cfg, res, runs):
     # the decisions at the start: those of the same ζ without the defer cull, and of the arm with the step loop's culls off
     assert np.array_equal(on["at_start"], off["at_start"]) and np.array_equal(on["at_start"], start["at_start"])
     assert not np.any(ended & (on["at_start"] == 1))
-    rc = Hd.gate_radius(cfg)
+    rc = H.gate_radius(cfg)
     assert np.all(on["r_start"][ended] > rc) and np.all(on["vr_start"][ended] < 0.0)
     assert np.all(on["nacc"][ended] == 1)
     assert np.all(on["status"][ended] == int(G.StatusCodes.NoStatus))
@@ -56,19 +50,19 @@ def _check_exact(G, cfg, res, runs):
 
 
 def test_constants_and_defaults():
-    """The older harnesses fill Params with memset + derive_params: they trace with the defer cull on.  ζ_dip < ζ_defer < ζ."""
-    assert Hd.default_defer_cull() == 1
-    assert Hd.zeta_dip() < Hd.zeta_defer() < Hd.zeta()
-    assert Hd.zeta() == He.zeta() and Hd.zeta_dip() == He.zeta_dip()
+    """memset + derive_params leave the entry cull and the defer cull on: render_tiles' defaults trace with both.  ζ_dip < ζ_defer < ζ."""
+    assert H.default_culls() == (1, 1)
+    assert H.zeta_dip() < H.zeta_defer() < H.zeta()
+    assert H.zeta_dip() == 0.2
 
 
 @pytest.fixture(scope="module")
 def bench(G):
     """The 400 tiles of tests/test_cull_host.py (25 600 rays of the 2048² bench plane), every arm once."""
-    cfg, pf = cull_census.bench_scene(G)
-    nt = cull_census.SIZE // 8
+    cfg, pf = cull_scenes.bench_scene(G)
+    nt = cull_scenes.SIZE // 8
     picks = np.random.default_rng(11).choice(nt * nt, size=400, replace=False)
-    res, runs = Hd.census(G, cfg, pf, picks)
+    res, runs = H.census(G, cfg, pf, picks, *H.DEFER)
     return cfg, pf, picks, res, runs
 
 
@@ -82,8 +76,8 @@ def test_bench_tiles_defer_cull_exact_and_fires(G, bench):
     assert a["all"]["wave_steps"] < a["no-defer"]["wave_steps"]
     # the entry cull keeps rays of its own (what chose kDeferCullZeta: at least 10 here)
     assert a["all"]["ended_on_entry"] >= 10
-    # the harness of the entry cull (memset + derive_params) traces the same rays with the defer cull on
-    old = He.render_tiles(G, cfg, pf, picks[:50], 1, 1, 1)
+    # render_tiles' own defaults (memset + derive_params and the library's ζ) trace the same rays as the explicit "all" arm
+    old = H.render_tiles(G, cfg, pf, picks[:50])
     assert np.array_equal(old["nacc"], runs["all"]["nacc"][:50]) and np.array_equal(old["nrej"], runs["all"]["nrej"][:50])
     # The ratio tests/test_gpu_escape_cull.py brackets at 2048²: accepted steps with GRADUS_MI355X_ESCAPE_CULL unset over =0
     print(f"GRADUS_MI355X_ESCAPE_CULL switch ratio on these tiles: {res['escape_switch_bracket_ratio']:.4f}")
@@ -98,9 +92,9 @@ def test_bench_tiles_each_switch_turns_the_defer_cull_off(G, bench):
     assert runs["all"]["defer_end"][:50].sum() > 0
     #                    step start entry defer zeta
     for name, args in {"defer": (1, 1, 1, 0, -1.0), "start": (1, 0, 1, 1, -1.0), "pass": (1, 1, 1, 1, 0.0), "escape": (0, 1, 1, 1, -1.0)}.items():
-        r = Hd.render_tiles(G, cfg, pf, t, *args)
+        r = H.render_tiles(G, cfg, pf, t, *args)
         assert not np.any(r["marked"]) and not np.any(r["defer_end"]), name
-        o = Hd.render_tiles(G, cfg, pf, t, *args[:3], 0, args[4])
+        o = H.render_tiles(G, cfg, pf, t, *args[:3], 0, args[4])
         for k in ("nacc", "nrej", "at_start", "entry_step", "status"):
             assert np.array_equal(r[k], o[k]), (name, k)
         assert r["image"].tobytes() == o["image"].tobytes(), name
@@ -112,10 +106,10 @@ def test_scenes_defer_cull_exact(G, name):
     (its misses that enter R_cull turn deeper than R_defer or fail the closed forms): there it must end nothing."""
     cfg, pf, _ = scene(G, **SCENES[name])
     tiles = np.arange(64)
-    res, runs = Hd.census(G, cfg, pf, tiles)
+    res, runs = H.census(G, cfg, pf, tiles, *H.DEFER)
     ended = _check_exact(G, cfg, res, runs)
     a = res["arms"]
-    print(name, json.dumps({k: a["all"][k] for k in ("decided_at_start", "ended_by_defer", "ended_on_entry", "accepted_steps")}),
+    print(name, json.dumps({k: a["all"][k] for k in ("decided_at_start_any", "ended_by_defer", "ended_on_entry", "accepted_steps")}),
           "no-defer", a["no-defer"]["ended_on_entry"], a["no-defer"]["accepted_steps"])
     if name == "theta30":
         assert ended.sum() == 0 and a["all"]["accepted_steps"] == a["no-defer"]["accepted_steps"]
@@ -134,7 +128,7 @@ def test_defer_cull_ends_nothing_where_it_cannot(G, case):
     else:
         cfg, pf, _ = scene(G, r_obs=30.0)
     tiles = np.arange(64)
-    res, runs = Hd.census(G, cfg, pf, tiles)
+    res, runs = H.census(G, cfg, pf, tiles, *H.DEFER)
     ended = _check_exact(G, cfg, res, runs)
     assert ended.sum() == 0 and not np.any(runs["all"]["marked"])
     assert np.array_equal(runs["all"]["nacc"], runs["no-defer"]["nacc"]) and np.array_equal(runs["all"]["nrej"], runs["no-defer"]["nrej"])

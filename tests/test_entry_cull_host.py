@@ -1,4 +1,4 @@
-"""The entry cull (Ray::step) on the kernel logic compiled for the host (tests/host_harness_entry_cull.cpp): whole
+"""The entry cull (Ray::step) on the kernel logic compiled for the host (tests/host_harness_culls.cpp): whole
 8 x 8 tiles traced with the entry cull on and off under every other cull.  Pixel bytes (NaN pattern included) and statuses must be
 identical, no ray flagged, no ray ended on entry a hit of the full trace; every such ray started outside R_cull and stands at or
 inside it after its last step; the cull must fire where it can and end nothing where it cannot.  The closed forms it decides by
@@ -10,20 +10,14 @@ time back at R_cull and the rates).  T_a^lo is asked to be <= 0 and nothing more
 the wedge ahead is the one the decision tests, and the formula is no bound of a negative time."""
 import json
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-import harness_entry_cull as He
-import harness_pass_cull as Hp
+import cull_scenes
+import harness_culls as H
 import test_pass_cull_bounds_host as B
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
-
-import cull_census  # noqa: E402
-from harness_pass_cull import SCENES, scene  # noqa: E402
+from cull_scenes import SCENES, bench_variant as scene
 
 
 def _check_exact(G, cfg, pf, tiles, res, runs):
@@ -31,17 +25,17 @@ def _check_exact(G, cfg, pf, tiles, res, runs):
         assert a["same_image"], arm
         assert a["same_status"], arm
         assert a["flagged"] == 0, arm
-        assert a["wrongly_ended"] == 0, arm
+        assert a["wrongly_ended_on_entry"] == 0, arm
     on = runs["all"]
     ended = on["entry_step"] > 0
     assert not np.any(runs["no-entry"]["entry_step"] > 0) and not np.any(runs["start"]["entry_step"] > 0)
     # against the full trace: every cull off
-    full = He.render_tiles(G, cfg, pf, tiles, 0, 0, 0, 0.0)
+    full = H.render_tiles(G, cfg, pf, tiles, step=0, start=0, entry=0, zeta=0.0)
     assert np.all(full["at_start"] == 0) and not np.any(full["entry_step"] > 0)
     assert on["image"].tobytes() == full["image"].tobytes()
     assert np.array_equal(on["status"], full["status"])
     assert not np.any(ended & (full["status"] == int(G.StatusCodes.IntersectedWithGeometry)))
-    rc = He.gate_radius(cfg)
+    rc = H.gate_radius(cfg)
     assert np.all(on["r_last"][ended] <= rc)
     assert np.all(on["r_start"][ended] > rc)
     assert np.all(on["vr_last"][ended] < 0.0)
@@ -56,27 +50,26 @@ def _check_exact(G, cfg, pf, tiles, res, runs):
 
 
 def test_derive_params_leaves_the_entry_cull_on():
-    """The older harnesses fill Params with memset + derive_params: they trace with the entry cull wherever r_cull and r_pass are finite."""
-    assert He.default_entry_cull() == 1
-    assert He.zeta_dip() == 0.2
-    assert He.zeta() == Hp.zeta()
+    """memset + derive_params leave the entry cull on: render_tiles' default traces with it wherever r_cull and r_pass are finite."""
+    assert H.default_culls()[0] == 1
+    assert H.zeta_dip() == 0.2
 
 
 def test_bench_tiles_entry_cull_exact_and_fires(G):
     """The 400 tiles of tests/test_cull_host.py (25 600 rays of the 2048² bench plane)."""
-    cfg, pf = cull_census.bench_scene(G)
-    nt = cull_census.SIZE // 8
+    cfg, pf = cull_scenes.bench_scene(G)
+    nt = cull_scenes.SIZE // 8
     picks = np.random.default_rng(11).choice(nt * nt, size=400, replace=False)
-    res, runs = He.census(G, cfg, pf, picks)
+    res, runs = H.census(G, cfg, pf, picks, *H.ENTRY)
     print(json.dumps(res, indent=1))
     ended = _check_exact(G, cfg, pf, picks, res, runs)
     a = res["arms"]
     assert ended.sum() > 0
-    assert a["all"]["decided_at_start"] == a["no-entry"]["decided_at_start"] == a["start"]["decided_at_start"] > 0
+    assert a["all"]["decided_at_start_any"] == a["no-entry"]["decided_at_start_any"] == a["start"]["decided_at_start_any"] > 0
     assert a["all"]["accepted_steps"] < a["no-entry"]["accepted_steps"] < a["start"]["accepted_steps"]
     assert a["all"]["wave_steps"] < a["no-entry"]["wave_steps"]
-    # the harness of the pass cull (memset + derive_params) traces the same rays with the entry cull on
-    old = Hp.render_tiles(G, cfg, pf, picks[:50], 1, 1)
+    # render_tiles' own defaults (memset + derive_params and the library's ζ) trace the same rays as the explicit "all" arm
+    old = H.render_tiles(G, cfg, pf, picks[:50])
     assert np.array_equal(old["nacc"], runs["all"]["nacc"][:50]) and np.array_equal(old["nrej"], runs["all"]["nrej"][:50])
     print(f"GRADUS_MI355X_ESCAPE_CULL switch ratio on these tiles: {res['escape_switch_bracket_ratio']:.4f}")
 
@@ -86,7 +79,7 @@ def test_scenes_entry_cull_exact_and_fires(G, name):
     """The scenes where the signs and closed forms can go wrong, at 64² (every tile)."""
     cfg, pf, _ = scene(G, **SCENES[name])
     tiles = np.arange(64)
-    res, runs = He.census(G, cfg, pf, tiles)
+    res, runs = H.census(G, cfg, pf, tiles, *H.ENTRY)
     print(json.dumps(res, indent=1))
     ended = _check_exact(G, cfg, pf, tiles, res, runs)
     assert ended.sum() > 0, name
@@ -101,7 +94,7 @@ def test_entry_cull_ends_nothing_where_it_cannot(G, case):
     else:
         cfg, pf, _ = scene(G, r_obs=30.0)
     tiles = np.arange(64)
-    res, runs = He.census(G, cfg, pf, tiles)
+    res, runs = H.census(G, cfg, pf, tiles, *H.ENTRY)
     ended = _check_exact(G, cfg, pf, tiles, res, runs)
     assert ended.sum() == 0
     a = res["arms"]
@@ -112,7 +105,7 @@ def test_entry_cull_ends_nothing_where_it_cannot(G, case):
 
 def _check_entry_bounds(cfg, a, rays):
     """The bounds at the asking state of each ray against root finding and quadrature; returns (bounds, asked, decided)."""
-    b = He.entry_bounds(cfg, rays.ravel())
+    b = H.entry_bounds(cfg, rays.ravel())
     asked = b["asked"] == 1.0
     assert np.all(b["u0"][asked] >= b["uc"][asked])          # at or inside R_cull
     assert np.all(b["vr"][asked] < 0.0)

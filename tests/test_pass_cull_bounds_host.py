@@ -1,5 +1,5 @@
 """The closed forms of the pass cull (KerrFamily::pass_cull_bounds) against independent numerics, ray by ray, on
-the kernel logic compiled for the host (tests/host_harness_pass_cull.cpp): the bracket of the radial turning point against the
+the kernel logic compiled for the host (tests/host_harness_culls.cpp): the bracket of the radial turning point against the
 quartic's root from numpy, the two Mino-time bounds against quadrature of du / sqrt(U), the phase-rate bounds against dψ/dτ on a
 grid, and every decided ray against the full host trace (a decided ray must be a miss).  CPU only.
 
@@ -12,14 +12,14 @@ import math
 import numpy as np
 import pytest
 
-import harness_pass_cull as Hp
-from harness_pass_cull import SCENES, scene
+import harness_culls as H
+from cull_scenes import SCENES, bench_variant as scene
 
 GL_X, GL_W = np.polynomial.legendre.leggauss(96)
 
 
 def tile_rays(tiles, H):
-    """plane indices of the tiles' rays, (len(tiles), 64), lanes as host_harness_pass_cull.cpp lays them out"""
+    """plane indices of the tiles' rays, (len(tiles), 64), lanes as host_harness_culls.cpp lays them out"""
     tiles = np.asarray(tiles, dtype=np.int64)
     tx, ty = tiles // (H // 8), tiles % (H // 8)
     lane = np.arange(64)
@@ -53,7 +53,7 @@ def _mino_time(poly_p, ut, u1):
 
 
 def _check_scene(G, cfg, pf, a, rays):
-    b = Hp.pass_bounds(cfg, rays.ravel())
+    b = H.pass_bounds(cfg, rays.ravel())
     gtol = cfg.abi_config().gtol
     formed = np.flatnonzero(b["Tb_hi"] > 0.0)          # rays whose radial side went through
     polar = np.flatnonzero(b["Om_hi"] > 0.0)           # ... and the polar side
@@ -93,7 +93,7 @@ def _check_scene(G, cfg, pf, a, rays):
 
 
 def _full_trace_hits(G, cfg, pf, tiles):
-    off = Hp.render_tiles(G, cfg, pf, tiles, 0, 0, 0.0)
+    off = H.render_tiles(G, cfg, pf, tiles, step=0, start=0, zeta=0.0)
     assert np.all(off["at_start"] == 0)
     return off["status"].ravel() == int(G.StatusCodes.IntersectedWithGeometry)
 

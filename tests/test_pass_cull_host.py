@@ -1,20 +1,15 @@
-"""The pass cull (Ray::start_decided) on the kernel logic compiled for the host (tests/host_harness_pass_cull.cpp):
+"""The pass cull (Ray::start_decided) on the kernel logic compiled for the host (tests/host_harness_culls.cpp):
 whole 8 x 8 tiles traced with the pass cull on and off, under the start cull alone and under all culls.  Pixel bytes (NaN pattern
 included) and statuses must be identical, no ray flagged, no decided ray a hit of the arm without the cull; the cull must decide
 something where it can and nothing where it cannot.  CPU only."""
 import json
-import os
-import sys
 
 import numpy as np
 import pytest
 
-import harness_pass_cull as Hp
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
-
-import cull_census  # noqa: E402
-from harness_pass_cull import SCENES, scene  # noqa: E402
+import cull_scenes
+import harness_culls as H
+from cull_scenes import SCENES, bench_variant as scene
 
 
 def _check_exact(res):
@@ -22,27 +17,27 @@ def _check_exact(res):
         assert a["same_image"], arm
         assert a["same_status"], arm
         assert a["flagged"] == 0, arm
-        assert a["wrongly_decided"] == 0, arm
+        assert a["wrongly_decided_by_pass"] == 0, arm
 
 
 def test_bench_tiles_pass_cull_exact_and_switch_ratio_in_bracket(G):
     """The 400 tiles of tests/test_cull_host.py::test_bench_tiles_all_arms_exact_and_fewer_steps (25 600 rays of the 2048² bench
     plane) with the pass cull as the library has it."""
-    cfg, pf = cull_census.bench_scene(G)
-    nt = cull_census.SIZE // 8
+    cfg, pf = cull_scenes.bench_scene(G)
+    nt = cull_scenes.SIZE // 8
     picks = np.random.default_rng(11).choice(nt * nt, size=400, replace=False)
-    res, runs = Hp.census(G, cfg, pf, picks)
+    res, runs = H.census(G, cfg, pf, picks, *H.PASS)
     print(json.dumps(res, indent=1))
     _check_exact(res)
     a = res["arms"]
     for with_pass, without in (("start+pass", "start"), ("both+pass", "both")):
         assert a[with_pass]["decided_by_pass_cull"] > 0 and a[without]["decided_by_pass_cull"] == 0
-        assert a[with_pass]["decided_at_start"] == a[without]["decided_at_start"] > 0      # the older test decides what it did
+        assert a[with_pass]["decided_by_start_test"] == a[without]["decided_by_start_test"] > 0      # the older test decides what it did
         assert a[with_pass]["accepted_steps"] < a[without]["accepted_steps"]
         assert a[with_pass]["wave_steps"] < a[without]["wave_steps"]
     # a ray the pass cull decides takes no step at all, keeps NoStatus and the fill value
     r = runs["both+pass"]
-    dec = r["at_start"] == 2
+    dec = r["by_pass"] == 1
     assert np.all(r["nacc"][dec] + r["nrej"][dec] == 0)
     assert np.all(r["status"][dec] == int(G.StatusCodes.NoStatus))
     assert np.all(np.isnan(r["image"][dec]))
@@ -58,7 +53,7 @@ def test_bench_tiles_pass_cull_exact_and_switch_ratio_in_bracket(G):
 def test_scenes_pass_cull_exact_and_fires(G, name):
     """The scenes where the signs and closed forms can go wrong, at 64² (every tile)."""
     cfg, pf, _ = scene(G, **SCENES[name])
-    res, _ = Hp.census(G, cfg, pf, np.arange(64))
+    res, _ = H.census(G, cfg, pf, np.arange(64), *H.PASS)
     print(json.dumps(res, indent=1))
     _check_exact(res)
     a = res["arms"]
@@ -74,7 +69,7 @@ def test_pass_cull_decides_nothing_where_it_cannot(G, case):
         cfg, pf, _ = scene(G, r_out=500.0)
     else:
         cfg, pf, _ = scene(G, r_obs=30.0)
-    res, _ = Hp.census(G, cfg, pf, np.arange(64))
+    res, _ = H.census(G, cfg, pf, np.arange(64), *H.PASS)
     _check_exact(res)
     a = res["arms"]
     for with_pass, without in (("start+pass", "start"), ("both+pass", "both")):

@@ -2,23 +2,16 @@
 an S x 9 block of 64-bit partial sums added into nine counters, against numpy; rows left at zero, row counts that are no multiple
 of the unrolled four, counters that already hold an earlier launch's sums, wrapping sums, and the block left zero."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_stats_fold.so")
-SRC = [os.path.join(HERE, "host_harness_stats_fold.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_stats_fold.hpp")]
+import hostbuild
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, SRC[0]])
-    L = C.CDLL(SO)
+    L = hostbuild.load("host_harness_stats_fold.cpp")
     L.hsf_column_sum.restype = C.c_ulonglong
     L.hsf_column_sum.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.hsf_fold.restype = None

@@ -4,24 +4,18 @@ in ascending tile index (a stable partition, against numpy); the flag patterns a
 flag; tile counts that are no multiple of the workgroup size, smaller than it, one and zero; one tile per thread as on the device;
 threads placing their chunks in any order give the same permutation."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SO = os.path.join(HERE, "libhost_harness_tile_order.so")
-SRC = [os.path.join(HERE, "host_harness_tile_order.cpp"), os.path.join(ROOT, "gradus.jl_amd", "csrc", "gr_tile_order.hpp")]
+import hostbuild
+
 SENTINEL = 0xFFFFFFFF
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, SRC[0]])
-    L = C.CDLL(SO)
+    L = hostbuild.load("host_harness_tile_order.cpp")
     L.hto_chunk_lo.restype = C.c_int64
     L.hto_chunk_lo.argtypes = [C.c_int64, C.c_int, C.c_int]
     L.hto_partition.restype = C.c_uint32
