@@ -16,9 +16,10 @@ from .corona import (BeamedPointSource, BothHemispheres, CoronaGeodesics, DiscCo
                      energy_ratio, lorentz_factor, sky_angles_to_velocity, tetradframe_matrix, tracecorona,
                      DEFAULT_β_ANGLES, LongitudalArms, corona_arm_traces, corona_arms, disc_corona_profile, ring_corona_profile)
 from . import adaptive, grids
-from .adaptive import (AdaptiveSky, AxisLimits, RadialBox, StepBlockCodes, adaptive_solve, bin_emissivity_grid, bin_redshift_grid,
-                       bin_time_grid, check_refine, empty_fraction, evaluate_refinement_metric, fill_sky_values, find_need_refine,
-                       fine_refine_function, interpolate_emissivity_grid, refine_and_trace, refine_function, refine_to_level,
+from .adaptive import (AdaptivePlane, AdaptiveSky, AxisLimits, RadialBox, StepBlockCodes, adaptive_solve, bin_emissivity_grid, bin_redshift_grid,
+                       bin_time_grid, check_refine, check_refine_plane, empty_fraction, evaluate_refinement_metric, fill_sky_values, find_need_refine,
+                       fine_refine_function, interpolate_emissivity_grid, refine_and_trace, refine_function, refine_plane,
+                       refine_to_level,
                        step_block, trace_initial, trace_step, unpack_sky)
 from .grids import AdaptiveGrid
 from .distributed import gather_buffers, gather_image, gather_image_async, gather_points, shard_plan

@@ -316,7 +316,7 @@ class gr_skycells(C.Structure):
 
 
 GR_SKY_MAX_BOXES = 8
-GR_SKY_CRIT_DEFAULT, GR_SKY_CRIT_FUNCTION, GR_SKY_CRIT_FINE, GR_SKY_CRIT_LEVEL = 0, 1, 2, 3
+GR_SKY_CRIT_DEFAULT, GR_SKY_CRIT_FUNCTION, GR_SKY_CRIT_FINE, GR_SKY_CRIT_LEVEL, GR_SKY_CRIT_PLANE = 0, 1, 2, 3, 4
 GR_SKY_MAP_EMISSIVITY, GR_SKY_MAP_REDSHIFT, GR_SKY_MAP_TIME = 0, 1, 2
 
 
@@ -453,6 +453,12 @@ EXPORTS = [
     "gr_disc_area_factor",
     "gr_sky_bin_grid",
     "gr_sky_fill",
+    "gr_plane_cells",
+    "gr_plane_cells_device",
+    "gr_plane_cells_multi",
+    "gr_sky_create_plane",
+    "gr_sky_download_points",
+    "gr_sky_fill_plane",
     "gr_render_endpoints_multi",
     "gr_trace_endpoints_multi",
     "gr_rayset_endpoints_multi",
@@ -550,6 +556,12 @@ def load():
     L.gr_disc_area_factor.argtypes = [vp, cfgp, pfp, vp, i64, vp]
     L.gr_sky_bin_grid.argtypes = [vp, i32, vp, i64, vp, i64, vp, vp, vp]
     L.gr_sky_fill.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    L.gr_plane_cells.argtypes = [vp, cfgp, plp, vp, vp, i64, vp, stp]
+    L.gr_plane_cells_device.argtypes = [vp, cfgp, plp, vp, vp, i64, vp, vp, vp]
+    L.gr_plane_cells_multi.argtypes = [ctxa, i32, cfgp, plp, vp, vp, i64, vp, vp]
+    L.gr_sky_create_plane.argtypes = [vp, cfgp, plp, vp, i32, C.POINTER(vp)]
+    L.gr_sky_download_points.argtypes = [vp, i64, i64, vp]
+    L.gr_sky_fill_plane.argtypes = [vp, pfp, vp, vp, i64, vp, i64, vp, vp]
     L.gr_render_endpoints_multi.argtypes = [ctxa, i32, cfgp, plp, i64, vp, vp]
     L.gr_trace_endpoints_multi.argtypes = [ctxa, i32, cfgp, vp, i64, vp, i64, vp, vp]
     L.gr_rayset_endpoints_multi.argtypes = [ctxa, i32, cfgp, rsp, vp, vp]

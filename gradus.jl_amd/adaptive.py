@@ -19,6 +19,12 @@ default criterion, `refine_to_level`, `refine_function` / `fine_refine_function`
 evaluated on the mirror against the pair list the device returns.  The maps and `fill_sky_values` read the mirror unless asked
 for `route="device"`, which forms them from the device's rows (`gr_sky_bin_grid`, `gr_sky_fill`) without a download.
 
+`AdaptivePlane(m, x, d)` (src/image-planes/adaptive-plane.jl) is the same tree laid over an observer's image plane (α, β): its rows
+are GeodesicPoints (`POINT_DTYPE`), its criterion `check_refine_plane` (hit against miss, or end points on the disc too far
+apart), every step's new cells one `gr_plane_cells` launch, `resident=True` as above (`gr_sky_create_plane`), and
+`fill_sky_values` interpolates one value per cell first across α, then along β (`gr_sky_fill_plane` for `route="device"`).  The
+maps and the drivers below read a corona's rows and refuse a plane.
+
 The drivers of adaptive-sample.jl:486-842 -- `empty_fraction`, `evaluate_refinement_metric`, `step_block`,
 `adaptive_solve` -- work on both kinds of sky.
 """
@@ -38,12 +44,38 @@ SKY_DTYPE = np.dtype([(f, np.float64) for f in SKY_FIELDS])
 TWO_PI = 2.0 * math.pi
 
 
-def make_null(n=1):
-    """make_null(CoronaGridValues): n rows of NaN"""
-    out = np.empty(n, dtype=SKY_DTYPE)
-    for f in SKY_FIELDS:
-        out[f] = np.nan
+def make_null(n=1, dtype=SKY_DTYPE):
+    """make_null(CoronaGridValues): n rows of NaN -- or, for another row type, n rows with NaN in every float field, 0 in every
+    integer field and, for a GeodesicPoint (POINT_DTYPE), the status NoStatus"""
+    out = np.zeros(n, dtype=dtype)
+    for f in out.dtype.names:
+        if out.dtype[f].base.kind == "f":
+            out[f] = np.nan
+    if "status" in out.dtype.names and out.dtype["status"].kind == "i":
+        out["status"] = _NO_STATUS
     return out
+
+
+_HIT, _NO_STATUS = 2, 3          # StatusCodes.IntersectedWithGeometry, StatusCodes.NoStatus
+
+
+def _is_plane(sky):
+    return bool(getattr(sky, "is_plane", False))
+
+
+def _both_miss(sky, i1, i2):
+    """a pair of cells whose rays both miss the geometry: NaN r on a corona sky, a status other than IntersectedWithGeometry on a
+    plane"""
+    if _is_plane(sky):
+        status = sky.values["status"]
+        return (status[i1] != _HIT) & (status[i2] != _HIT)
+    r = sky.values["r"]
+    return np.isnan(r[i1]) & np.isnan(r[i2])
+
+
+def _corona_only(sky, name):
+    if _is_plane(sky):
+        raise TypeError(f"{name} reads the (t, r, ϕ, g, J) rows of a corona's sky: an AdaptivePlane holds GeodesicPoints")
 
 
 def _isapprox(a, b, rtol):
@@ -168,11 +200,36 @@ def refine_to_level(n):
 
     def refiner(sky, i1, i2):
         i1, i2 = np.asarray(i1), np.asarray(i2)
-        both_miss = np.isnan(sky.values["r"][i1]) & np.isnan(sky.values["r"][i2])
-        return ~both_miss & (sky.grid.level[i2] < n)
+        return ~_both_miss(sky, i1, i2) & (sky.grid.level[i2] < n)
 
     refiner.gr_criterion = _criterion(3, level=n)
     return refiner
+
+
+def check_refine_plane(sky, i1, i2, percentage=20):
+    """The criterion of an AdaptivePlane (adaptive-plane.jl:24-50) over index arrays: a pair whose rays both miss the geometry is
+    left alone, a pair of which one hits is refined, a pair that both hit is refined where log10 of the coordinate radius x[1] or
+    θ = x[2] mod 2π differ by more than `percentage` per cent.  (The reference also computes a ϕ term and never uses it.)"""
+    v1, v2 = sky.values[np.asarray(i1)], sky.values[np.asarray(i2)]
+    hit1, hit2 = v1["status"] == _HIT, v2["status"] == _HIT
+    x1, x2 = v1["x"], v2["x"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r_too_coarse = ~_isapprox(np.log10(x1[..., 1]), np.log10(x2[..., 1]), percentage / 100)
+        θ_too_coarse = ~_isapprox(np.mod(x1[..., 2], TWO_PI), np.mod(x2[..., 2], TWO_PI), percentage / 100)
+    return (hit1 | hit2) & (~(hit1 & hit2) | r_too_coarse | θ_too_coarse)
+
+
+check_refine_plane.gr_criterion = _criterion(4, percentage=20)
+
+
+def refine_plane(percentage=20):
+    """check_refine_plane at another percentage, as a criterion a resident plane evaluates on the device"""
+
+    def _refine(sky, i1, i2):
+        return check_refine_plane(sky, i1, i2, percentage=percentage)
+
+    _refine.gr_criterion = _criterion(4, percentage=percentage)
+    return _refine
 
 
 def gr_criterion_of(check_refine):
@@ -200,11 +257,17 @@ class AdaptiveSky:
     """AdaptiveSky(calc_values, check_refine; pole_offset = 1e-6) -- the generic form, adaptive-sky.jl:26-46: `calc_values(cos θ[],
     ϕ[])` returns a structured array of SKY_DTYPE -- or AdaptiveSky(m, corona, d; ensemble, t_max, solver_opts...)
     (adaptive-sample.jl:156-178), whose `calc_values` is one `gr_sky_cells` launch per call.  With `resident=True` the tree and
-    the rows of the latter live on the device (one context), and `grid` / `values` are mirrors of them."""
+    the rows of the latter live on the device (one context), and `grid` / `values` are mirrors of them.
+    The generic form takes `limits=(x1, x2, y1, y2)`, `x_periodic=` and `null=` (one null row of another structured dtype: the
+    row type of `calc_values`) for a grid over something else than a source's sky -- AdaptivePlane builds on it."""
 
-    def __init__(self, *args, check_refine=None, pole_offset=1e-6, **kwargs):
+    def __init__(self, *args, check_refine=None, pole_offset=1e-6, limits=None, x_periodic=True, null=None, **kwargs):
         self._dev = None
+        self._null = make_null(1) if null is None else np.array(null).reshape(1)
+        self._dtype = self._null.dtype
         resident = bool(kwargs.pop("resident", False))
+        if len(args) == 3 and not callable(args[0]) and (limits is not None or null is not None):
+            raise TypeError("limits / null belong to the generic form AdaptiveSky(calc_values, check_refine)")
         if len(args) == 3 and not callable(args[0]):
             if check_refine is not None:
                 raise TypeError("AdaptiveSky(m, corona, d) brings the default criterion; pass another to trace_step")
@@ -226,10 +289,13 @@ class AdaptiveSky:
             else:
                 raise TypeError("AdaptiveSky(calc_values, check_refine) or AdaptiveSky(m, corona, d)")
             self.tracer = None
-        self._grid = AdaptiveGrid(math.cos(pole_offset), math.cos(math.pi - pole_offset), -math.pi, math.pi)
+        if limits is None:
+            self._grid = AdaptiveGrid(math.cos(pole_offset), math.cos(math.pi - pole_offset), -math.pi, math.pi)
+        else:
+            self._grid = AdaptiveGrid(*limits, x_periodic=x_periodic)
         self.calculate_value = calc_values
         self.check_refine = criterion
-        self._values = make_null(1)
+        self._values = self._null.copy()
         self._n_values = 0
         if resident:
             self._make_resident()
@@ -240,6 +306,17 @@ class AdaptiveSky:
     @property
     def resident(self):
         return self._dev is not None
+
+    @property
+    def is_plane(self):
+        """are the rows GeodesicPoints (an AdaptivePlane) rather than a corona's (t, r, ϕ, g, J, status)?"""
+        from ._lib import POINT_DTYPE
+
+        return self._dtype == POINT_DTYPE
+
+    def make_null(self, n=1):
+        """n null rows of this sky's row type"""
+        return np.repeat(self._null, n)
 
     @property
     def n_cells(self):
@@ -279,6 +356,16 @@ class AdaptiveSky:
         tr = self.tracer
         if tr["ensemble"].multi:
             raise ValueError("AdaptiveSky(resident=True) keeps the sky on ONE context")
+        if self.is_plane:
+            (x1, x2), (y1, y2) = self._grid.limits
+            limits = (C.c_double * 4)(x1, x2, y1, y2)
+            handle = C.c_void_p()
+            self._L = _lib.load()
+            _lib.check(self._L.gr_sky_create_plane(tr["ensemble"].ctx.handle, C.byref(tr["cfg"]), C.byref(tr["plane"]), limits,
+                                                   int(self._grid.x_periodic), C.byref(handle)))
+            self._dev = handle
+            self._stale = False
+            return
         source = _lib.gr_skycells()
         for q in range(4):
             source.x_src[q] = tr["x_src"][q]
@@ -326,7 +413,7 @@ class AdaptiveSky:
             return
         g._reserve(n - g.n)
         if n + 1 > self._values.size:
-            grown = np.empty(max(n + 1, 2 * self._values.size, 1024), dtype=SKY_DTYPE)
+            grown = np.empty(max(n + 1, 2 * self._values.size, 1024), dtype=self._dtype)
             grown[:self._n_values + 1] = self._values[:self._n_values + 1]
             self._values = grown
         groups = count // 9 if first >= 10 else 0
@@ -334,8 +421,10 @@ class AdaptiveSky:
         kids = np.empty((groups, 9), dtype=np.int64)
         ptr = lambda a: C.c_void_p(a[first:].ctypes.data)
         _lib.check(self._L.gr_sky_download(self._dev, first, count, ptr(g.pos), ptr(g.level), ptr(g.children), ptr(g.neighbours), ptr(g.parent),
-                                           ptr(g.location), ptr(self._values), C.c_void_p(refined.ctypes.data) if groups else None,
-                                           C.c_void_p(kids.ctypes.data) if groups else None))
+                                           ptr(g.location), None if self.is_plane else ptr(self._values),
+                                           C.c_void_p(refined.ctypes.data) if groups else None, C.c_void_p(kids.ctypes.data) if groups else None))
+        if self.is_plane:
+            _lib.check(self._L.gr_sky_download_points(self._dev, first, count, ptr(self._values)))
         if groups:
             g.children[refined] = kids
         g.n = n
@@ -351,6 +440,9 @@ class AdaptiveSky:
         cr = gr_criterion_of(check_refine)
         if cr is None:
             return None
+        if self.is_plane != (cr.kind == _lib.GR_SKY_CRIT_PLANE) and cr.kind != _lib.GR_SKY_CRIT_LEVEL:
+            raise TypeError("a plane's criteria are check_refine_plane / refine_plane and refine_to_level; check_refine, refine_function "
+                            "and fine_refine_function read the rows of a corona's sky (and check_refine_plane those of a plane)")
         count = C.c_int64(0)
         _lib.check(self._L.gr_sky_find_need_refine(self._dev, C.byref(cr), C.byref(count)))
         return int(count.value)
@@ -442,7 +534,7 @@ class AdaptiveSky:
     def _append(self, rows):
         need = self.n_values + rows.size
         if need + 1 > self._values.size:
-            grown = np.empty(max(need + 1, 2 * self._values.size, 1024), dtype=SKY_DTYPE)
+            grown = np.empty(max(need + 1, 2 * self._values.size, 1024), dtype=self._dtype)
             grown[:self.n_values + 1] = self._values[:self.n_values + 1]
             self._values = grown
         self._values[self.n_values + 1:need + 1] = rows
@@ -453,8 +545,8 @@ class AdaptiveSky:
         cells = np.asarray(cells, dtype=np.int64)
         pos = self.grid.pos[cells]
         rows = np.asarray(self.calculate_value(np.ascontiguousarray(pos[:, 0]), np.ascontiguousarray(pos[:, 1])))
-        if rows.dtype != SKY_DTYPE or rows.shape != (cells.size,):
-            raise ValueError("calc_values must return one SKY_DTYPE row per cell")
+        if rows.dtype != self._dtype or rows.shape != (cells.size,):
+            raise ValueError(f"calc_values must return one row of {'SKY_DTYPE' if self._dtype == SKY_DTYPE else self._dtype} per cell")
         return rows
 
 
@@ -506,7 +598,7 @@ def refine_and_trace(sky, cell_ids):
         sky._device_refine(cell_ids)
         return sky
     kids = sky.grid.refine_many(cell_ids)
-    rows = make_null(kids.size).reshape(kids.shape)
+    rows = sky.make_null(kids.size).reshape(kids.shape)
     rows[:, 4] = sky.values[cell_ids]
     outer = np.ones(9, dtype=bool)
     outer[4] = False
@@ -560,14 +652,121 @@ def _device_route(sky, route):
     return True
 
 
-def fill_sky_values(sky, grid, route=None, cells=False):
+def _plane_cell_values(sky, pf, metric):
+    """one double per cell (row 0 included) for fill_sky_values of a plane: x[0] of every point (the reference's default pf), an
+    array of the caller's, a built-in point function evaluated by the device on the mirror's points (gr_apply_pointfunction, as
+    the resident route evaluates it on the device's), any other PointFunction point by point, or a callable given the points"""
+    from .pointfunctions import AbstractPointFunction
+
+    points = sky.values
+    if pf is None:
+        return np.ascontiguousarray(points["x"][:, 0])
+    if isinstance(pf, AbstractPointFunction):
+        tracer = getattr(sky, "tracer", None)
+        val = np.full(points.size, np.nan)
+        if pf.fusable:
+            if tracer is None:
+                raise TypeError("a built-in point function is evaluated on the device: this sky has no tracer (pass a callable over the points)")
+            from .rendering import apply_pointfunction
+
+            val[1:] = apply_pointfunction(tracer["ensemble"], tracer["config"], pf, points[1:], tracer["cfg"].lambda1)
+        else:
+            max_time = tracer["cfg"].lambda1 if tracer is not None else math.inf
+            val[1:] = [pf(metric, gp, max_time) for gp in points[1:]]
+        return val
+    val = np.ascontiguousarray(pf(points) if callable(pf) else pf, dtype=np.float64)
+    if val.shape != (points.size,):
+        raise ValueError("pf must give one value per cell, row 0 included")
+    return val
+
+
+def _fill_plane_values(sky, x_grid, y_grid, metric=None, pf=None, route=None, cells=False):
+    """fill_sky_values of an AdaptivePlane (adaptive-plane.jl:100-181) -> out[β, α].  Per column (an α of the x grid) the β grid is
+    walked ascending and every run of points held by one cell c is recorded; c's value is interpolated across α with its left
+    (x < pos_x(c)) or right neighbour -- unless there is none, it lies across the periodic wrap, or its ray did not hit -- and
+    the column is interpolated linearly in β between pos_y of its cells.  Where the reference is wrong or cannot run: the
+    neighbour's x is its x position (the reference reads pos[2], a typo); a column with fewer than two cells is NaN (the
+    reference indexes out of bounds); the image is out[β index, α index] (the reference's reshape is meaningful for square grids
+    only); the values are doubles; the β grid may come in any order."""
+    from .pointfunctions import AbstractPointFunction
+
+    if _device_route(sky, route):
+        import ctypes as C
+
+        from . import _lib
+
+        x_grid, y_grid = np.ascontiguousarray(x_grid), np.ascontiguousarray(y_grid)
+        out = np.empty((y_grid.size, x_grid.size))
+        held = np.empty((y_grid.size, x_grid.size, 2), dtype=np.int64) if cells else None
+        s, keep, val = None, None, None
+        if isinstance(pf, AbstractPointFunction) and pf.fusable:
+            from .rendering import abi_pointfunction
+
+            s, keep = abi_pointfunction(pf)
+        elif pf is not None:
+            val = _plane_cell_values(sky, pf, metric)
+        _lib.check(sky._L.gr_sky_fill_plane(sky._dev, None if s is None else C.byref(s), None if val is None else C.c_void_p(val.ctypes.data),
+                                            C.c_void_p(x_grid.ctypes.data), x_grid.size, C.c_void_p(y_grid.ctypes.data), y_grid.size,
+                                            C.c_void_p(out.ctypes.data), None if held is None else C.c_void_p(held.ctypes.data)))
+        del keep
+        return (out, (held[..., 0].copy(), held[..., 1].copy())) if cells else out
+    g, val, status = sky.grid, _plane_cell_values(sky, pf, metric), sky.values["status"]
+    out = np.full((y_grid.size, x_grid.size), np.nan)
+    lower, upper = (np.zeros(out.shape, dtype=np.int64) for _ in range(2))
+    order = np.argsort(y_grid, kind="stable")          # ascending, NaN last, equal values in the caller's order (theta_order)
+    ys = y_grid[order]
+    for k, x in enumerate(x_grid):
+        idx = np.fromiter((g.get_parent_index(x, y) for y in ys), dtype=np.int64, count=ys.size)
+        idx = idx[idx != 0]
+        if idx.size == 0:
+            continue
+        first = np.ones(idx.size, dtype=bool)
+        first[1:] = idx[1:] != idx[:-1]
+        held = idx[first]
+        if held.size < 2:
+            continue
+        cx = g.pos[held, 0]
+        left = x < cx
+        nb = np.where(left, g.neighbours[held, 3], g.neighbours[held, 1])
+        nx = g.pos[nb, 0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            usable = (nb != 0) & np.where(left, nx < cx, nx > cx) & (status[nb] == _HIT)
+            w = (x - nx) / (cx - nx)
+            from_left = (1.0 - w) * val[nb] + w * val[held]
+            w = (x - cx) / (nx - cx)
+            from_right = (1.0 - w) * val[held] + w * val[nb]
+            values = np.where(usable, np.where(left, from_left, from_right), val[held])
+            column = g.pos[held, 1]
+            i = np.clip(np.searchsorted(column, ys, side="right"), 1, column.size - 1) - 1
+            w = (ys - column[i]) / (column[i + 1] - column[i])
+            out[order, k] = (1.0 - w) * values[i] + w * values[i + 1]
+        lower[order, k], upper[order, k] = held[i], held[i + 1]
+    return (out, (lower, upper)) if cells else out
+
+
+def fill_sky_values(sky, grid, route=None, cells=False, metric=None, pf=None):
     """fill_sky_values(sky, N) -> (ϕ grid, θ grid, rows[θ, ϕ]); fill_sky_values(sky, (ϕ grid, θ grid)) -> rows[θ, ϕ]
     (adaptive-sample.jl:196-250): per column of ϕ, the cells that hold the grid's points, sorted by θ and linearly interpolated.
     All six fields are averaged: the reference's _to_vector packs five of the six into a six-vector and so drops the status
     (adaptive-sample.jl:28); a column with fewer than two cells (the reference indexes out of bounds there) is NaN.
     `cells=True` appends (lower cell[θ, ϕ], upper cell[θ, ϕ]) -- the two cells every point is interpolated between, 0 in a NaN
     column -- to what is returned.  `route="device"` forms the image on a resident sky's device (gr_sky_fill) instead of
-    reading the mirror.  The θ grid may be in any order on both routes."""
+    reading the mirror.  The θ grid may be in any order on both routes.
+    On an AdaptivePlane: fill_sky_values(sky, N, metric=m) -> (α grid, β grid, out[β, α]) and fill_sky_values(sky, (α grid, β grid),
+    metric=m) -> out[β, α] of adaptive-plane.jl:93-181, one double per point: `pf` is a point function (None: the coordinate time
+    x[0] of the end point, the reference's default; a built-in of ConstPointFunctions is evaluated on the device; any other
+    callable is given the mirror's points, row 0 included, and returns one value per row; an array is taken as those values).
+    `route="device"`: gr_sky_fill_plane.  See _fill_plane_values for what is decided where the reference cannot run."""
+    if _is_plane(sky):
+        if np.isscalar(grid):
+            (x1, x2), (y1, y2) = sky.grid.limits
+            x_grid, y_grid = np.linspace(x1, x2, int(grid)), np.linspace(y1, y2, int(grid))
+            filled = _fill_plane_values(sky, x_grid, y_grid, metric=metric, pf=pf, route=route, cells=cells)
+            return (x_grid, y_grid) + (filled if cells else (filled,))
+        x_grid, y_grid = (np.asarray(a, dtype=np.float64) for a in grid)
+        return _fill_plane_values(sky, x_grid, y_grid, metric=metric, pf=pf, route=route, cells=cells)
+    if pf is not None:
+        raise TypeError("pf belongs to an AdaptivePlane: a corona's sky is filled with its six row fields")
     if np.isscalar(grid):
         ϕ_grid = np.linspace(-math.pi, math.pi, int(grid))
         θ_grid = np.linspace(0.0, math.pi, int(grid))
@@ -634,6 +833,7 @@ def bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky, Γ=2, ensemble=None, route=N
     routes agree to rounding (DESIGN_measurements.md §M33) with one exception: for KerrRefractive, at radii within 1.25 of its
     corona_radius, the device's γ A carries ∂n/∂r of the refractive index and numpy's (metrics.KerrRefractive._components)
     does not, so the maps differ by up to 1.6 % in the bins of those radii."""
+    _corona_only(sky, "bin_emissivity_grid")
     if _device_route(sky, route):
         return sky.device_bin_grid("emissivity", r_bins, ϕ_bins, Γ=Γ)
     from .corona import _plunging_table, _proper_area, keplerian_velocity_projector, lorentz_factor
@@ -668,6 +868,7 @@ def bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky, Γ=2, ensemble=None, route=N
 def bin_redshift_grid(r_bins, ϕ_bins, sky, route=None):
     """bin_redshift_grid(r_bins, ϕ_bins, sky) (adaptive-sample.jl:364-406): the solid-angle weighted mean of g per bin;
     `route="device"`: on a resident sky's device"""
+    _corona_only(sky, "bin_redshift_grid")
     if _device_route(sky, route):
         return sky.device_bin_grid("redshift", r_bins, ϕ_bins, Γ=None)
     return _bin_grid(sky, r_bins, ϕ_bins, lambda v: v["g"])
@@ -676,6 +877,7 @@ def bin_redshift_grid(r_bins, ϕ_bins, sky, route=None):
 def bin_time_grid(r_bins, ϕ_bins, sky, route=None):
     """bin_time_grid(r_bins, ϕ_bins, sky) (adaptive-sample.jl:408-450): the solid-angle weighted mean of t per bin;
     `route="device"`: on a resident sky's device"""
+    _corona_only(sky, "bin_time_grid")
     if _device_route(sky, route):
         return sky.device_bin_grid("time", r_bins, ϕ_bins, Γ=None)
     return _bin_grid(sky, r_bins, ϕ_bins, lambda v: v["t"])
@@ -752,6 +954,69 @@ def _make_emissivity_tracer(m, corona, d, *, ensemble=None, t_max=1_000_000.0, *
     return calc_values, keep
 
 
+def _make_plane_tracer(m, x, d, *, ensemble=None, t_max=None, **solver_opts):
+    """_init_adaptive_tracer (adaptive-plane.jl:1-22): chart_for_metric(m, 2 * 2 x[1]), no callback, λ in (0, t_max = 2 x[1]).
+    Returns (calc_values(α[], β[]) -> POINT_DTYPE rows, what it keeps alive)."""
+    import ctypes as C
+
+    from . import _lib
+    from .tracing import chart_for_metric, lnr_momentum_to_global_velocity_matrix, tracing_configuration
+
+    x = np.array(x, dtype=np.float64)
+    t_max = 2 * x[1] if t_max is None else float(t_max)
+    solver_opts.setdefault("chart", chart_for_metric(m, 2 * 2 * x[1]))
+    config = tracing_configuration(m, x, np.zeros((1, 4)), d, (0.0, t_max), ensemble=ensemble, **solver_opts)
+    ens = config.ensemble
+    cfg = config.abi_config()
+    plane = _lib.gr_plane()
+    for q in range(4):
+        plane.x_obs[q] = x[q]
+    for q, val in enumerate(np.ascontiguousarray(lnr_momentum_to_global_velocity_matrix(m, x)).ravel()):
+        plane.Mx[q] = val
+    L = _lib.load()
+    keep = {"config": config, "cfg": cfg, "plane": plane, "ensemble": ens, "x_obs": x, "launches": []}
+
+    def calc_values(α, β):
+        α, β = np.ascontiguousarray(α, dtype=np.float64), np.ascontiguousarray(β, dtype=np.float64)
+        out = np.zeros(α.size, dtype=_lib.POINT_DTYPE)
+        if ens.multi:
+            ctx_arr, ctx_stats = _lib.ctx_array(ens.contexts)
+            _lib.check(L.gr_plane_cells_multi(ctx_arr, len(ens.contexts), C.byref(cfg), C.byref(plane), α.ctypes.data, β.ctypes.data, α.size,
+                                              out.ctypes.data, ctx_stats))
+            st = _lib.merge_stats(ctx_stats)
+        else:
+            st = _lib.gr_stats()
+            _lib.check(L.gr_plane_cells(ens.ctx.handle, C.byref(cfg), C.byref(plane), α.ctypes.data, β.ctypes.data, α.size, out.ctypes.data,
+                                        C.byref(st)))
+        keep["launches"].append((int(α.size), float(st.call_ms)))
+        return out
+
+    return calc_values, keep
+
+
+def AdaptivePlane(m, x, d, *, check_refine=None, α_lims=(-10, 10), β_lims=(-10, 10), ensemble=None, t_max=None, x_periodic=False,
+                  resident=False, **solver_opts):
+    """AdaptivePlane(m, x, d; check_refine = check_refine_plane, α_lims, β_lims, t_max = 2 x[1], solver_opts...)
+    (adaptive-plane.jl:60-91): an AdaptiveSky over an observer's impact parameters (α, β) whose rows are GeodesicPoints
+    (`sky.values` is a POINT_DTYPE array; row 0 a null point, NaN fields and NoStatus).  Cell (α, β) is the ray
+    map_impact_parameters(m, x, -α, β); every step's new cells are ONE gr_plane_cells launch (shared among the contexts of a
+    multi-device ensemble).  `resident=True` keeps the tree and the points on the device (gr_sky_create_plane; one context).
+    `x_periodic=False` is a deliberate deviation: the reference's AdaptiveGrid(α_lims..., β_lims...) inherits x_periodic = true
+    by accident and so pairs the left edge of an image with its right edge; `x_periodic=True` reproduces the reference's grid."""
+    from . import _lib
+
+    if resident and ensemble is not None and ensemble.multi:
+        raise ValueError("AdaptivePlane(resident=True) keeps the plane on ONE context: pass an ensemble of one device, "
+                         "or resident=False to share every step's cells among the contexts")
+    calc_values, tracer = _make_plane_tracer(m, x, d, ensemble=ensemble, t_max=t_max, **solver_opts)
+    sky = AdaptiveSky(calc_values, check_refine_plane if check_refine is None else check_refine,
+                      limits=(α_lims[0], α_lims[1], β_lims[0], β_lims[1]), x_periodic=x_periodic, null=make_null(1, _lib.POINT_DTYPE))
+    sky.tracer = tracer
+    if resident:
+        sky._make_resident()
+    return sky
+
+
 # ---- the drivers: adaptive-sample.jl:486-842 ----
 
 class AxisLimits:
@@ -791,6 +1056,7 @@ def evaluate_refinement_metric(m, d, sky, r_bins, ϕ_bins, split=6, metric=empty
     (r limits, ϕ limits, score) in the reference's order: the blocks that wrap around ϕ = 0 first, then ϕ by ϕ, r fastest.
     On a resident sky the default metric reads the device's census of the bins (gr_sky_occupancy), which is non-zero exactly
     where the map is; any other metric is given the map of the mirror."""
+    _corona_only(sky, "evaluate_refinement_metric")
     N = len(r_bins)
     if len(ϕ_bins) != N:
         raise ValueError("r_bins and ϕ_bins must have the same length")
@@ -823,6 +1089,7 @@ def step_block(m, d, sky, check_threshold=True, threshold=0.2, N=500, top=3, spl
     range(0, 2π), score the blocks, and refine -- to `percentage` per cent -- the pairs with a cell in one of the `top`
     lowest-scoring blocks (those below `threshold` if check_threshold).  StepBlockCodes.converged if no block is left,
     limit_exceeded (and nothing refined) if more than `limit` cells would be refined, else not_converged."""
+    _corona_only(sky, "step_block")
     r_bins = np.geomspace(m.isco(), 1000.0, N)
     ϕ_bins = np.linspace(0.0, TWO_PI, N)
     counts = evaluate_refinement_metric(m, d, sky, r_bins, ϕ_bins, split=split, metric=metric)
@@ -849,6 +1116,7 @@ def adaptive_solve(m, d, sky, verbose=True, limit=50, trace_calls=2, **step_bloc
     trace_calls plain steps, a pass over the far radii (r > 800 at 10 %) and one over the innermost (r_isco < r < 2 at 20 %), then
     step_block (split = 5, top = 4 unless given) until every block is covered or `limit` iterations are spent, then levels 4
     and 5.  Returns the number of refinement iterations."""
+    _corona_only(sky, "adaptive_solve")
     i = 0
     t0 = time.perf_counter()
 

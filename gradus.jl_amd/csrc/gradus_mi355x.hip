@@ -34,6 +34,7 @@
 #include "gr_tftd.hpp"
 #include "gr_ringarm.hpp"
 #include "gr_skygrid.hpp"
+#include "gr_planegrid.hpp"
 
 using namespace gr;
 
@@ -1939,6 +1940,77 @@ int32_t gr_sky_cells_device(gr_ctx* ctx, const gr_config* cfg, const gr_skycells
     cd.lp_pairs = d_out;
     p.stats = (unsigned long long*)d_stats;
     return launch_trace(ctx, p, cd, stream);
+}
+
+// ---- the cells of an observer's adaptive image plane (AdaptivePlane, adaptive-plane.jl:60-91): gr_plane_cells ----
+
+// Cell j is the ray of impact parameters (α_j, β_j): v = Mx local_momentum(x_obs[1], -α, β) (utility.jl:13-20; the sign of α:
+// adaptive-plane.jl:81) in the arithmetic of tracing.map_impact_parameters, unconstrained.  out: x_obs[4], v[n][4]
+struct PlaneCellParams {
+    double x_obs[4], Mx[16];
+    const double* alpha;       // device, n
+    const double* beta;        // device, n
+    int64_t n;
+};
+__global__ void __launch_bounds__(256) k_plane_velocities(const PlaneCellParams p, double* out)
+{
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.n; j += (int64_t)gridDim.x * 256) {
+        if (j == 0)
+            for (int q = 0; q < 4; ++q) out[q] = p.x_obs[q];
+        const double a = -p.alpha[j] / p.x_obs[1], b = p.beta[j] / p.x_obs[1];
+        const double pr = -1.0 / sqrt(1.0 + a * a + b * b);
+        const double pb[4] = { 1.0, pr, b * pr, a * pr };
+        double* v = out + 4 + 4 * j;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = p.Mx[q * 4 + 0] * pb[0] + p.Mx[q * 4 + 1] * pb[1] + p.Mx[q * 4 + 2] * pb[2] + p.Mx[q * 4 + 3] * pb[3];
+    }
+}
+
+// what every gr_plane_cells* and gr_sky_create_plane refuse before anything touches the device
+static int32_t planecells_check(const gr_config* cfg, const gr_plane* plane)
+{
+    int32_t rc;
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if (!plane) return fail(GR_ERR_INVALID_ARGUMENT, "gr_plane_cells: plane is null");
+    if (cfg->metric_id == GR_METRIC_TABULATED) {
+        const double r = plane->x_obs[1], t_min = cfg->metric_table[gr_tab::H_RMIN], t_max = cfg->metric_table[gr_tab::H_RMAX];
+        if (!(r >= t_min - 1e-9 * std::fabs(t_min) - 1e-12) || !(r <= t_max + 1e-9 * std::fabs(t_max)))
+            return fail(GR_ERR_INVALID_ARGUMENT, "gr_plane_cells: the observer at r = " + std::to_string(r) + " lies outside the radial range of the metric table ["
+                                                 + std::to_string(t_min) + ", " + std::to_string(t_max) + "]");
+    }
+    return GR_OK;
+}
+static int32_t planecells_args(const double* alpha, const double* beta, int64_t n, const gr_point* out)
+{
+    if (n < 0 || n > (int64_t)INT32_MAX) return fail(GR_ERR_INVALID_ARGUMENT, "gr_plane_cells: n in 0 ... 2^31 - 1");
+    if (n > 0 && (!alpha || !beta || !out)) return fail(GR_ERR_INVALID_ARGUMENT, "gr_plane_cells: alpha / beta / out is null");
+    return GR_OK;
+}
+
+int32_t gr_plane_cells_device(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const double* d_alpha, const double* d_beta, int64_t n,
+                              gr_point* d_out, gr_stats* d_stats, void* hip_stream)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc;
+    if ((rc = planecells_check(cfg, plane)) != GR_OK) return rc;
+    if ((rc = planecells_args(d_alpha, d_beta, n, d_out)) != GR_OK) return rc;
+    GR_HIP(hipSetDevice(ctx->device));
+    if (n == 0) return GR_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    // the rays go into the context's sky buffer (ordered against earlier launches that read it: sky_prepare)
+    if ((rc = tables_acquire(ctx, stream)) != GR_OK) return rc;
+    if ((rc = ensure((void**)&ctx->d_sky, &ctx->sky_bytes, sizeof(double) * (4 + 4 * (size_t)n))) != GR_OK) return rc;
+    PlaneCellParams pp;
+    std::memcpy(pp.x_obs, plane->x_obs, sizeof pp.x_obs);
+    std::memcpy(pp.Mx, plane->Mx, sizeof pp.Mx);
+    pp.alpha = d_alpha;
+    pp.beta = d_beta;
+    pp.n = n;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 2048));
+    hipLaunchKernelGGL(k_plane_velocities, dim3(blocks), dim3(256), 0, stream, pp, ctx->d_sky);
+    GR_HIP(hipGetLastError());
+    if ((rc = gr_trace_endpoints_device(ctx, cfg, ctx->d_sky, 0, ctx->d_sky + 4, n, d_out, d_stats, hip_stream)) != GR_OK) return rc;
+    return tables_release(ctx, stream);
 }
 
 int32_t gr_rayset_endpoints_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, gr_point* d_points,
@@ -4489,6 +4561,75 @@ int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg,
     return multi_drive(ctxs, n, stats, enq, copy);
 }
 
+// ---- gr_plane_cells: host buffers, as gr_sky_cells ----
+
+extern "C++" {
+namespace {
+// cells [off, off + cnt) of host (α, β) arrays -> the context's input buffer
+int32_t stage_planecells(gr_ctx* c, const double* alpha, const double* beta, int64_t off, int64_t cnt)
+{
+    int32_t rc;
+    if ((rc = ensure(&c->d_in, &c->in_bytes, sizeof(double) * 2 * (size_t)cnt + 64)) != GR_OK) return rc;
+    if ((rc = ensure(&c->d_scratch, &c->scratch_bytes, cnt ? sizeof(gr_point) * (size_t)cnt : 8)) != GR_OK) return rc;
+    double* b = (double*)c->d_in;
+    if (cnt > 0) {
+        GR_HIP(hipMemcpyAsync(b, alpha + off, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+        GR_HIP(hipMemcpyAsync(b + cnt, beta + off, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+    }
+    return GR_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t gr_plane_cells(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const double* alpha, const double* beta, int64_t n, gr_point* out,
+                       gr_stats* stats)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc;
+    if ((rc = planecells_check(cfg, plane)) != GR_OK) return rc;
+    if ((rc = planecells_args(alpha, beta, n, out)) != GR_OK) return rc;
+    GR_HIP(hipSetDevice(ctx->device));
+    if ((rc = stage_planecells(ctx, alpha, beta, 0, n)) != GR_OK) return rc;      // (its copies come before ev0: the staging is not timed)
+    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
+    const double* b = (const double*)ctx->d_in;
+    if ((rc = gr_plane_cells_device(ctx, cfg, plane, b, b + n, n, (gr_point*)ctx->d_scratch, stats ? (gr_stats*)ctx->d_stats : nullptr,
+                                    ctx->stream)) != GR_OK) return rc;
+    if (n) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, sizeof(gr_point) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return end_host_call(ctx, stats);
+}
+
+int32_t gr_plane_cells_multi(gr_ctx* const* ctxs, int32_t n_ctx, const gr_config* cfg, const gr_plane* plane, const double* alpha,
+                             const double* beta, int64_t n, gr_point* out, gr_stats* stats)
+{
+    int32_t rc;
+    if ((rc = validate_ctxs(ctxs, n_ctx)) != GR_OK) return rc;
+    if (n_ctx > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
+    if ((rc = planecells_check(cfg, plane)) != GR_OK) return rc;
+    if ((rc = planecells_args(alpha, beta, n, out)) != GR_OK) return rc;
+    auto enq = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        int64_t off, cnt;
+        contiguous_share(n, n_ctx, k, &off, &cnt);
+        int32_t r;
+        GR_HIP(hipSetDevice(c->device));
+        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;      // (before the staging, see rayset_rows_multi)
+        if ((r = stage_planecells(c, alpha, beta, off, cnt)) != GR_OK) return r;
+        if (cnt == 0) return GR_OK;
+        const double* b = (const double*)c->d_in;
+        return gr_plane_cells_device(c, cfg, plane, b, b + cnt, cnt, (gr_point*)c->d_scratch, stats ? (gr_stats*)c->d_stats : nullptr, c->stream);
+    };
+    auto copy = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        int64_t off, cnt;
+        contiguous_share(n, n_ctx, k, &off, &cnt);
+        if (cnt == 0) return GR_OK;
+        GR_HIP(hipSetDevice(c->device));
+        GR_HIP(hipMemcpyAsync(out + off, c->d_scratch, sizeof(gr_point) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        return GR_OK;
+    };
+    return multi_drive(ctxs, n_ctx, stats, enq, copy);
+}
+
 // ---- an adaptive sky resident on the device: gr_sky_* (AdaptiveSky, adaptive-sky.jl; the drivers of adaptive-sample.jl:486-842) ----
 // The tree (the arrays of grids.AdaptiveGrid) and the rows stay in device memory between refinement steps; the pair search,
 // the refinement and the census of the (r, ϕ) bins are the kernels below around the functions of gr_skygrid.hpp, and the new
@@ -4499,6 +4640,9 @@ struct gr_sky {
     gr_config cfg;
     gr_pointfunction pf;
     gr_skycells src;                       // x_src, Mx
+    gr_plane pl;                           // a plane sky's x_obs, Mx (gr_sky_create_plane)
+    bool plane = false;                    // the rows are gr_points, the cells traced by gr_plane_cells_device
+    int row = 6;                           // doubles per row: 6 (t, r, ϕ, g, J, status), or 19 (a gr_point)
     double lim[4] = { 0, 0, 0, 0 };
     int64_t n = 0, cap = 0;                // cells; rows the arrays below hold (cap >= n + 1)
     double* d_pos = nullptr;
@@ -4516,7 +4660,7 @@ struct gr_sky {
     void* d_need = nullptr;                // the list of the last find_need_refine / a host list
     size_t need_bytes = 0;
     int64_t need_n = -1;                   // -1: no list
-    void* d_ang = nullptr;                 // (cos θ, ϕ) of the cells of a launch, then their rows
+    void* d_ang = nullptr;                 // (cos θ, ϕ) -- a plane's (α, β) -- of the cells of a launch, then their rows
     size_t ang_bytes = 0;
     void* d_tmp = nullptr;                 // pairs, bin edges and counts, downloads
     size_t tmp_bytes = 0;
@@ -4657,6 +4801,19 @@ __global__ void __launch_bounds__(256) k_sky_mark_need(const gr_skygrid::Grid g,
     }
 }
 
+// ... on a plane sky: the rows are gr_points, the criterion is gr_planegrid::need_refine
+__global__ void __launch_bounds__(256) k_plane_mark_need(const gr_skygrid::Grid g, const gr_point* __restrict__ pts, const gr_sky_criterion cr,
+                                                         uint8_t* mark, int32_t* flag)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x + 1; c <= g.n; c += (int64_t)gridDim.x * 256) {
+        if (!gr_skygrid::is_leaf(g, c)) continue;
+        const int k = gr_skygrid::walk_bordering(g, c, [&](int64_t other) {
+            if (gr_planegrid::need_refine(cr, g, pts, c, other)) mark[other] = 1;
+        });
+        if (k < 0) *flag = 5;
+    }
+}
+
 // bordering_pairs: the count pass and the fill pass
 __global__ void __launch_bounds__(256) k_sky_pair_count(const gr_skygrid::Grid g, uint32_t* __restrict__ cnt, int32_t* flag)
 {
@@ -4700,7 +4857,9 @@ __global__ void __launch_bounds__(256) k_sky_refusals(const gr_skygrid::Grid g, 
 }
 
 // refine_many on the device: work-item 9 k + c writes child c of the k-th cell of the list into row first + 9 k + c; the middle
-// child takes its parent's row, the eight others leave (cos θ, ϕ) for the launch, in child order per parent
+// child takes its parent's row (ROW doubles: 6, or the 19 of a plane's whole gr_point), the eight others leave (cos θ, ϕ) for the
+// launch, in child order per parent
+template <int ROW>
 __global__ void __launch_bounds__(256) k_sky_children(const gr_skygrid::Grid g, const int64_t* __restrict__ list, int64_t m, double* rows,
                                                       double* __restrict__ cos_theta, double* __restrict__ phi)
 {
@@ -4710,7 +4869,7 @@ __global__ void __launch_bounds__(256) k_sky_children(const gr_skygrid::Grid g, 
         const int64_t cell = list[k], first = g.n + 1 + 9 * k, row = first + c;
         gr_skygrid::write_child(g, cell, first, c);
         if (c == 4) {
-            for (int q = 0; q < 6; ++q) rows[6 * row + q] = rows[6 * cell + q];
+            for (int q = 0; q < ROW; ++q) rows[ROW * row + q] = rows[ROW * cell + q];
         } else {
             const int64_t j = 8 * k + (c < 4 ? c : c - 1);
             cos_theta[j] = g.pos[2 * row];
@@ -4719,13 +4878,14 @@ __global__ void __launch_bounds__(256) k_sky_children(const gr_skygrid::Grid g, 
     }
 }
 // the rows of the launch into the children's slots
+template <int ROW>
 __global__ void __launch_bounds__(256) k_sky_scatter(const double* __restrict__ traced, int64_t m, int64_t first, double* __restrict__ rows)
 {
     for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < 8 * m; w += (int64_t)gridDim.x * 256) {
         const int64_t k = w / 8;
         const int j = (int)(w - 8 * k);
         const int64_t row = first + 9 * k + (j < 4 ? j : j + 1);
-        for (int q = 0; q < 6; ++q) rows[6 * row + q] = traced[6 * w + q];
+        for (int q = 0; q < ROW; ++q) rows[ROW * row + q] = traced[ROW * w + q];
     }
 }
 __global__ void __launch_bounds__(256) k_sky_positions(const double* __restrict__ pos, int64_t first, int64_t m, double* __restrict__ cos_theta,
@@ -4898,6 +5058,47 @@ __global__ void __launch_bounds__(256) k_sky_fill(const gr_skygrid::Grid g, cons
     }
 }
 
+// ---- the filled image of a plane sky: gr_sky_fill_plane (adaptive-plane.jl:100-181; the arithmetic is gr_planegrid.hpp).  Three
+// passes: the cell of every point (x_k, y_j), one work-item per point; the cells a column meets and their values interpolated
+// across α, one work-item per column (a serial walk over the column's cell indices: integer compares); every point between two
+// cells of its column, one work-item per point. ----
+__global__ void __launch_bounds__(256) k_plane_default_values(const gr_point* __restrict__ pts, int64_t n_rows, double* __restrict__ val)
+{
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < n_rows; c += (int64_t)gridDim.x * 256) val[c] = pts[c].x[0];
+}
+// idx[k n_y + j]: y ascends along j (gr_skygrid::theta_order)
+__global__ void __launch_bounds__(256) k_plane_fill_locate(const gr_skygrid::Grid g, const double* __restrict__ x, int64_t n_x,
+                                                           const double* __restrict__ y, int64_t n_y, int64_t* __restrict__ idx)
+{
+    for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < n_x * n_y; w += (int64_t)gridDim.x * 256) {
+        const int64_t k = w / n_y, j = w - k * n_y;
+        idx[w] = gr_skygrid::parent_index(g, x[k], y[j]);
+    }
+}
+__global__ void __launch_bounds__(256) k_plane_fill_columns(const gr_skygrid::Grid g, const gr_point* __restrict__ pts, const double* __restrict__ val,
+                                                            const double* __restrict__ x, int64_t n_x, int64_t n_y, const int64_t* __restrict__ idx,
+                                                            int64_t* __restrict__ comp, double* __restrict__ col, double* __restrict__ colval,
+                                                            int64_t* __restrict__ count)
+{
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n_x; k += (int64_t)gridDim.x * 256)
+        count[k] = gr_planegrid::build_column(g, pts, val, x[k], idx + k * n_y, n_y, comp + k * n_y, col + k * n_y, colval + k * n_y);
+}
+__global__ void __launch_bounds__(256) k_plane_fill(const double* __restrict__ y, int64_t n_x, int64_t n_y, const int64_t* __restrict__ perm,
+                                                    const int64_t* __restrict__ comp, const double* __restrict__ col,
+                                                    const double* __restrict__ colval, const int64_t* __restrict__ count, double* __restrict__ out,
+                                                    int64_t* __restrict__ cells_out)
+{
+    for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < n_x * n_y; w += (int64_t)gridDim.x * 256) {
+        const int64_t k = w / n_y, j = w - k * n_y;
+        const int64_t at = perm[j] * n_x + k;        // the point is the caller's perm[j]
+        const int64_t m = count[k];
+        int64_t lower = 0, upper = 0;
+        out[at] = m < 2 ? NAN : gr_planegrid::fill_point(col + k * n_y, colval + k * n_y, comp + k * n_y, m, y[j], lower, upper);
+        cells_out[2 * at] = lower;
+        cells_out[2 * at + 1] = upper;
+    }
+}
+
 // the cells refined since a download and their rows of `children`: every nine cells from `first` on share a parent
 __global__ void __launch_bounds__(256) k_sky_refined(const gr_skygrid::Grid g, int64_t first, int64_t groups, int64_t* __restrict__ refined,
                                                      int64_t* __restrict__ kids)
@@ -4947,7 +5148,7 @@ int32_t sky_reserve(gr_sky* s, int64_t cells)
     if ((rc = sky_grow(&s->d_neighbours, 4 * have, 4 * cap, st)) != GR_OK) return rc;
     if ((rc = sky_grow(&s->d_parent, have, cap, st)) != GR_OK) return rc;
     if ((rc = sky_grow(&s->d_location, have, cap, st)) != GR_OK) return rc;
-    if ((rc = sky_grow(&s->d_rows, 6 * have, 6 * cap, st)) != GR_OK) return rc;
+    if ((rc = sky_grow(&s->d_rows, (size_t)s->row * have, (size_t)s->row * cap, st)) != GR_OK) return rc;
     if ((rc = sky_fresh(&s->d_mark, cap)) != GR_OK) return rc;
     if ((rc = sky_fresh(&s->d_cnt, cap)) != GR_OK) return rc;
     if ((rc = sky_fresh(&s->d_off, cap + 1)) != GR_OK) return rc;
@@ -4974,6 +5175,9 @@ int32_t sky_launch_trace(gr_sky* s, int64_t m, gr_stats* stats)
 {
     gr_skycells cells = s->src;
     double* ang = (double*)s->d_ang;
+    if (s->plane)
+        return gr_plane_cells_device(s->ctx, &s->cfg, &s->pl, ang, ang + m, m, (gr_point*)(ang + 2 * m), stats ? (gr_stats*)s->ctx->d_stats : nullptr,
+                                     s->ctx->stream);
     cells.cos_theta = ang;
     cells.phi = ang + m;
     cells.n = m;
@@ -5004,10 +5208,12 @@ int32_t sky_refine_launch(gr_sky* s, int64_t m, int64_t* traced, gr_stats* stats
     }
     if ((rc = begin_host_call(s->ctx, stats)) != GR_OK) return rc;
     double* ang = (double*)s->d_ang;
-    hipLaunchKernelGGL(k_sky_children, dim3(sky_blocks(9 * m)), dim3(256), 0, st, g, list, m, s->d_rows, ang, ang + 8 * m);
+    if (s->plane) hipLaunchKernelGGL(k_sky_children<19>, dim3(sky_blocks(9 * m)), dim3(256), 0, st, g, list, m, s->d_rows, ang, ang + 8 * m);
+    else hipLaunchKernelGGL(k_sky_children<6>, dim3(sky_blocks(9 * m)), dim3(256), 0, st, g, list, m, s->d_rows, ang, ang + 8 * m);
     GR_HIP(hipGetLastError());
     if ((rc = sky_launch_trace(s, 8 * m, stats)) != GR_OK) return rc;
-    hipLaunchKernelGGL(k_sky_scatter, dim3(sky_blocks(8 * m)), dim3(256), 0, st, (const double*)(ang + 16 * m), m, s->n + 1, s->d_rows);
+    if (s->plane) hipLaunchKernelGGL(k_sky_scatter<19>, dim3(sky_blocks(8 * m)), dim3(256), 0, st, (const double*)(ang + 16 * m), m, s->n + 1, s->d_rows);
+    else hipLaunchKernelGGL(k_sky_scatter<6>, dim3(sky_blocks(8 * m)), dim3(256), 0, st, (const double*)(ang + 16 * m), m, s->n + 1, s->d_rows);
     GR_HIP(hipGetLastError());
     if ((rc = end_host_call(s->ctx, stats)) != GR_OK) return rc;
     s->n += 9 * m;
@@ -5023,7 +5229,7 @@ int32_t sky_refine_list(gr_sky* s, int64_t m, int64_t* traced, gr_stats* stats)
     if (m == 0) return GR_OK;
     int32_t rc;
     if ((rc = sky_reserve(s, s->n + 9 * m)) != GR_OK) return rc;
-    if ((rc = ensure(&s->d_ang, &s->ang_bytes, sizeof(double) * 8 * 8 * (size_t)m)) != GR_OK) return rc;
+    if ((rc = ensure(&s->d_ang, &s->ang_bytes, sizeof(double) * (size_t)(2 + s->row) * 8 * (size_t)m)) != GR_OK) return rc;
     return sky_refine_launch(s, m, traced, stats);
 }
 
@@ -5053,6 +5259,65 @@ static void sky_drop_ctx(gr_ctx* c)
 }
 }  // extern "C"
 
+// what gr_sky_create and gr_sky_create_plane share: the limits, room for the nine top cells, the cells themselves and null rows
+// (NaN; a plane's: NoStatus points with NaN fields).  `s` is freed on failure.
+static int32_t sky_create_common(gr_ctx* ctx, gr_sky* s, const double* limits, int32_t x_periodic, gr_sky** sky)
+{
+    int32_t rc;
+    s->ctx = ctx;
+    s->lim[0] = std::min(limits[0], limits[1]);
+    s->lim[1] = std::max(limits[0], limits[1]);
+    s->lim[2] = std::min(limits[2], limits[3]);
+    s->lim[3] = std::max(limits[2], limits[3]);
+    if ((rc = sky_reserve(s, 9)) != GR_OK) {
+        sky_free(s);
+        return rc;
+    }
+    // the nine top cells, formed here as AdaptiveGrid.__init__ forms them
+    double pos[20];
+    int32_t level[10];
+    int64_t children[90], neighbours[40], parent[10];
+    int8_t location[10];
+    double rows[190];
+    gr_skygrid::Grid g = sky_grid(s);
+    g.pos = pos;
+    g.level = level;
+    g.children = children;
+    g.neighbours = neighbours;
+    g.parent = parent;
+    g.location = location;
+    gr_skygrid::top_cells(g, x_periodic != 0);
+    for (double& v : rows) v = NAN;
+    if (s->plane)
+        for (int i = 0; i < 10; ++i) {
+            gr_point null_point;
+            std::memcpy(&null_point, rows + 19 * i, sizeof null_point);
+            null_point.status = GR_STATUS_NO_STATUS;
+            null_point.flags = 0;
+            std::memcpy(rows + 19 * i, &null_point, sizeof null_point);
+        }
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMemcpyAsync(s->d_pos, pos, sizeof pos, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_level, level, sizeof level, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_children, children, sizeof children, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_neighbours, neighbours, sizeof neighbours, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_parent, parent, sizeof parent, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_location, location, sizeof location, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_rows, rows, sizeof(double) * (size_t)s->row * 10, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        sky_free(s);
+        return fail(GR_ERR_HIP, std::string("gr_sky_create: ") + hipGetErrorString(e));
+    }
+    s->n = 9;
+    {
+        std::lock_guard<std::mutex> lock(g_sky_mutex);
+        g_skies.push_back(s);
+    }
+    *sky = s;
+    return GR_OK;
+}
+
 int32_t gr_sky_create(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* source, const gr_pointfunction* pf, const double* limits,
                       int32_t x_periodic, gr_sky** sky)
 {
@@ -5072,53 +5337,31 @@ int32_t gr_sky_create(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* sour
     GR_HIP(hipSetDevice(ctx->device));
     gr_sky* s = new (std::nothrow) gr_sky;
     if (!s) return fail(GR_ERR_OUT_OF_MEMORY, "gr_sky_create: out of memory");
-    s->ctx = ctx;
     s->cfg = *cfg;
     s->pf = *pf;
     s->src = none;
-    s->lim[0] = std::min(limits[0], limits[1]);
-    s->lim[1] = std::max(limits[0], limits[1]);
-    s->lim[2] = std::min(limits[2], limits[3]);
-    s->lim[3] = std::max(limits[2], limits[3]);
-    if ((rc = sky_reserve(s, 9)) != GR_OK) {
-        sky_free(s);
-        return rc;
-    }
-    // the nine top cells, formed here as AdaptiveGrid.__init__ forms them
-    double pos[20];
-    int32_t level[10];
-    int64_t children[90], neighbours[40], parent[10];
-    int8_t location[10];
-    double rows[60];
-    gr_skygrid::Grid g = sky_grid(s);
-    g.pos = pos;
-    g.level = level;
-    g.children = children;
-    g.neighbours = neighbours;
-    g.parent = parent;
-    g.location = location;
-    gr_skygrid::top_cells(g, x_periodic != 0);
-    for (double& v : rows) v = NAN;
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMemcpyAsync(s->d_pos, pos, sizeof pos, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_level, level, sizeof level, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_children, children, sizeof children, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_neighbours, neighbours, sizeof neighbours, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_parent, parent, sizeof parent, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_location, location, sizeof location, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_rows, rows, sizeof rows, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        sky_free(s);
-        return fail(GR_ERR_HIP, std::string("gr_sky_create: ") + hipGetErrorString(e));
-    }
-    s->n = 9;
-    {
-        std::lock_guard<std::mutex> lock(g_sky_mutex);
-        g_skies.push_back(s);
-    }
-    *sky = s;
-    return GR_OK;
+    return sky_create_common(ctx, s, limits, x_periodic, sky);
+}
+
+int32_t gr_sky_create_plane(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const double* limits, int32_t x_periodic, gr_sky** sky)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!sky || !limits) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_create_plane: sky / limits is null");
+    *sky = nullptr;
+    int32_t rc;
+    if ((rc = planecells_check(cfg, plane)) != GR_OK) return rc;
+    for (int q = 0; q < 4; ++q)
+        if (!std::isfinite(limits[q])) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_create_plane: the limits must be finite");
+    GR_HIP(hipSetDevice(ctx->device));
+    gr_sky* s = new (std::nothrow) gr_sky;
+    if (!s) return fail(GR_ERR_OUT_OF_MEMORY, "gr_sky_create_plane: out of memory");
+    s->cfg = *cfg;
+    std::memset(&s->pf, 0, sizeof s->pf);
+    std::memset(&s->src, 0, sizeof s->src);
+    s->pl = *plane;
+    s->plane = true;
+    s->row = 19;
+    return sky_create_common(ctx, s, limits, x_periodic, sky);
 }
 
 int32_t gr_sky_destroy(gr_sky* sky)
@@ -5148,12 +5391,12 @@ int32_t gr_sky_trace_initial(gr_sky* sky, int32_t level, int64_t* launch_sizes)
     if (sky->traced || sky->n != 9) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_trace_initial: the sky has been traced already");
     if (level < 1 || level > GR_SKY_MAX_LEVEL) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_trace_initial: level in 1 ... 20");
     hipStream_t st = sky->ctx->stream;
-    if ((rc = ensure(&sky->d_ang, &sky->ang_bytes, sizeof(double) * 8 * 9)) != GR_OK) return rc;
+    if ((rc = ensure(&sky->d_ang, &sky->ang_bytes, sizeof(double) * (size_t)(2 + sky->row) * 9)) != GR_OK) return rc;
     double* ang = (double*)sky->d_ang;
     hipLaunchKernelGGL(k_sky_positions, dim3(1), dim3(256), 0, st, (const double*)sky->d_pos, (int64_t)1, (int64_t)9, ang, ang + 9);
     GR_HIP(hipGetLastError());
     if ((rc = sky_launch_trace(sky, 9, nullptr)) != GR_OK) return rc;
-    GR_HIP(hipMemcpyAsync(sky->d_rows + 6, ang + 18, sizeof(double) * 6 * 9, hipMemcpyDeviceToDevice, st));
+    GR_HIP(hipMemcpyAsync(sky->d_rows + sky->row, ang + 18, sizeof(double) * (size_t)sky->row * 9, hipMemcpyDeviceToDevice, st));
     GR_HIP(hipStreamSynchronize(st));
     sky->traced = true;
     if (launch_sizes) launch_sizes[0] = 9;
@@ -5182,8 +5425,12 @@ int32_t gr_sky_find_need_refine(gr_sky* sky, const gr_sky_criterion* criterion, 
     int32_t rc;
     if ((rc = sky_check(sky)) != GR_OK) return rc;
     if (!criterion || !count) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: criterion / count is null");
-    if (criterion->kind < GR_SKY_CRIT_DEFAULT || criterion->kind > GR_SKY_CRIT_LEVEL)
+    if (criterion->kind < GR_SKY_CRIT_DEFAULT || criterion->kind > GR_SKY_CRIT_PLANE)
         return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: unknown criterion kind");
+    if (sky->plane && criterion->kind != GR_SKY_CRIT_PLANE && criterion->kind != GR_SKY_CRIT_LEVEL)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: a plane sky's criteria are GR_SKY_CRIT_PLANE and GR_SKY_CRIT_LEVEL (the others read corona rows)");
+    if (!sky->plane && criterion->kind == GR_SKY_CRIT_PLANE)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: GR_SKY_CRIT_PLANE reads the points of a plane sky (gr_sky_create_plane)");
     if (criterion->n_boxes < 0 || criterion->n_boxes > GR_SKY_MAX_BOXES)
         return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_find_need_refine: n_boxes in 0 ... 8");
     for (int k = 0; k < criterion->n_boxes; ++k)
@@ -5196,8 +5443,12 @@ int32_t gr_sky_find_need_refine(gr_sky* sky, const gr_sky_criterion* criterion, 
     if ((rc = ensure(&sky->d_need, &sky->need_bytes, sizeof(int64_t) * (size_t)n_rows)) != GR_OK) return rc;
     GR_HIP(hipMemsetAsync(sky->d_mark, 0, (size_t)n_rows, st));
     GR_HIP(hipMemsetAsync(sky_flag(sky), 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_sky_mark_need, dim3(sky_blocks(sky->n)), dim3(256), 0, st, sky_grid(sky), (const double*)sky->d_rows, *criterion, sky->d_mark,
-                       sky_flag(sky));
+    if (sky->plane)
+        hipLaunchKernelGGL(k_plane_mark_need, dim3(sky_blocks(sky->n)), dim3(256), 0, st, sky_grid(sky), (const gr_point*)sky->d_rows, *criterion,
+                           sky->d_mark, sky_flag(sky));
+    else
+        hipLaunchKernelGGL(k_sky_mark_need, dim3(sky_blocks(sky->n)), dim3(256), 0, st, sky_grid(sky), (const double*)sky->d_rows, *criterion, sky->d_mark,
+                           sky_flag(sky));
     GR_HIP(hipGetLastError());
     int32_t why = 0;
     GR_HIP(hipMemcpyAsync(&why, sky_flag(sky), sizeof why, hipMemcpyDeviceToHost, st));
@@ -5279,6 +5530,7 @@ int32_t gr_sky_occupancy(gr_sky* sky, const double* r_bins, int64_t n_r, const d
 {
     int32_t rc;
     if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (sky && sky->plane) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_occupancy: a plane sky has no (r, ϕ) rows");
     if (!r_bins || !phi_bins || !counts || n_r < 1 || n_phi < 1 || n_r > 46340 || n_phi > 46340)
         return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_occupancy: r_bins / phi_bins / counts is null, or a count outside 1 ... 46340");
     hipStream_t st = sky->ctx->stream;
@@ -5312,6 +5564,7 @@ int32_t gr_sky_bin_grid(gr_sky* sky, int32_t what, const double* r_bins, int64_t
 {
     // refusals first: nothing has touched the device when one is found
     if (!sky) return fail(GR_ERR_INVALID_ARGUMENT, "sky is null");
+    if (sky->plane) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_bin_grid: a plane sky has no (r, ϕ) rows");
     if (!r_bins || !phi_bins || !out || n_r < 1 || n_phi < 1 || n_r > 46340 || n_phi > 46340)
         return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_bin_grid: r_bins / phi_bins / out is null, or a count outside 1 ... 46340");
     if (what < GR_SKY_MAP_EMISSIVITY || what > GR_SKY_MAP_TIME) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_bin_grid: unknown map (GR_SKY_MAP_*)");
@@ -5394,6 +5647,7 @@ int32_t gr_sky_bin_grid(gr_sky* sky, int32_t what, const double* r_bins, int64_t
 int32_t gr_sky_fill(gr_sky* sky, const double* phi_grid, int64_t n_phi, const double* theta_grid, int64_t n_theta, double* out, int64_t* cells)
 {
     if (!sky) return fail(GR_ERR_INVALID_ARGUMENT, "sky is null");
+    if (sky->plane) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill: a plane sky is filled by gr_sky_fill_plane");
     if (!phi_grid || !theta_grid || !out || n_phi < 1 || n_theta < 1 || n_phi > 46340 || n_theta > 46340)
         return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill: phi_grid / theta_grid / out is null, or a count outside 1 ... 46340");
     if (!sky->traced) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill: the sky has not been traced (gr_sky_trace_initial comes first)");
@@ -5452,6 +5706,7 @@ int32_t gr_sky_download(gr_sky* sky, int64_t first_cell, int64_t count, double* 
     if ((rc = sky_check(sky)) != GR_OK) return rc;
     if (first_cell < 0 || count < 0 || first_cell + count > sky->n + 1)
         return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_download: cells first_cell ... first_cell + count - 1 must lie in 0 ... n_cells");
+    if (rows && sky->plane) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_download: the rows of a plane sky are gr_points: gr_sky_download_points");
     if (count == 0) return GR_OK;
     hipStream_t st = sky->ctx->stream;
     const size_t f = (size_t)first_cell, c = (size_t)count;
@@ -5474,6 +5729,85 @@ int32_t gr_sky_download(gr_sky* sky, int64_t first_cell, int64_t count, double* 
         GR_HIP(hipMemcpyAsync(refined, d_ref, sizeof(int64_t) * (size_t)groups, hipMemcpyDeviceToHost, st));
         GR_HIP(hipMemcpyAsync(refined_children, d_ref + groups, sizeof(int64_t) * 9 * (size_t)groups, hipMemcpyDeviceToHost, st));
     }
+    GR_HIP(hipStreamSynchronize(st));
+    return GR_OK;
+}
+
+int32_t gr_sky_download_points(gr_sky* sky, int64_t first_cell, int64_t count, gr_point* out)
+{
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    if (!sky->plane) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_download_points: the rows of a corona sky are six doubles: gr_sky_download");
+    if (first_cell < 0 || count < 0 || first_cell + count > sky->n + 1)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_download_points: cells first_cell ... first_cell + count - 1 must lie in 0 ... n_cells");
+    if (count == 0) return GR_OK;
+    if (!out) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_download_points: out is null");
+    hipStream_t st = sky->ctx->stream;
+    GR_HIP(hipMemcpyAsync(out, (const gr_point*)sky->d_rows + first_cell, sizeof(gr_point) * (size_t)count, hipMemcpyDeviceToHost, st));
+    GR_HIP(hipStreamSynchronize(st));
+    return GR_OK;
+}
+
+int32_t gr_sky_fill_plane(gr_sky* sky, const gr_pointfunction* pf, const double* cell_values, const double* x_grid, int64_t n_x, const double* y_grid,
+                          int64_t n_y, double* out, int64_t* cells)
+{
+    if (!sky) return fail(GR_ERR_INVALID_ARGUMENT, "sky is null");
+    if (!sky->plane) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill_plane: a corona sky is filled by gr_sky_fill");
+    if (!x_grid || !y_grid || !out || n_x < 1 || n_y < 1 || n_x > 46340 || n_y > 46340)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill_plane: x_grid / y_grid / out is null, or a count outside 1 ... 46340");
+    if (pf && cell_values) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill_plane: pf or cell_values, not both");
+    if (!sky->traced) return fail(GR_ERR_INVALID_ARGUMENT, "gr_sky_fill_plane: the sky has not been traced (gr_sky_trace_initial comes first)");
+    int32_t rc;
+    if ((rc = sky_check(sky)) != GR_OK) return rc;
+    hipStream_t st = sky->ctx->stream;
+    const size_t points = (size_t)n_y * (size_t)n_x, n_rows = (size_t)sky->n + 1;
+    std::vector<double> grids;
+    std::vector<int64_t> perm;
+    try {
+        grids.resize((size_t)n_x + (size_t)n_y);
+        perm.resize((size_t)n_y);
+    } catch (...) {
+        return fail(GR_ERR_OUT_OF_MEMORY, "gr_sky_fill_plane: out of memory");
+    }
+    gr_skygrid::theta_order(y_grid, n_y, perm.data());
+    std::memcpy(grids.data(), x_grid, sizeof(double) * (size_t)n_x);
+    for (int64_t j = 0; j < n_y; ++j) grids[(size_t)(n_x + j)] = y_grid[perm[(size_t)j]];
+    // x | y ascending | the values of the cells | out | column y | column values | the caller's index of every y | cells of the points |
+    // compacted cells | cells out | cells per column
+    const size_t bytes = sizeof(double) * (grids.size() + n_rows + 3 * points) + sizeof(int64_t) * (perm.size() + 4 * points + (size_t)n_x) + 16;
+    if ((rc = ensure(&sky->d_tmp, &sky->tmp_bytes, bytes)) != GR_OK) return rc;
+    double* d_x = (double*)sky->d_tmp;
+    double* d_y = d_x + n_x;
+    double* d_val = d_y + n_y;
+    double* d_out = d_val + n_rows;
+    double* d_col = d_out + points;
+    double* d_colval = d_col + points;
+    int64_t* d_perm = (int64_t*)(d_colval + points);
+    int64_t* d_idx = d_perm + n_y;
+    int64_t* d_comp = d_idx + points;
+    int64_t* d_cells = d_comp + points;
+    int64_t* d_count = d_cells + 2 * points;
+    const gr_point* pts = (const gr_point*)sky->d_rows;
+    const gr_skygrid::Grid g = sky_grid(sky);
+    GR_HIP(hipMemcpyAsync(d_x, grids.data(), sizeof(double) * grids.size(), hipMemcpyHostToDevice, st));
+    GR_HIP(hipMemcpyAsync(d_perm, perm.data(), sizeof(int64_t) * perm.size(), hipMemcpyHostToDevice, st));
+    if (cell_values) {
+        GR_HIP(hipMemcpyAsync(d_val, cell_values, sizeof(double) * n_rows, hipMemcpyHostToDevice, st));
+    } else if (pf) {
+        // cells 1 ... n; the null cell's value is never read (a cell or a neighbour 0 is no cell)
+        GR_HIP(hipMemsetAsync(d_val, 0xFF, sizeof(double), st));
+        if ((rc = gr_apply_pointfunction_device(sky->ctx, &sky->cfg, pf, pts + 1, sky->n, sky->cfg.lambda1, d_val + 1, st)) != GR_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(k_plane_default_values, dim3(sky_blocks((int64_t)n_rows)), dim3(256), 0, st, pts, (int64_t)n_rows, d_val);
+    }
+    hipLaunchKernelGGL(k_plane_fill_locate, dim3(sky_blocks((int64_t)points)), dim3(256), 0, st, g, (const double*)d_x, n_x, (const double*)d_y, n_y, d_idx);
+    hipLaunchKernelGGL(k_plane_fill_columns, dim3(sky_blocks(n_x)), dim3(256), 0, st, g, pts, (const double*)d_val, (const double*)d_x, n_x, n_y,
+                       (const int64_t*)d_idx, d_comp, d_col, d_colval, d_count);
+    hipLaunchKernelGGL(k_plane_fill, dim3(sky_blocks((int64_t)points)), dim3(256), 0, st, (const double*)d_y, n_x, n_y, (const int64_t*)d_perm,
+                       (const int64_t*)d_comp, (const double*)d_col, (const double*)d_colval, (const int64_t*)d_count, d_out, d_cells);
+    GR_HIP(hipGetLastError());
+    GR_HIP(hipMemcpyAsync(out, d_out, sizeof(double) * points, hipMemcpyDeviceToHost, st));
+    if (cells) GR_HIP(hipMemcpyAsync(cells, d_cells, sizeof(int64_t) * 2 * points, hipMemcpyDeviceToHost, st));
     GR_HIP(hipStreamSynchronize(st));
     return GR_OK;
 }

@@ -782,7 +782,8 @@ int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg,
  * leaf's level is below `level`.  A box is an r interval and zero, one or two intervals of fmod(ϕ, 2π) (+ 2π where negative),
  * every bound open or closed. */
 #define GR_SKY_MAX_BOXES 8
-enum { GR_SKY_CRIT_DEFAULT = 0, GR_SKY_CRIT_FUNCTION = 1, GR_SKY_CRIT_FINE = 2, GR_SKY_CRIT_LEVEL = 3 };
+enum { GR_SKY_CRIT_DEFAULT = 0, GR_SKY_CRIT_FUNCTION = 1, GR_SKY_CRIT_FINE = 2, GR_SKY_CRIT_LEVEL = 3,
+       GR_SKY_CRIT_PLANE = 4 /* a plane sky's (gr_sky_create_plane, below) */ };
 typedef struct gr_sky_box {
     double r_lo, r_hi;
     double phi_lo[2], phi_hi[2];
@@ -865,6 +866,42 @@ int32_t gr_sky_bin_grid(gr_sky* sky, int32_t what, const double* r_bins, int64_t
  * rectangles does that). */
 int32_t gr_sky_fill(gr_sky* sky, const double* phi_grid, int64_t n_phi, const double* theta_grid, int64_t n_theta,
                     double* out /* host, n_theta x n_phi x 6 */, int64_t* cells /* host, n_theta x n_phi x 2, or NULL */);
+
+/* ---- an observer's adaptive image plane (added within ABI 8; AdaptivePlane, src/image-planes/adaptive-plane.jl) ----
+ * Cell j is the ray of impact parameters (alpha[j], beta[j]) of an observer at plane->x_obs: the unconstrained velocity
+ * v = Mx local_momentum(x_obs[1], -alpha, beta) (the sign of alpha: adaptive-plane.jl:81) is formed on the device and traced to its
+ * end point, one gr_point per cell.  Of `plane` only x_obs and Mx are read.  cfg->disc_id may be GR_DISC_NONE.
+ * GR_ERR_INVALID_ARGUMENT, before anything touches the device, for a null pointer and for an observer outside the radial range
+ * of a GR_METRIC_TABULATED table.  gr_plane_cells_device: alpha, beta and the points are device memory, nothing is waited for.
+ * gr_plane_cells_multi: contiguous shares of the cells, one per context, the points of one context bit for bit. */
+int32_t gr_plane_cells(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane /* x_obs, Mx */, const double* alpha /* host, n */,
+                       const double* beta /* host, n */, int64_t n, gr_point* out /* host, n */, gr_stats* stats);
+int32_t gr_plane_cells_device(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const double* d_alpha, const double* d_beta,
+                              int64_t n, gr_point* d_out, gr_stats* d_stats, void* hip_stream);
+int32_t gr_plane_cells_multi(gr_ctx* const* ctxs, int32_t n_ctx, const gr_config* cfg, const gr_plane* plane, const double* alpha,
+                             const double* beta, int64_t n, gr_point* out /* host, n */, gr_stats* stats /* n_ctx, or NULL */);
+/* A gr_sky over (alpha, beta) whose rows are gr_point records -- row 0 a NoStatus one with NaN fields: the tree of gr_sky_create with every new
+ * cell traced by gr_plane_cells_device; the middle child of a refined cell inherits its parent's whole point.  gr_sky_size,
+ * gr_sky_trace_initial, gr_sky_find_need_refine, gr_sky_need_refine_list, gr_sky_pairs, gr_sky_refine_and_trace, gr_sky_destroy
+ * and the tree arrays of gr_sky_download work on it as on a corona sky.  Its criteria are GR_SKY_CRIT_PLANE (adaptive-plane.jl:24-50:
+ * with "hit" = status IntersectedWithGeometry, a pair that both miss is left alone, a pair of which one hits is refined, a pair
+ * that both hit is refined if log10 x[1] or fmod(x[2], 2π) (+ 2π where negative) of the two points are not isapprox at rtol) and
+ * GR_SKY_CRIT_LEVEL (a pair that both miss is left alone).  GR_ERR_INVALID_ARGUMENT, with the sky untouched, for the corona kinds
+ * DEFAULT / FUNCTION / FINE on a plane sky, for GR_SKY_CRIT_PLANE on a corona sky, for gr_sky_occupancy, gr_sky_bin_grid,
+ * gr_sky_fill and the `rows` of gr_sky_download on a plane sky, and for the two calls below on a corona sky. */
+int32_t gr_sky_create_plane(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane /* x_obs, Mx */, const double* limits /* 4 */,
+                            int32_t x_periodic, gr_sky** sky);
+int32_t gr_sky_download_points(gr_sky* sky, int64_t first_cell, int64_t count, gr_point* out /* host, count */);
+/* fill_sky_values of a plane (adaptive-plane.jl:100-181) from one value per cell: pf evaluated on the resident points
+ * (gr_apply_pointfunction_device, max_time = cfg->lambda1), or cell_values, or -- both NULL -- x[0] of every point (the
+ * reference's default pf).  Per column x_k the y grid is walked ascending and every run of points held by one cell c is recorded;
+ * c's value is interpolated in x with its left (x_k < pos_x(c)) or right neighbour unless there is none, it lies across the
+ * periodic wrap or its ray did not hit; the column's abscissae are pos_y(c); every point takes the interval
+ * clamp(searchsortedlast(column, y), 1, cells - 1) and interpolates linearly in y.  out[j * n_x + k] belongs to (x_k, y_j); a
+ * column with fewer than two cells is NaN (cells 0, 0).  The y grid may come in any order.  Refused as gr_sky_fill refuses. */
+int32_t gr_sky_fill_plane(gr_sky* sky, const gr_pointfunction* pf /* or NULL */, const double* cell_values /* host, n_cells + 1, or NULL */,
+                          const double* x_grid, int64_t n_x, const double* y_grid, int64_t n_y, double* out /* host, n_y x n_x */,
+                          int64_t* cells /* host, n_y x n_x x 2, or NULL */);
 
 /* ---- tabulated metrics (ABI 7; segments, axis terms: ABI 8; GR_METRIC_TABULATED): the AbstractMetric plugin interface on the device ----
  * Host-only functions (no context, no device): plan a grid, learn its nodes, fit, check.
