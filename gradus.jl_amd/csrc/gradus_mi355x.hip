@@ -879,9 +879,10 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
 {
     Cold cold = cold_in;
     cold.winding_plane = p.cfg.winding_plane;
-    if (p.cfg.metric_id == GR_METRIC_TABULATED && cold_in.src_mode != 1) {
+    if (p.cfg.metric_id == GR_METRIC_TABULATED && cold_in.src_mode != 1 && !(cold_in.src_mode == 3 && ctx->sky_rows)) {
         // (validate_cfg has compared the chart with the table's range; p.cfg.metric_table is still the caller's host table here.)
-        // The observer / source position the rays start from must lie inside the table as well.
+        // The observer / source position the rays start from must lie inside the table as well.  (A sky source with sky_rows has no
+        // such position -- x_obs is not read: the host-pointer entry points have checked every row's radius, sky_rows_in_table.)
         const double r_obs = cold_in.plane.x_obs[1], t_min = p.cfg.metric_table[gr_tab::H_RMIN], t_max = p.cfg.metric_table[gr_tab::H_RMAX];
         if (!(r_obs >= t_min - 1e-9 * std::fabs(t_min) - 1e-12) || !(r_obs <= t_max + 1e-9 * std::fabs(t_max)))
             return fail(GR_ERR_INVALID_ARGUMENT, "GR_METRIC_TABULATED: the rays start at r = " + std::to_string(r_obs) + ", outside the radial range of the "
@@ -1695,6 +1696,40 @@ int32_t gr_trace_path(gr_ctx* ctx, const gr_config* cfg, const double* x, const 
     return gr_trace_paths(ctx, cfg, x, 0, v, 1, cap, path, n_rows, endpoint);
 }
 
+// A source without one position (gr_rayset.sky_rows) brings a source velocity per sample: only gr_ray_summary / gr_corona_trace scale a
+// row's g with its sample's factor (k_sky_scale_g).  The line profile, the (g, ρ) pairs and the ray tangents would return g against
+// the static observer instead: they refuse such a set, before anything of it is staged.
+static int32_t refuse_sky_rows(const gr_rayset* rays, const char* who)
+{
+    if (rays && rays->sky_sampler && rays->sky_rows)
+        return fail(GR_ERR_INVALID_ARGUMENT, std::string(who) + ": a sky source with sky_rows (a source velocity per sample) is traced by gr_ray_summary / "
+                                             "gr_corona_trace, the only calls that form g against each sample's own velocity");
+    return GR_OK;
+}
+
+// GR_METRIC_TABULATED under a source without one position: EVERY sample's start radius (sky_rows[28 j + 1], host memory here) must lie
+// inside the table's radial range, with the slack of launch_trace's guard on x_obs -- which is not read for such a set.
+static int32_t sky_rows_in_table(const gr_config* cfg, const gr_rayset* rays)
+{
+    if (!cfg || cfg->metric_id != GR_METRIC_TABULATED || !rays || !rays->sky_sampler || !rays->sky_rows || rays->n <= 0) return GR_OK;
+    const int32_t trc = gr_metric_table_check(cfg->metric_table, cfg->metric_table_n);
+    if (trc != GR_OK) return trc;
+    const double t_min = cfg->metric_table[gr_tab::H_RMIN], t_max = cfg->metric_table[gr_tab::H_RMAX];
+    double lo = INFINITY, hi = -INFINITY;
+    bool nan = false;
+    for (int64_t j = 0; j < rays->n; ++j) {
+        const double r = rays->sky_rows[GR_SKY_ROW * j + 1];
+        nan = nan || !(r == r);
+        lo = std::fmin(lo, r);
+        hi = std::fmax(hi, r);
+    }
+    const bool below = !(lo >= t_min - 1e-9 * std::fabs(t_min) - 1e-12), above = !(hi <= t_max + 1e-9 * std::fabs(t_max));
+    if (nan || below || above)
+        return fail(GR_ERR_INVALID_ARGUMENT, "GR_METRIC_TABULATED: a sample of the sky source starts at r = " + (nan ? std::string("nan") : std::to_string(below ? lo : hi))
+                                             + ", outside the radial range of the metric table [" + std::to_string(t_min) + ", " + std::to_string(t_max) + "]");
+    return GR_OK;
+}
+
 static int32_t rays_params(gr_ctx* ctx, Params& p, Cold& cd, const gr_config* cfg, const gr_rayset* rays)
 {
     if (!rays) return fail(GR_ERR_INVALID_ARGUMENT, "rayset is null");
@@ -1773,6 +1808,7 @@ int32_t gr_lineprofile_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset
 {
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     int32_t rc;
+    if ((rc = refuse_sky_rows(rays, "gr_lineprofile_device")) != GR_OK) return rc;
     if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
     if (!b || b->n_bins < 1 || !b->bin_edges || !d_flux) return fail(GR_ERR_INVALID_ARGUMENT, "binning/flux is null or empty");
     if (!(b->r_max >= b->r_min)) return fail(GR_ERR_INVALID_ARGUMENT, "maxrₑ below minrₑ");
@@ -1801,6 +1837,7 @@ int32_t gr_redshift_radius_device(gr_ctx* ctx, const gr_config* cfg, const gr_ra
 {
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     int32_t rc;
+    if ((rc = refuse_sky_rows(rays, "gr_redshift_radius_device")) != GR_OK) return rc;
     if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
     GR_HIP(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -1853,6 +1890,7 @@ int32_t gr_ray_tangent_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset
 {
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     int32_t rc;
+    if ((rc = refuse_sky_rows(rays, "gr_ray_tangent_device")) != GR_OK) return rc;
     if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
     if (cfg->disc_id == GR_DISC_NONE) return fail(GR_ERR_INVALID_ARGUMENT, "ray tangents are taken where the ray meets the geometry: none given");
     GR_HIP(hipSetDevice(ctx->device));
@@ -2643,6 +2681,7 @@ int32_t gr_lineprofile(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays,
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!b || b->n_bins < 1 || !b->bin_edges || !flux) return fail(GR_ERR_INVALID_ARGUMENT, "binning/flux is null or empty");
     int32_t rc;
+    if ((rc = refuse_sky_rows(rays, "gr_lineprofile")) != GR_OK) return rc;
     GR_HIP(hipSetDevice(ctx->device));
     gr_rayset dev;
     void* extra = nullptr;
@@ -2673,6 +2712,7 @@ int32_t gr_redshift_radius(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* r
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     if (rays && rays->n > 0 && !pairs) return fail(GR_ERR_INVALID_ARGUMENT, "pairs is null");
     int32_t rc;
+    if ((rc = refuse_sky_rows(rays, "gr_redshift_radius")) != GR_OK) return rc;
     GR_HIP(hipSetDevice(ctx->device));
     gr_rayset dev;
     if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
@@ -2691,6 +2731,7 @@ int32_t gr_ray_summary(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays,
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     if (rays && rays->n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
     int32_t rc;
+    if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
     GR_HIP(hipSetDevice(ctx->device));
     gr_rayset dev;
     if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
@@ -3248,6 +3289,7 @@ int32_t gr_corona_trace(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays
     if (cfg && cfg->disc_id == GR_DISC_NONE) return fail(GR_ERR_INVALID_ARGUMENT, "a corona illuminates accretion geometry: none given");
     int32_t rc;
     ctx->corona_n = -1;
+    if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
     unsigned long long h[5];
     double v[5];
     if ((rc = corona_enqueue(ctx, cfg, rays, pf, stats, h)) != GR_OK) return rc;
@@ -3267,6 +3309,7 @@ int32_t gr_corona_trace_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* c
     if (!rho_min_max || !n_hits) return fail(GR_ERR_INVALID_ARGUMENT, "rho_min_max / n_hits is null");
     if (cfg && cfg->disc_id == GR_DISC_NONE) return fail(GR_ERR_INVALID_ARGUMENT, "a corona illuminates accretion geometry: none given");
     for (int k = 0; k < n; ++k) ctxs[k]->corona_n = -1;
+    if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
     std::vector<unsigned long long> h(5 * (size_t)n);
     std::vector<gr_rayset> share((size_t)n);
     // every context's share is queued before any is waited for
@@ -4194,6 +4237,7 @@ int32_t gr_ray_tangent(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays,
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     if (rays && rays->n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
     int32_t rc;
+    if ((rc = refuse_sky_rows(rays, "gr_ray_tangent")) != GR_OK) return rc;
     GR_HIP(hipSetDevice(ctx->device));
     gr_rayset dev;
     if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
@@ -4211,6 +4255,7 @@ int32_t gr_rayset_endpoints(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* 
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     if (rays && rays->n > 0 && !points) return fail(GR_ERR_INVALID_ARGUMENT, "points is null");
     int32_t rc;
+    if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
     GR_HIP(hipSetDevice(ctx->device));
     gr_rayset dev;
     if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
@@ -4319,6 +4364,7 @@ int32_t rayset_rows_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, 
     if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
     if (!rays) return fail(GR_ERR_INVALID_ARGUMENT, "rayset is null");
     if (rays->n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "output is null");
+    if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
     {
         gr_rayset probe;
         int64_t o;
@@ -4380,6 +4426,8 @@ int32_t gr_ray_summary_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
 int32_t gr_ray_tangent_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
                              double* out, gr_stats* stats)
 {
+    int32_t rc;
+    if ((rc = refuse_sky_rows(rays, "gr_ray_tangent_multi")) != GR_OK) return rc;
     return rayset_rows_multi(ctxs, n, cfg, rays, sizeof(double) * 8, out, stats,
                              [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
                                  return gr_ray_tangent_device(c, cfg, dev, pf, (double*)d_out, d_st, c->stream);
@@ -4389,6 +4437,8 @@ int32_t gr_ray_tangent_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
 int32_t gr_redshift_radius_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays,
                                  const gr_pointfunction* pf, double r_min, double r_max, double* pairs, gr_stats* stats)
 {
+    int32_t rc;
+    if ((rc = refuse_sky_rows(rays, "gr_redshift_radius_multi")) != GR_OK) return rc;
     return rayset_rows_multi(ctxs, n, cfg, rays, sizeof(double) * 2, pairs, stats,
                              [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
                                  return gr_redshift_radius_device(c, cfg, dev, pf, r_min, r_max, (double*)d_out, d_st, c->stream);
@@ -4403,6 +4453,7 @@ int32_t gr_lineprofile_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
     if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
     if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
     if (!rays) return fail(GR_ERR_INVALID_ARGUMENT, "rayset is null");
+    if ((rc = refuse_sky_rows(rays, "gr_lineprofile_multi")) != GR_OK) return rc;
     if (!b || b->n_bins < 1 || !b->bin_edges || !flux) return fail(GR_ERR_INVALID_ARGUMENT, "binning/flux is null or empty");
     if (rays->sep_r && rays->sep_block != 0)
         return fail(GR_ERR_INVALID_ARGUMENT, "gr_lineprofile_multi: a separable ray set must come whole (sep_block = 0): the call deals it itself");

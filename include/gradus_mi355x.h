@@ -483,7 +483,16 @@ typedef struct gr_rayset {
      *     gt[4]      g_tμ(x)
      * and the rows of gr_ray_summary / gr_corona_trace hold g = energy_ratio against THAT sample's source velocity (pf->has_u_src
      * must be 0: the library forms (u_cov · v) / (gt · v) per ray and scales the static-observer ratio with it).  Host or device
-     * pointer like alpha; NULL: one position. */
+     * pointer like alpha; NULL: one position.
+     * Two rules go with it:
+     *   - ONLY gr_ray_summary / gr_corona_trace (and their _device / _multi forms) form that per-sample ratio; gr_rayset_endpoints
+     *     takes such a set too (its records carry no g).  gr_lineprofile, gr_redshift_radius and gr_ray_tangent -- host, _device
+     *     and _multi forms -- would return g against the static observer: they refuse a set with sky_rows
+     *     (GR_ERR_INVALID_ARGUMENT) before anything is staged.
+     *   - Under GR_METRIC_TABULATED every sample's start radius x[1] must lie inside the table's radial range (x_obs is not
+     *     read, so it is not what is checked).  The entry points that take HOST pointers check all n rows before staging and
+     *     refuse a set with a start outside [r_min, r_max] (GR_ERR_INVALID_ARGUMENT, the radius in the message); the _device
+     *     forms cannot see the rows: there the caller vouches that every row starts inside the table. */
     const double* sky_rows;
 } gr_rayset;
 #define GR_SKY_ROW 28
