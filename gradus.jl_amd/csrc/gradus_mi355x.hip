@@ -2287,7 +2287,9 @@ int32_t validate_ctxs(gr_ctx* const* ctxs, int32_t n)
     return GR_OK;
 }
 
-// enq(k): stage and launch context k's share (begins with begin_host_call); copy(k): queue its copy home.
+// The one path of a host call that has a *_multi form: the one-context entry point is the same implementation on `&ctx, 1`.
+// enq(k): stage and launch context k's share (begins with begin_host_call, before it stages: kernel_ms / call_ms count the
+// staging); copy(k): queue its copy home -- no enq queues a copy to the host, so every share is queued before any is waited for.
 // Whatever was started is waited for before the call returns, also on an error: the buffers belong to the caller.
 template <class Enqueue, class CopyBack>
 int32_t multi_drive(gr_ctx* const* ctxs, int32_t n, gr_stats* stats, Enqueue enq, CopyBack copy)
@@ -2318,6 +2320,13 @@ int32_t multi_drive(gr_ctx* const* ctxs, int32_t n, gr_stats* stats, Enqueue enq
         if (rc == GR_OK) rc = e;
         if (st && rc == GR_OK) st->enqueue_ms = k < 64 ? t_enq[k] : 0.0;
     }
+    return rc;
+}
+
+// what a one-context entry point returns of its shared implementation's result: enqueue_ms is the *_multi forms' to report
+int32_t one_context(int32_t rc, gr_stats* stats)
+{
+    if (rc == GR_OK && stats) stats->enqueue_ms = 0.0;
     return rc;
 }
 
@@ -2553,33 +2562,6 @@ int32_t gr_render_endpoints(gr_ctx* ctx, const gr_config* cfg, const gr_plane* p
     return end_host_call(ctx, stats);
 }
 
-int32_t gr_trace_endpoints(gr_ctx* ctx, const gr_config* cfg, const double* x, int64_t x_stride, const double* v,
-                           int64_t n, gr_point* points, gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "n must be non-negative");
-    if (x_stride != 0 && x_stride != 4) return fail(GR_ERR_INVALID_ARGUMENT, "x_stride must be 0 or 4");
-    if (n > 0 && (!x || !v || !points)) return fail(GR_ERR_INVALID_ARGUMENT, "x/v/points is null");
-    GR_HIP(hipSetDevice(ctx->device));      // before any allocation: ensure() mallocs on the current device
-    int32_t rc;
-    const size_t nx = (size_t)(x_stride == 0 ? 4 : 4 * n), nv = (size_t)(4 * n);
-    const size_t out_bytes = sizeof(gr_point) * (size_t)n;
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, out_bytes ? out_bytes : 8)) != GR_OK) return rc;
-    if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, sizeof(double) * (nx + nv) + 8)) != GR_OK) return rc;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    double* d_x = (double*)ctx->d_in;
-    double* d_v = d_x + nx;
-    if (n > 0) {
-        GR_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * nx, hipMemcpyHostToDevice, ctx->stream));
-        GR_HIP(hipMemcpyAsync(d_v, v, sizeof(double) * nv, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = gr_trace_endpoints_device(ctx, cfg, d_x, x_stride, d_v, n, (gr_point*)ctx->d_scratch,
-                                        stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream)) != GR_OK) return rc;
-    if (!is_pinned(points, out_bytes)) prefault_output(points, out_bytes, ctx->hugepages != 0);
-    if (out_bytes) GR_HIP(hipMemcpyAsync(points, ctx->d_scratch, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
-}
-
 int32_t gr_apply_pointfunction(gr_ctx* ctx, const gr_config* cfg, const gr_pointfunction* pf, const gr_point* points,
                                int64_t n, double max_time, double* out)
 {
@@ -2673,75 +2655,6 @@ static int32_t stage_rays(gr_ctx* ctx, const gr_rayset* rays, gr_rayset& dev, si
     }
     if (extra) *extra = (void*)(base + 4 * n);
     return GR_OK;
-}
-
-int32_t gr_lineprofile(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
-                       const gr_binning* b, double* flux, gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (!b || b->n_bins < 1 || !b->bin_edges || !flux) return fail(GR_ERR_INVALID_ARGUMENT, "binning/flux is null or empty");
-    int32_t rc;
-    if ((rc = refuse_sky_rows(rays, "gr_lineprofile")) != GR_OK) return rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    gr_rayset dev;
-    void* extra = nullptr;
-    const size_t nb = (size_t)b->n_bins;
-    const size_t ne = (b->eps_n >= 2 && b->eps_r && b->eps_v) ? (size_t)b->eps_n : 0;
-    if ((rc = stage_rays(ctx, rays, dev, sizeof(double) * (2 * nb + 2 * ne), &extra)) != GR_OK) return rc;
-    double* d_edges = (double*)extra;
-    double* d_flux = d_edges + nb;
-    GR_HIP(hipMemcpyAsync(d_edges, b->bin_edges, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
-    gr_binning db = *b;
-    db.bin_edges = d_edges;
-    if (ne) {
-        double* d_er = d_flux + nb;
-        GR_HIP(hipMemcpyAsync(d_er, b->eps_r, sizeof(double) * ne, hipMemcpyHostToDevice, ctx->stream));
-        GR_HIP(hipMemcpyAsync(d_er + ne, b->eps_v, sizeof(double) * ne, hipMemcpyHostToDevice, ctx->stream));
-        db.eps_r = d_er;
-        db.eps_v = d_er + ne;
-    }
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if ((rc = gr_lineprofile_device(ctx, cfg, &dev, pf, &db, d_flux, stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream)) != GR_OK) return rc;
-    GR_HIP(hipMemcpyAsync(flux, d_flux, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
-}
-
-int32_t gr_redshift_radius(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
-                           double r_min, double r_max, double* pairs, gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (rays && rays->n > 0 && !pairs) return fail(GR_ERR_INVALID_ARGUMENT, "pairs is null");
-    int32_t rc;
-    if ((rc = refuse_sky_rows(rays, "gr_redshift_radius")) != GR_OK) return rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    gr_rayset dev;
-    if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
-    const size_t bytes = sizeof(double) * 2 * (size_t)rays->n;
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if ((rc = gr_redshift_radius_device(ctx, cfg, &dev, pf, r_min, r_max, (double*)ctx->d_scratch,
-                                        stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream)) != GR_OK) return rc;
-    if (bytes) GR_HIP(hipMemcpyAsync(pairs, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
-}
-
-int32_t gr_ray_summary(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
-                       double* out, gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (rays && rays->n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
-    int32_t rc;
-    if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    gr_rayset dev;
-    if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
-    const size_t bytes = sizeof(double) * 4 * (size_t)rays->n;
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if ((rc = gr_ray_summary_device(ctx, cfg, &dev, pf, (double*)ctx->d_scratch, stats ? (gr_stats*)ctx->d_stats : nullptr,
-                                    ctx->stream)) != GR_OK) return rc;
-    if (bytes) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
 }
 
 // ---- corona -> disc: the reductions of emissivity_profile (src/corona/radial.jl:38-100) on the summaries gr_corona_trace keeps ----
@@ -3236,98 +3149,62 @@ int32_t rayset_share(const gr_rayset* rays, int32_t n, int k, gr_rayset& out, in
 }  // namespace
 }  // extern "C++"
 
-// gr_corona_trace in two halves, so that gr_corona_trace_multi can queue every context's share before it waits for any:
-// corona_enqueue stages the rays, traces, reduces (min ρ, max ρ, hits, max |g|, max |t|) and queues the 40-byte copy into `h`;
-// corona_collect waits for the context and reads them.
-static int32_t corona_enqueue(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf, gr_stats* stats,
-                              unsigned long long* h /* 5, pinned or pageable host memory that outlives the wait */)
-{
-    int32_t rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    ctx->corona_n = -1;
-    gr_rayset dev;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
-    const size_t bytes = sizeof(double) * 4 * (size_t)rays->n + 64;
-    if ((rc = ensure((void**)&ctx->d_corona, &ctx->corona_bytes, bytes)) != GR_OK) return rc;
-    unsigned long long* red = (unsigned long long*)(ctx->d_corona + 4 * (size_t)rays->n);
-    static const unsigned long long init[5] = { ~0ull, 0ull, 0ull, 0ull, 0ull };
-    GR_HIP(hipMemcpyAsync(red, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
-    ctx->sky_any_order = true;      // (the rows are reduced and binned: their order is the library's to choose)
-    rc = gr_ray_summary_device(ctx, cfg, &dev, pf, ctx->d_corona, stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream);
-    ctx->sky_any_order = false;
-    if (rc != GR_OK) return rc;
-    if (rays->n > 0) {
-        int64_t blocks = (rays->n + 255) / 256;
-        blocks = blocks > 512 ? 512 : blocks;
-        hipLaunchKernelGGL(k_corona_minmax, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->d_corona, rays->n, red);
-        GR_HIP(hipGetLastError());
-    }
-    GR_HIP(hipMemcpyAsync(h, red, sizeof(unsigned long long) * 5, hipMemcpyDeviceToHost, ctx->stream));
-    return GR_OK;
-}
-static int32_t corona_collect(gr_ctx* ctx, gr_stats* stats, const unsigned long long* h, int64_t n_rays, double v[5], int64_t* hits)
-{
-    int32_t rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    if ((rc = end_host_call(ctx, stats)) != GR_OK) return rc;      // (synchronises the stream)
-    std::memcpy(v, h, sizeof(double) * 5);
-    *hits = (int64_t)h[2];
-    ctx->corona_gmax = v[3];
-    ctx->corona_tmax = v[4];
-    ctx->corona_hits = *hits;
-    ctx->corona_n = n_rays;
-    return GR_OK;
-}
-
-int32_t gr_corona_trace(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
-                        double* rho_min_max, int64_t* n_hits, gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (!rays || !rays->sky_sampler) return fail(GR_ERR_INVALID_ARGUMENT, "gr_corona_trace traces a sky source (gr_rayset.sky_sampler != 0)");
-    if (!rho_min_max || !n_hits) return fail(GR_ERR_INVALID_ARGUMENT, "rho_min_max / n_hits is null");
-    if (cfg && cfg->disc_id == GR_DISC_NONE) return fail(GR_ERR_INVALID_ARGUMENT, "a corona illuminates accretion geometry: none given");
-    int32_t rc;
-    ctx->corona_n = -1;
-    if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
-    unsigned long long h[5];
-    double v[5];
-    if ((rc = corona_enqueue(ctx, cfg, rays, pf, stats, h)) != GR_OK) return rc;
-    if ((rc = corona_collect(ctx, stats, h, rays->n, v, n_hits)) != GR_OK) return rc;
-    rho_min_max[0] = *n_hits ? v[0] : NAN;
-    rho_min_max[1] = *n_hits ? v[1] : NAN;
-    return GR_OK;
-}
-
-int32_t gr_corona_trace_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
-                              double* rho_min_max, int64_t* n_hits, gr_stats* stats)
+// gr_corona_trace[_multi]: every context stages its share of the samples, traces it into its d_corona and reduces it there
+// (k_corona_minmax: min ρ, max ρ, hits, max |g|, max |t|); the 40 bytes of each come home in the driver's second phase and the
+// host folds them.  Whatever fails, no context of the call keeps rows to bin (corona_n = -1).
+static int32_t corona_trace_on(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                               double* rho_min_max, int64_t* n_hits, gr_stats* stats, const char* who)
 {
     int32_t rc;
     if ((rc = validate_ctxs(ctxs, n)) != GR_OK) return rc;
     if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
-    if (!rays || !rays->sky_sampler) return fail(GR_ERR_INVALID_ARGUMENT, "gr_corona_trace_multi traces a sky source (gr_rayset.sky_sampler != 0)");
+    for (int k = 0; k < n; ++k) ctxs[k]->corona_n = -1;
+    if (!rays || !rays->sky_sampler) return fail(GR_ERR_INVALID_ARGUMENT, std::string(who) + " traces a sky source (gr_rayset.sky_sampler != 0)");
     if (!rho_min_max || !n_hits) return fail(GR_ERR_INVALID_ARGUMENT, "rho_min_max / n_hits is null");
     if (cfg && cfg->disc_id == GR_DISC_NONE) return fail(GR_ERR_INVALID_ARGUMENT, "a corona illuminates accretion geometry: none given");
-    for (int k = 0; k < n; ++k) ctxs[k]->corona_n = -1;
     if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
     std::vector<unsigned long long> h(5 * (size_t)n);
     std::vector<gr_rayset> share((size_t)n);
-    // every context's share is queued before any is waited for
     for (int k = 0; k < n; ++k) {
         int64_t off;
         if ((rc = rayset_share(rays, n, k, share[(size_t)k], &off)) != GR_OK) return rc;
-        const auto t0 = std::chrono::steady_clock::now();
-        if ((rc = corona_enqueue(ctxs[k], cfg, &share[(size_t)k], pf, stats ? stats + k : nullptr, h.data() + 5 * (size_t)k)) != GR_OK) return rc;
-        if (stats) stats[k].enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
+    auto red_of = [&](int k) { return (unsigned long long*)(ctxs[k]->d_corona + 4 * (size_t)share[(size_t)k].n); };
+    auto enq = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        const gr_rayset& sh = share[(size_t)k];
+        int32_t r;
+        GR_HIP(hipSetDevice(c->device));
+        gr_rayset dev;
+        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
+        if ((r = stage_rays(c, &sh, dev, 0, nullptr)) != GR_OK) return r;
+        if ((r = ensure((void**)&c->d_corona, &c->corona_bytes, sizeof(double) * 4 * (size_t)sh.n + 64)) != GR_OK) return r;
+        static const unsigned long long init[5] = { ~0ull, 0ull, 0ull, 0ull, 0ull };
+        GR_HIP(hipMemcpyAsync(red_of(k), init, sizeof init, hipMemcpyHostToDevice, c->stream));
+        c->sky_any_order = true;      // (the rows are reduced and binned: their order is the library's to choose)
+        r = gr_ray_summary_device(c, cfg, &dev, pf, c->d_corona, stats ? (gr_stats*)c->d_stats : nullptr, c->stream);
+        c->sky_any_order = false;
+        if (r != GR_OK) return r;
+        if (sh.n > 0) {
+            int64_t blocks = (sh.n + 255) / 256;
+            blocks = blocks > 512 ? 512 : blocks;
+            hipLaunchKernelGGL(k_corona_minmax, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->d_corona, sh.n, red_of(k));
+            GR_HIP(hipGetLastError());
+        }
+        return GR_OK;
+    };
+    auto copy = [&](int k) -> int32_t {
+        GR_HIP(hipSetDevice(ctxs[k]->device));
+        GR_HIP(hipMemcpyAsync(h.data() + 5 * (size_t)k, red_of(k), sizeof(unsigned long long) * 5, hipMemcpyDeviceToHost, ctxs[k]->stream));
+        return GR_OK;
+    };
+    if ((rc = multi_drive(ctxs, n, stats, enq, copy)) != GR_OK) return rc;
     double lo = INFINITY, hi = -INFINITY, gmax = 0.0, tmax = 0.0;
     int64_t hits = 0;
     for (int k = 0; k < n; ++k) {
         double v[5];
-        int64_t hk;
-        const double enq = stats ? stats[k].enqueue_ms : 0.0;
-        if ((rc = corona_collect(ctxs[k], stats ? stats + k : nullptr, h.data() + 5 * (size_t)k, share[(size_t)k].n, v, &hk)) != GR_OK) return rc;
-        if (stats) stats[k].enqueue_ms = enq;
+        std::memcpy(v, h.data() + 5 * (size_t)k, sizeof v);
+        const int64_t hk = (int64_t)h[5 * (size_t)k + 2];
         if (hk) { lo = std::fmin(lo, v[0]); hi = std::fmax(hi, v[1]); }
         gmax = std::fmax(gmax, v[3]);
         tmax = std::fmax(tmax, v[4]);
@@ -3338,6 +3215,7 @@ int32_t gr_corona_trace_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* c
         ctxs[k]->corona_gmax = gmax;
         ctxs[k]->corona_tmax = tmax;
         ctxs[k]->corona_hits = hits;
+        ctxs[k]->corona_n = share[(size_t)k].n;
     }
     *n_hits = hits;
     rho_min_max[0] = hits ? lo : NAN;
@@ -3345,88 +3223,89 @@ int32_t gr_corona_trace_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* c
     return GR_OK;
 }
 
-// gr_corona_bin's device half: the context's rows into integer accumulators (count, Σg hi / lo, Σt hi / lo) on the grid of its
-// corona_gmax / corona_tmax / corona_hits; `acc` (5 nb, host) is filled when the stream has drained
-static int32_t corona_bin_enqueue(gr_ctx* ctx, const double* edges, size_t nb, long long* acc)
+int32_t gr_corona_trace(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                        double* rho_min_max, int64_t* n_hits, gr_stats* stats)
+{
+    return one_context(corona_trace_on(&ctx, 1, cfg, rays, pf, rho_min_max, n_hits, stats, "gr_corona_trace"), stats);
+}
+
+int32_t gr_corona_trace_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                              double* rho_min_max, int64_t* n_hits, gr_stats* stats)
+{
+    return corona_trace_on(ctxs, n, cfg, rays, pf, rho_min_max, n_hits, stats, "gr_corona_trace_multi");
+}
+
+// gr_corona_bin[_multi]: every context bins its rows into integer accumulators (count, Σg hi / lo, Σt hi / lo) on the grid of the
+// trace's corona_gmax / corona_tmax / corona_hits; the 5 nb accumulators of each come home in the driver's second phase.
+static int32_t corona_bin_on(gr_ctx* const* ctxs, int32_t n, const double* edges, int64_t n_edges, double* out, bool multi)
 {
     int32_t rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, sizeof(double) * 6 * nb + 64)) != GR_OK) return rc;
-    double* d_edges = (double*)ctx->d_in;
-    unsigned long long* d_acc = (unsigned long long*)(d_edges + nb);
-    GR_HIP(hipMemcpyAsync(d_edges, edges, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
-    GR_HIP(hipMemsetAsync(d_acc, 0, sizeof(unsigned long long) * 5 * nb, ctx->stream));
-    const CoronaGrid gg = corona_grid(ctx->corona_gmax, ctx->corona_hits), gt = corona_grid(ctx->corona_tmax, ctx->corona_hits);
-    if (ctx->corona_n > 0) {
-        int64_t blocks = (ctx->corona_n + 255) / 256;
-        blocks = blocks > 1024 ? 1024 : blocks;
-        if (nb <= 1024) {
-            hipLaunchKernelGGL(k_corona_bin<1>, dim3((unsigned)blocks), dim3(256), sizeof(unsigned long long) * 5 * nb, ctx->stream,
-                               ctx->d_corona, ctx->corona_n, d_edges, (int)nb, gg.sc, gt.sc, d_acc);
-        } else {
-            hipLaunchKernelGGL(k_corona_bin<0>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->d_corona, ctx->corona_n,
-                               d_edges, (int)nb, gg.sc, gt.sc, d_acc);
-        }
-        GR_HIP(hipGetLastError());
+    if ((rc = validate_ctxs(ctxs, n)) != GR_OK) return rc;
+    if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
+    const gr_ctx* c0 = ctxs[0];
+    for (int k = 0; k < n; ++k) {
+        if (ctxs[k]->corona_n < 0)
+            return fail(GR_ERR_INVALID_ARGUMENT, multi ? "gr_corona_bin_multi bins the rays of the contexts' last gr_corona_trace_multi: there is none"
+                                                       : "gr_corona_bin bins the rays of the context's last gr_corona_trace: there is none");
+        if (ctxs[k]->corona_gmax != c0->corona_gmax || ctxs[k]->corona_tmax != c0->corona_tmax || ctxs[k]->corona_hits != c0->corona_hits)
+            return fail(GR_ERR_INVALID_ARGUMENT, "gr_corona_bin_multi: the contexts do not hold the shares of ONE gr_corona_trace_multi");
     }
-    GR_HIP(hipMemcpyAsync(acc, d_acc, sizeof(long long) * 5 * nb, hipMemcpyDeviceToHost, ctx->stream));
-    return GR_OK;
-}
-static void corona_bins_out(const long long* acc, size_t nb, double gmax, double tmax, int64_t hits, double* out)
-{
-    const CoronaGrid gg = corona_grid(gmax, hits), gt = corona_grid(tmax, hits);
+    if (!edges || !out || n_edges < 1 || n_edges > 65536) return fail(GR_ERR_INVALID_ARGUMENT, "edges / out is null or n_edges not in 1..65536");
+    for (int64_t i = 1; i < n_edges; ++i)
+        if (!(edges[i] >= edges[i - 1])) return fail(GR_ERR_INVALID_ARGUMENT, "bin edges must ascend");
+    const size_t nb = (size_t)n_edges;
+    const CoronaGrid gg = corona_grid(c0->corona_gmax, c0->corona_hits), gt = corona_grid(c0->corona_tmax, c0->corona_hits);
+    std::vector<long long> acc(5 * nb * (size_t)n);
+    // (no statistics and no timing here: the call begins with its staging, the driver's wait ends it)
+    auto enq = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        int32_t r;
+        GR_HIP(hipSetDevice(c->device));
+        if ((r = ensure(&c->d_in, &c->in_bytes, sizeof(double) * 6 * nb + 64)) != GR_OK) return r;
+        double* d_edges = (double*)c->d_in;
+        unsigned long long* d_acc = (unsigned long long*)(d_edges + nb);
+        GR_HIP(hipMemcpyAsync(d_edges, edges, sizeof(double) * nb, hipMemcpyHostToDevice, c->stream));
+        GR_HIP(hipMemsetAsync(d_acc, 0, sizeof(unsigned long long) * 5 * nb, c->stream));
+        if (c->corona_n > 0) {
+            int64_t blocks = (c->corona_n + 255) / 256;
+            blocks = blocks > 1024 ? 1024 : blocks;
+            if (nb <= 1024) {
+                hipLaunchKernelGGL(k_corona_bin<1>, dim3((unsigned)blocks), dim3(256), sizeof(unsigned long long) * 5 * nb, c->stream,
+                                   c->d_corona, c->corona_n, d_edges, (int)nb, gg.sc, gt.sc, d_acc);
+            } else {
+                hipLaunchKernelGGL(k_corona_bin<0>, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->d_corona, c->corona_n,
+                                   d_edges, (int)nb, gg.sc, gt.sc, d_acc);
+            }
+            GR_HIP(hipGetLastError());
+        }
+        return GR_OK;
+    };
+    auto copy = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        GR_HIP(hipSetDevice(c->device));
+        GR_HIP(hipMemcpyAsync(acc.data() + 5 * nb * (size_t)k, (const double*)c->d_in + nb, sizeof(long long) * 5 * nb, hipMemcpyDeviceToHost, c->stream));
+        return GR_OK;
+    };
+    if ((rc = multi_drive(ctxs, n, nullptr, enq, copy)) != GR_OK) return rc;
+    // integer addition is associative: the sums of the shares are the sums one context would have formed of all rays
+    for (int k = 1; k < n; ++k)
+        for (size_t i = 0; i < 5 * nb; ++i) acc[i] += acc[5 * nb * (size_t)k + i];
     for (size_t i = 0; i < nb; ++i) {
         out[i] = (double)acc[i];
         out[nb + i] = (double)(((long double)acc[nb + i] + (long double)acc[2 * nb + i] * (long double)gg.lo_unit) * (long double)gg.step);
         out[2 * nb + i] = (double)(((long double)acc[3 * nb + i] + (long double)acc[4 * nb + i] * (long double)gt.lo_unit) * (long double)gt.step);
     }
-}
-static int32_t corona_bin_args(const double* edges, int64_t n_edges, const double* out)
-{
-    if (!edges || !out || n_edges < 1 || n_edges > 65536) return fail(GR_ERR_INVALID_ARGUMENT, "edges / out is null or n_edges not in 1..65536");
-    for (int64_t i = 1; i < n_edges; ++i)
-        if (!(edges[i] >= edges[i - 1])) return fail(GR_ERR_INVALID_ARGUMENT, "bin edges must ascend");
     return GR_OK;
 }
 
 int32_t gr_corona_bin(gr_ctx* ctx, const double* edges, int64_t n_edges, double* out)
 {
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (ctx->corona_n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_corona_bin bins the rays of the context's last gr_corona_trace: there is none");
-    int32_t rc;
-    if ((rc = corona_bin_args(edges, n_edges, out)) != GR_OK) return rc;
-    const size_t nb = (size_t)n_edges;
-    std::vector<long long> acc(5 * nb);
-    if ((rc = corona_bin_enqueue(ctx, edges, nb, acc.data())) != GR_OK) return rc;
-    GR_HIP(hipStreamSynchronize(ctx->stream));
-    corona_bins_out(acc.data(), nb, ctx->corona_gmax, ctx->corona_tmax, ctx->corona_hits, out);
-    return GR_OK;
+    return corona_bin_on(&ctx, 1, edges, n_edges, out, false);
 }
 
 int32_t gr_corona_bin_multi(gr_ctx* const* ctxs, int32_t n, const double* edges, int64_t n_edges, double* out)
 {
-    int32_t rc;
-    if ((rc = validate_ctxs(ctxs, n)) != GR_OK) return rc;
-    if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
-    for (int k = 0; k < n; ++k) {
-        if (ctxs[k]->corona_n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "gr_corona_bin_multi bins the rays of the contexts' last gr_corona_trace_multi: there is none");
-        if (ctxs[k]->corona_gmax != ctxs[0]->corona_gmax || ctxs[k]->corona_tmax != ctxs[0]->corona_tmax || ctxs[k]->corona_hits != ctxs[0]->corona_hits)
-            return fail(GR_ERR_INVALID_ARGUMENT, "gr_corona_bin_multi: the contexts do not hold the shares of ONE gr_corona_trace_multi");
-    }
-    if ((rc = corona_bin_args(edges, n_edges, out)) != GR_OK) return rc;
-    const size_t nb = (size_t)n_edges;
-    std::vector<long long> acc(5 * nb * (size_t)n);
-    for (int k = 0; k < n; ++k)
-        if ((rc = corona_bin_enqueue(ctxs[k], edges, nb, acc.data() + 5 * nb * (size_t)k)) != GR_OK) return rc;
-    for (int k = 0; k < n; ++k) {
-        GR_HIP(hipSetDevice(ctxs[k]->device));
-        GR_HIP(hipStreamSynchronize(ctxs[k]->stream));
-    }
-    // integer addition is associative: the sums of the shares are the sums one context would have formed of all rays
-    for (int k = 1; k < n; ++k)
-        for (size_t i = 0; i < 5 * nb; ++i) acc[i] += acc[5 * nb * (size_t)k + i];
-    corona_bins_out(acc.data(), nb, ctxs[0]->corona_gmax, ctxs[0]->corona_tmax, ctxs[0]->corona_hits, out);
-    return GR_OK;
+    return corona_bin_on(ctxs, n, edges, n_edges, out, true);
 }
 
 // ---- observer -> disc on the device: lagtransfer's second half and binflux (transfer-functions-2d.jl:141-242) ----
@@ -4231,45 +4110,7 @@ int32_t gr_ring_arms(gr_ctx* ctx, const gr_config* cfg, const gr_ringset* rings,
     return GR_OK;
 }
 
-int32_t gr_ray_tangent(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
-                       double* out, gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (rays && rays->n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
-    int32_t rc;
-    if ((rc = refuse_sky_rows(rays, "gr_ray_tangent")) != GR_OK) return rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    gr_rayset dev;
-    if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
-    const size_t bytes = sizeof(double) * 8 * (size_t)rays->n;
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if ((rc = gr_ray_tangent_device(ctx, cfg, &dev, pf, (double*)ctx->d_scratch, stats ? (gr_stats*)ctx->d_stats : nullptr,
-                                    ctx->stream)) != GR_OK) return rc;
-    if (bytes) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
-}
-
-int32_t gr_rayset_endpoints(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, gr_point* points, gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (rays && rays->n > 0 && !points) return fail(GR_ERR_INVALID_ARGUMENT, "points is null");
-    int32_t rc;
-    if ((rc = sky_rows_in_table(cfg, rays)) != GR_OK) return rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    gr_rayset dev;
-    if ((rc = stage_rays(ctx, rays, dev, 0, nullptr)) != GR_OK) return rc;
-    const size_t bytes = sizeof(gr_point) * (size_t)rays->n;
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if ((rc = gr_rayset_endpoints_device(ctx, cfg, &dev, (gr_point*)ctx->d_scratch, stats ? (gr_stats*)ctx->d_stats : nullptr,
-                                         ctx->stream)) != GR_OK) return rc;
-    if (!is_pinned(points, bytes)) prefault_output(points, bytes, ctx->hugepages != 0);
-    if (bytes) GR_HIP(hipMemcpyAsync(points, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
-}
-
-// ---- *_multi on ray arrays and ray sets ----
+// ---- ray arrays and ray sets: one context, or contiguous shares of the rays over several ----
 
 int32_t gr_trace_endpoints_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const double* x, int64_t x_stride,
                                  const double* v, int64_t n_rays, gr_point* points, gr_stats* stats)
@@ -4316,13 +4157,25 @@ int32_t gr_trace_endpoints_multi(gr_ctx* const* ctxs, int32_t n, const gr_config
     return multi_drive(ctxs, n, stats, enq, copy);
 }
 
+int32_t gr_trace_endpoints(gr_ctx* ctx, const gr_config* cfg, const double* x, int64_t x_stride, const double* v,
+                           int64_t n, gr_point* points, gr_stats* stats)
+{
+    return one_context(gr_trace_endpoints_multi(&ctx, 1, cfg, x, x_stride, v, n, points, stats), stats);
+}
+
 extern "C++" {
 namespace {
-// context k's contiguous share of a ray set (host pointers)
+// context k's contiguous share of a ray set (host pointers); one context's share is the caller's set as it came -- tiled or
+// blocked, with its own sky_first / sky_total: only sharing rays out needs them in ray order
 int32_t rayset_share(const gr_rayset* rays, int32_t n, int k, gr_rayset& out, int64_t* off_out)
 {
     if (!rays) return fail(GR_ERR_INVALID_ARGUMENT, "rayset is null");
     if (rays->n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "n must be non-negative");
+    if (n == 1) {
+        out = *rays;
+        *off_out = 0;
+        return GR_OK;
+    }
     if (rays->sep_r && (rays->sep_block != 0 || rays->sep_tiled))
         return fail(GR_ERR_INVALID_ARGUMENT, "*_multi: a separable ray set with one output row per ray must come whole and in ray order "
                                              "(sep_block = 0, sep_tiled = 0)");
@@ -4352,10 +4205,10 @@ int32_t rayset_share(const gr_rayset* rays, int32_t n, int k, gr_rayset& out, in
     return GR_OK;
 }
 
-// One output row of `row_bytes` per ray: context k stages its share of the rays, `launch(ctx, device rayset, d_out, d_stats)`
-// queues the kernel, the rows go home with one contiguous copy.
+// One output row of `row_bytes` per ray, for one context or several: context k stages its share of the rays,
+// `launch(ctx, device rayset, d_out, d_stats)` queues the kernel, the rows go home with one contiguous copy.
 template <class Launch>
-int32_t rayset_rows_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, size_t row_bytes,
+int32_t rayset_rows(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, size_t row_bytes,
                           void* out, gr_stats* stats, Launch launch)
 {
     int32_t rc;
@@ -4379,8 +4232,6 @@ int32_t rayset_rows_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, 
         int32_t r;
         if ((r = rayset_share(rays, n, k, share, &off)) != GR_OK) return r;
         GR_HIP(hipSetDevice(c->device));
-        // (before the rays are staged: kernel_ms / call_ms count from the start of the call's device work, input staging included,
-        // as in the single-context entry points)
         if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
         if ((r = stage_rays(c, &share, dev, 0, nullptr)) != GR_OK) return r;
         const size_t bytes = row_bytes * (size_t)share.n;
@@ -4408,54 +4259,94 @@ int32_t rayset_rows_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, 
 int32_t gr_rayset_endpoints_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, gr_point* points,
                                   gr_stats* stats)
 {
-    return rayset_rows_multi(ctxs, n, cfg, rays, sizeof(gr_point), points, stats,
-                             [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
-                                 return gr_rayset_endpoints_device(c, cfg, dev, (gr_point*)d_out, d_st, c->stream);
-                             });
+    return rayset_rows(ctxs, n, cfg, rays, sizeof(gr_point), points, stats,
+                       [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
+                           return gr_rayset_endpoints_device(c, cfg, dev, (gr_point*)d_out, d_st, c->stream);
+                       });
+}
+
+int32_t gr_rayset_endpoints(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, gr_point* points, gr_stats* stats)
+{
+    return one_context(gr_rayset_endpoints_multi(&ctx, 1, cfg, rays, points, stats), stats);
 }
 
 int32_t gr_ray_summary_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
                              double* out, gr_stats* stats)
 {
-    return rayset_rows_multi(ctxs, n, cfg, rays, sizeof(double) * 4, out, stats,
-                             [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
-                                 return gr_ray_summary_device(c, cfg, dev, pf, (double*)d_out, d_st, c->stream);
-                             });
+    return rayset_rows(ctxs, n, cfg, rays, sizeof(double) * 4, out, stats,
+                       [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
+                           return gr_ray_summary_device(c, cfg, dev, pf, (double*)d_out, d_st, c->stream);
+                       });
+}
+
+int32_t gr_ray_summary(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                       double* out, gr_stats* stats)
+{
+    return one_context(gr_ray_summary_multi(&ctx, 1, cfg, rays, pf, out, stats), stats);
+}
+
+// (the two that refuse a source velocity per sample name the entry point the caller used)
+static int32_t ray_tangent_on(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                              double* out, gr_stats* stats, const char* who)
+{
+    int32_t rc;
+    if ((rc = refuse_sky_rows(rays, who)) != GR_OK) return rc;
+    return rayset_rows(ctxs, n, cfg, rays, sizeof(double) * 8, out, stats,
+                       [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
+                           return gr_ray_tangent_device(c, cfg, dev, pf, (double*)d_out, d_st, c->stream);
+                       });
+}
+
+int32_t gr_ray_tangent(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                       double* out, gr_stats* stats)
+{
+    return one_context(ray_tangent_on(&ctx, 1, cfg, rays, pf, out, stats, "gr_ray_tangent"), stats);
 }
 
 int32_t gr_ray_tangent_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
                              double* out, gr_stats* stats)
 {
+    return ray_tangent_on(ctxs, n, cfg, rays, pf, out, stats, "gr_ray_tangent_multi");
+}
+
+static int32_t redshift_radius_on(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                                  double r_min, double r_max, double* pairs, gr_stats* stats, const char* who)
+{
     int32_t rc;
-    if ((rc = refuse_sky_rows(rays, "gr_ray_tangent_multi")) != GR_OK) return rc;
-    return rayset_rows_multi(ctxs, n, cfg, rays, sizeof(double) * 8, out, stats,
-                             [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
-                                 return gr_ray_tangent_device(c, cfg, dev, pf, (double*)d_out, d_st, c->stream);
-                             });
+    if ((rc = refuse_sky_rows(rays, who)) != GR_OK) return rc;
+    return rayset_rows(ctxs, n, cfg, rays, sizeof(double) * 2, pairs, stats,
+                       [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
+                           return gr_redshift_radius_device(c, cfg, dev, pf, r_min, r_max, (double*)d_out, d_st, c->stream);
+                       });
+}
+
+int32_t gr_redshift_radius(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                           double r_min, double r_max, double* pairs, gr_stats* stats)
+{
+    return one_context(redshift_radius_on(&ctx, 1, cfg, rays, pf, r_min, r_max, pairs, stats, "gr_redshift_radius"), stats);
 }
 
 int32_t gr_redshift_radius_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays,
                                  const gr_pointfunction* pf, double r_min, double r_max, double* pairs, gr_stats* stats)
 {
-    int32_t rc;
-    if ((rc = refuse_sky_rows(rays, "gr_redshift_radius_multi")) != GR_OK) return rc;
-    return rayset_rows_multi(ctxs, n, cfg, rays, sizeof(double) * 2, pairs, stats,
-                             [&](gr_ctx* c, const gr_rayset* dev, void* d_out, gr_stats* d_st) {
-                                 return gr_redshift_radius_device(c, cfg, dev, pf, r_min, r_max, (double*)d_out, d_st, c->stream);
-                             });
+    return redshift_radius_on(ctxs, n, cfg, rays, pf, r_min, r_max, pairs, stats, "gr_redshift_radius_multi");
 }
 
-int32_t gr_lineprofile_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
-                             const gr_binning* b, double* flux, gr_stats* stats)
+// One histogram per context, added on the host.  The two entry points differ in the deal alone: gr_lineprofile takes the set as
+// it is given (a shard of gradus.jl_amd/distributed.py comes with its own sep_block / sep_stride), gr_lineprofile_multi deals a
+// separable plane in strips itself.
+static int32_t lineprofile_on(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                              const gr_binning* b, double* flux, gr_stats* stats, bool multi)
 {
+    const char* who = multi ? "gr_lineprofile_multi" : "gr_lineprofile";
     int32_t rc;
     if ((rc = validate_ctxs(ctxs, n)) != GR_OK) return rc;
     if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
     if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
     if (!rays) return fail(GR_ERR_INVALID_ARGUMENT, "rayset is null");
-    if ((rc = refuse_sky_rows(rays, "gr_lineprofile_multi")) != GR_OK) return rc;
+    if ((rc = refuse_sky_rows(rays, who)) != GR_OK) return rc;
     if (!b || b->n_bins < 1 || !b->bin_edges || !flux) return fail(GR_ERR_INVALID_ARGUMENT, "binning/flux is null or empty");
-    if (rays->sep_r && rays->sep_block != 0)
+    if (multi && rays->sep_r && rays->sep_block != 0)
         return fail(GR_ERR_INVALID_ARGUMENT, "gr_lineprofile_multi: a separable ray set must come whole (sep_block = 0): the call deals it itself");
     const size_t nb = (size_t)b->n_bins;
     const size_t ne = (b->eps_n >= 2 && b->eps_r && b->eps_v) ? (size_t)b->eps_n : 0;
@@ -4472,10 +4363,10 @@ int32_t gr_lineprofile_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
     try {
         part.assign(nb * (size_t)n, 0.0);
     } catch (...) {
-        return fail(GR_ERR_OUT_OF_MEMORY, "gr_lineprofile_multi: partial histograms");
+        return fail(GR_ERR_OUT_OF_MEMORY, std::string(who) + ": partial histograms");
     }
     auto share_of = [&](int k, gr_rayset& sh) -> int32_t {
-        if (!rays->sep_r) {
+        if (!multi || !rays->sep_r) {
             int64_t off;
             return rayset_share(rays, n, k, sh, &off);
         }
@@ -4501,7 +4392,7 @@ int32_t gr_lineprofile_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
         if ((r = share_of(k, sh)) != GR_OK) return r;
         GR_HIP(hipSetDevice(c->device));
         void* extra = nullptr;
-        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;      // (before the staging, see rayset_rows_multi)
+        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
         if ((r = stage_rays(c, &sh, dev, sizeof(double) * (2 * nb + 2 * ne), &extra)) != GR_OK) return r;
         double* d_edges = (double*)extra;
         double* d_flux = d_edges + nb;
@@ -4534,6 +4425,18 @@ int32_t gr_lineprofile_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
     return GR_OK;
 }
 
+int32_t gr_lineprofile(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                       const gr_binning* b, double* flux, gr_stats* stats)
+{
+    return one_context(lineprofile_on(&ctx, 1, cfg, rays, pf, b, flux, stats, false), stats);
+}
+
+int32_t gr_lineprofile_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                             const gr_binning* b, double* flux, gr_stats* stats)
+{
+    return lineprofile_on(ctxs, n, cfg, rays, pf, b, flux, stats, true);
+}
+
 }  // extern "C"
 
 // ---- gr_sky_cells: host buffers; one context, or contiguous shares of the cells over several ----
@@ -4559,25 +4462,6 @@ int32_t stage_skycells(gr_ctx* c, const gr_skycells* cells, int64_t off, int64_t
 }  // namespace
 }  // extern "C++"
 
-int32_t gr_sky_cells(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf, double* out,
-                     gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    int32_t rc;
-    if ((rc = skycells_check(cfg, cells, pf, true)) != GR_OK) return rc;
-    if (cells->n > 0 && !out) return fail(GR_ERR_INVALID_ARGUMENT, "out is null");
-    GR_HIP(hipSetDevice(ctx->device));
-    gr_skycells dev;
-    if ((rc = stage_skycells(ctx, cells, 0, cells->n, dev)) != GR_OK) return rc;
-    const size_t bytes = sizeof(double) * GR_SKYCELL_ROW * (size_t)cells->n;
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if ((rc = gr_sky_cells_device(ctx, cfg, &dev, pf, (double*)ctx->d_scratch, stats ? (gr_stats*)ctx->d_stats : nullptr,
-                                  ctx->stream)) != GR_OK) return rc;
-    if (bytes) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
-}
-
 int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf,
                            double* out, gr_stats* stats)
 {
@@ -4593,7 +4477,7 @@ int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg,
         contiguous_share(cells->n, n, k, &off, &cnt);
         int32_t r;
         GR_HIP(hipSetDevice(c->device));
-        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;      // (before the staging, see rayset_rows_multi)
+        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
         gr_skycells dev;
         if ((r = stage_skycells(c, cells, off, cnt, dev)) != GR_OK) return r;
         if ((r = ensure(&c->d_scratch, &c->scratch_bytes, cnt ? row_bytes * (size_t)cnt : 8)) != GR_OK) return r;
@@ -4610,6 +4494,12 @@ int32_t gr_sky_cells_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg,
         return GR_OK;
     };
     return multi_drive(ctxs, n, stats, enq, copy);
+}
+
+int32_t gr_sky_cells(gr_ctx* ctx, const gr_config* cfg, const gr_skycells* cells, const gr_pointfunction* pf, double* out,
+                     gr_stats* stats)
+{
+    return one_context(gr_sky_cells_multi(&ctx, 1, cfg, cells, pf, out, stats), stats);
 }
 
 // ---- gr_plane_cells: host buffers, as gr_sky_cells ----
@@ -4632,23 +4522,6 @@ int32_t stage_planecells(gr_ctx* c, const double* alpha, const double* beta, int
 }  // namespace
 }  // extern "C++"
 
-int32_t gr_plane_cells(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const double* alpha, const double* beta, int64_t n, gr_point* out,
-                       gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    int32_t rc;
-    if ((rc = planecells_check(cfg, plane)) != GR_OK) return rc;
-    if ((rc = planecells_args(alpha, beta, n, out)) != GR_OK) return rc;
-    GR_HIP(hipSetDevice(ctx->device));
-    if ((rc = stage_planecells(ctx, alpha, beta, 0, n)) != GR_OK) return rc;      // (its copies come before ev0: the staging is not timed)
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    const double* b = (const double*)ctx->d_in;
-    if ((rc = gr_plane_cells_device(ctx, cfg, plane, b, b + n, n, (gr_point*)ctx->d_scratch, stats ? (gr_stats*)ctx->d_stats : nullptr,
-                                    ctx->stream)) != GR_OK) return rc;
-    if (n) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, sizeof(gr_point) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
-}
-
 int32_t gr_plane_cells_multi(gr_ctx* const* ctxs, int32_t n_ctx, const gr_config* cfg, const gr_plane* plane, const double* alpha,
                              const double* beta, int64_t n, gr_point* out, gr_stats* stats)
 {
@@ -4663,7 +4536,7 @@ int32_t gr_plane_cells_multi(gr_ctx* const* ctxs, int32_t n_ctx, const gr_config
         contiguous_share(n, n_ctx, k, &off, &cnt);
         int32_t r;
         GR_HIP(hipSetDevice(c->device));
-        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;      // (before the staging, see rayset_rows_multi)
+        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
         if ((r = stage_planecells(c, alpha, beta, off, cnt)) != GR_OK) return r;
         if (cnt == 0) return GR_OK;
         const double* b = (const double*)c->d_in;
@@ -4679,6 +4552,12 @@ int32_t gr_plane_cells_multi(gr_ctx* const* ctxs, int32_t n_ctx, const gr_config
         return GR_OK;
     };
     return multi_drive(ctxs, n_ctx, stats, enq, copy);
+}
+
+int32_t gr_plane_cells(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const double* alpha, const double* beta, int64_t n, gr_point* out,
+                       gr_stats* stats)
+{
+    return one_context(gr_plane_cells_multi(&ctx, 1, cfg, plane, alpha, beta, n, out, stats), stats);
 }
 
 // ---- an adaptive sky resident on the device: gr_sky_* (AdaptiveSky, adaptive-sky.jl; the drivers of adaptive-sample.jl:486-842) ----

@@ -357,8 +357,10 @@ int32_t gr_render(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane,
  *            may block the host until THAT device's kernel has finished -- every other device is already running);
  *   phase 3  wait for all of them.
  * There is no exchange between devices at all.  ctxs must be distinct contexts; they may live on different devices or (for
- * testing) on the same one.  stats[k] receives the counters of ctxs[k] (may be NULL).  With n = 1 a call is equivalent to its
- * single-context entry point and produces the same bytes.
+ * testing) on the same one.  stats[k] receives the counters of ctxs[k] (may be NULL).  With n = 1 a call produces the bytes of
+ * its single-context entry point -- which, the two image-plane renders apart, IS this call on its one context: the same checks,
+ * the same timings (kernel_ms / call_ms from before the staging of the inputs), nothing left in flight on an error, a ray set
+ * taken as it is given (the refusals below concern sharing rays out: n > 1), and enqueue_ms = 0.
  *
  * Image planes (gr_render_multi, gr_render_endpoints_multi): the columns are dealt to the n contexts block-cyclically in
  * groups of `block_cols` columns (0 = default 8, halved until it divides width / n) -- centre columns hold the long rays, so

@@ -481,3 +481,85 @@ def test_corona_through_the_fp32_kernels(G, ens):
         c = K.device_radial_profile(m, d, model, sampler=s, n_samples=40_000, N=30, ensemble=ens, abstol=1e-5, reltol=1e-5)
         ri = np.array([3.0, 4.0, 6.0])
         np.testing.assert_allclose(b.emissivity_at(ri), c.emissivity_at(ri), rtol=0.4)       # fp32 and fp64 at the SAME tolerance lose the same share there (which photons: a matter of step placement)
+
+
+def _lamp_post_abi(G, ens, n):
+    """(cfg, sky rayset, point function, what they keep alive) of a lamp-post source of n samples over a Kerr thin disc"""
+    from gradus_jl_amd.pointfunctions import GR_PF_REDSHIFT, PointFunction
+    from gradus_jl_amd.rendering import abi_pointfunction
+    from gradus_jl_amd.tracing import tracing_configuration
+
+    m = G.KerrMetric(1.0, 0.998)
+    model, d = G.LampPostModel(h=6.0), G.ThinDisc(0.0, 300.0)
+    s = G.EvenSampler(G.BothHemispheres(), G.GoldenSpiralGenerator())
+    rs, keep, x, v = G.corona.sky_rayset(m, model, s, n)
+    config = tracing_configuration(m, x, np.zeros((1, 4)), d, (0.0, 5000.0), callback=G.domain_upper_hemisphere(), ensemble=ens)
+    pf, keep_pf = abi_pointfunction(PointFunction(None, device_pf=GR_PF_REDSHIFT, extra={"r_isco": m.isco(), "plunge": None}))
+    pf.has_u_src = 1
+    for q in range(4):
+        pf.u_src[q] = v[q]
+    return config.abi_config(), rs, pf, (keep, keep_pf, config)
+
+
+@pytest.mark.gpu
+def test_a_refused_corona_trace_multi_leaves_nothing_behind(G, ens):
+    """Three contexts that hold the shares of a trace, then a gr_corona_trace_multi whose configuration validate_cfg rejects --
+    which the call learns on context 0's stream, after that context's call has begun: it returns an error with nothing in
+    flight, NO context keeps rows (gr_corona_bin_multi: "there is none"), and the same contexts then trace and bin the bits of
+    the one-context pair."""
+    from gradus_jl_amd import _lib
+
+    L = _lib.load()
+    n = 3001
+    cfg, rs, pf, keep = _lamp_post_abi(G, ens, n)
+    three = [G.EnsembleMI355X(0) for _ in range(3)]
+    arr, sts = _lib.ctx_array([e.ctx for e in three])
+    lim, hits, st = np.zeros(2), C.c_int64(0), _lib.gr_stats()
+    _lib.check(L.gr_corona_trace(ens.ctx.handle, C.byref(cfg), C.byref(rs), C.byref(pf), lim.ctypes.data, C.byref(hits), C.byref(st)))
+    assert 0.3 * n < hits.value < 0.7 * n and st.rays == n and st.enqueue_ms == 0.0
+    edges = np.ascontiguousarray(np.linspace(lim[0], lim[1], 32))
+    one = np.zeros((3, edges.size))
+    _lib.check(L.gr_corona_bin(ens.ctx.handle, edges.ctypes.data, edges.size, one.ctypes.data))
+    lim3, hits3 = np.zeros(2), C.c_int64(0)
+    _lib.check(L.gr_corona_trace_multi(arr, 3, C.byref(cfg), C.byref(rs), C.byref(pf), lim3.ctypes.data, C.byref(hits3), sts))
+    bad_cfg = type(cfg).from_buffer_copy(cfg)
+    bad_cfg.abstol = -1.0
+    lim_bad, hits_bad = np.full(2, -7.0), C.c_int64(-7)
+    assert L.gr_corona_trace_multi(arr, 3, C.byref(bad_cfg), C.byref(rs), C.byref(pf), lim_bad.ctypes.data, C.byref(hits_bad), sts) != 0
+    assert np.all(lim_bad == -7.0) and hits_bad.value == -7
+    multi = np.full((3, edges.size), -7.0)
+    assert L.gr_corona_bin_multi(arr, 3, edges.ctypes.data, edges.size, multi.ctypes.data) != 0
+    assert "there is none" in L.gr_last_error().decode() and np.all(multi == -7.0)
+    for k in range(3):          # ... on every context of the call, not on the one that failed alone
+        assert L.gr_corona_bin(three[k].ctx.handle, edges.ctypes.data, edges.size, multi.ctypes.data) != 0
+        assert "there is none" in L.gr_last_error().decode()
+    _lib.check(L.gr_corona_trace_multi(arr, 3, C.byref(cfg), C.byref(rs), C.byref(pf), lim3.ctypes.data, C.byref(hits3), sts))
+    assert hits3.value == hits.value and lim3.tobytes() == lim.tobytes()
+    assert sum(x.rays for x in sts) == n and all(x.rays > 0 and x.enqueue_ms > 0.0 for x in sts)
+    _lib.check(L.gr_corona_bin_multi(arr, 3, edges.ctypes.data, edges.size, multi.ctypes.data))
+    assert multi.tobytes() == one.tobytes()
+
+
+CORONA_ENQUEUE_SAMPLES = 300      # the smallest count probed (192, 300, 1000, 3001, ...) whose shares run 20 x the longest enqueue: DESIGN_measurements.md
+
+
+@pytest.mark.gpu
+def test_corona_enqueue_phase_does_not_wait_for_a_device(G, ens):
+    """gr_corona_trace_multi over three contexts queues every share before it waits for any: the host time each context's
+    enqueue took is a small fraction of the kernels' time (the bound of test_gpu_multi.py::
+    test_enqueue_phase_does_not_wait_for_a_device).  A copy to the host inside the enqueue loop that blocked would show as
+    enqueue_ms of a context about equal to its kernel_ms."""
+    from gradus_jl_amd import _lib
+
+    L = _lib.load()
+    cfg, rs, pf, keep = _lamp_post_abi(G, ens, CORONA_ENQUEUE_SAMPLES)
+    three = [G.EnsembleMI355X(0) for _ in range(3)]
+    arr, sts = _lib.ctx_array([e.ctx for e in three])
+    lim, hits = np.zeros(2), C.c_int64(0)
+    for rep in range(2):          # the first call allocates the buffers and loads code objects
+        _lib.check(L.gr_corona_trace_multi(arr, 3, C.byref(cfg), C.byref(rs), C.byref(pf), lim.ctypes.data, C.byref(hits), sts))
+    enq, ker, call = ([getattr(x, f) for x in sts] for f in ("enqueue_ms", "kernel_ms", "call_ms"))
+    print(f"  corona {CORONA_ENQUEUE_SAMPLES} samples: enqueue_ms {['%.3f' % e for e in enq]} kernel_ms {['%.2f' % q for q in ker]} "
+          f"call_ms {['%.2f' % q for q in call]}")
+    assert max(enq) < 0.1 * max(ker), (enq, ker)
+    assert sum(x.rays for x in sts) == CORONA_ENQUEUE_SAMPLES

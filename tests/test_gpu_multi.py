@@ -14,6 +14,7 @@ Two properties are asserted for every entry point of the boundary (src/tracing/t
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
@@ -262,6 +263,89 @@ def test_multi_argument_errors(G, ens, multi4):
     rs, keep = separable_rayset(m, X_FAR, plane, tiled=False)
     assert L.gr_rayset_endpoints_multi(arr, 2, C.byref(cfg), C.byref(rs), pts.ctypes.data, sts) == 0
     assert sum(s.rays for s in sts) == 256
+
+
+GOLDEN_TILED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rayset_endpoints_tiled_16x16.npy")
+
+
+def test_one_context_call_is_its_multi_form_on_one_context(G, ens, multi4):
+    """The one-context entry points ARE their *_multi forms with n = 1: the same bytes and the same counters from both, for
+    gr_ray_summary, gr_rayset_endpoints, gr_sky_cells and gr_plane_cells on 3001 rays / cells (no multiple of 64) and on a TILED
+    separable set -- which has no ray order to share out, so two contexts refuse it, and which one context takes as it is given:
+    its rows are the ones recorded before the two forms became one (tests/golden).  Only enqueue_ms tells the forms apart."""
+    import skycell_scene as S
+    from gradus_jl_amd import _lib
+    from gradus_jl_amd.rendering import abi_pointfunction
+    from gradus_jl_amd.tracing import lnr_momentum_to_global_velocity_matrix, separable_rayset
+
+    L = _lib.load()
+    h = ens.ctx.handle
+    one_ctx = (C.c_void_p * 1)(h)
+    m, config = _render_config(G, ens, 64, 64)
+    cfg = config.abi_config()
+    pf, keep_pf = abi_pointfunction(G.ConstPointFunctions.redshift(m, X_FAR))
+
+    def both(what, single, multi, out):
+        """single(out, stats) and multi(ctxs, 1, out, stats) -> the bytes both wrote"""
+        st, sts = _lib.gr_stats(), (_lib.gr_stats * 1)()
+        st.enqueue_ms = -1.0
+        a, b = np.full_like(out, 0xFF), np.full_like(out, 0xFF)
+        _lib.check(single(a.ctypes.data, C.byref(st)))
+        _lib.check(multi(one_ctx, 1, b.ctypes.data, sts))
+        assert a.tobytes() == b.tobytes(), what
+        for f in ("rays", "accepted_steps", "rejected_steps"):
+            assert getattr(st, f) == getattr(sts[0], f), (what, f)
+        assert list(st.status_count) == list(sts[0].status_count) and st.accepted_steps > 0, what
+        assert st.enqueue_ms == 0.0 and sts[0].enqueue_ms > 0.0, (what, st.enqueue_ms, sts[0].enqueue_ms)
+        assert st.kernel_ms > 0.0 and st.call_ms >= st.kernel_ms, what
+        return st, a
+
+    n = 3001
+    rng = np.random.default_rng(5)
+    al, be = np.ascontiguousarray(rng.uniform(-30, 30, n)), np.ascontiguousarray(rng.uniform(-20, 20, n))
+    rs = _lib.gr_rayset()
+    Mx = lnr_momentum_to_global_velocity_matrix(m, X_FAR)
+    for i in range(4):
+        rs.x_obs[i] = float(X_FAR[i])
+        for q in range(4):
+            rs.Mx[4 * i + q] = float(Mx[i, q])
+    rs.alpha, rs.beta, rs.n = al.ctypes.data, be.ctypes.data, n
+    plane = G.PolarPlane(G.GeometricGrid(), Nr=16, Nθ=16, r_min=1.0, r_max=40.0)
+    tiled, keep_tiled = separable_rayset(m, X_FAR, plane, tiled=True)
+    for what, q in (("arrays", rs), ("tiled", tiled)):
+        st, _ = both(f"gr_ray_summary {what}",
+                     lambda o, s: L.gr_ray_summary(h, C.byref(cfg), C.byref(q), C.byref(pf), o, s),
+                     lambda a, k, o, s: L.gr_ray_summary_multi(a, k, C.byref(cfg), C.byref(q), C.byref(pf), o, s),
+                     np.zeros(32 * q.n, dtype=np.uint8))
+        assert st.rays == q.n
+        st, pts = both(f"gr_rayset_endpoints {what}",
+                       lambda o, s: L.gr_rayset_endpoints(h, C.byref(cfg), C.byref(q), o, s),
+                       lambda a, k, o, s: L.gr_rayset_endpoints_multi(a, k, C.byref(cfg), C.byref(q), o, s),
+                       np.zeros(152 * q.n, dtype=np.uint8))
+        assert st.rays == q.n
+    assert (pts.view(_lib.POINT_DTYPE)["status"] == 2).sum() > 20
+    assert pts.tobytes() == np.load(GOLDEN_TILED).tobytes()
+    # ... and sharing the tiled set out is still refused
+    arr, sts = _ctxs(multi4, 2)
+    assert L.gr_rayset_endpoints_multi(arr, 2, C.byref(cfg), C.byref(tiled), pts.ctypes.data, sts) == -1
+    assert b"ray order" in L.gr_last_error()
+
+    # cells of a source's sky
+    su = S.setup(G, S.KERR, None, ensemble=ens)
+    cosθ, ϕ = np.ascontiguousarray(rng.uniform(-0.95, 0.95, n)), np.ascontiguousarray(rng.uniform(-math.pi, math.pi, n))
+    cells = S.skycells_struct(G, su, cosθ, ϕ)
+    st, _ = both("gr_sky_cells",
+                 lambda o, s: L.gr_sky_cells(h, C.byref(su["cfg"]), C.byref(cells), C.byref(su["pf"]), o, s),
+                 lambda a, k, o, s: L.gr_sky_cells_multi(a, k, C.byref(su["cfg"]), C.byref(cells), C.byref(su["pf"]), o, s),
+                 np.zeros(48 * n, dtype=np.uint8))
+    assert st.rays == n
+    # cells of an observer's plane
+    pl = config.abi_plane()
+    st, _ = both("gr_plane_cells",
+                 lambda o, s: L.gr_plane_cells(h, C.byref(cfg), C.byref(pl), al.ctypes.data, be.ctypes.data, n, o, s),
+                 lambda a, k, o, s: L.gr_plane_cells_multi(a, k, C.byref(cfg), C.byref(pl), al.ctypes.data, be.ctypes.data, n, o, s),
+                 np.zeros(152 * n, dtype=np.uint8))
+    assert st.rays == n
 
 
 @pytest.mark.parametrize("pinned", [False, True])
