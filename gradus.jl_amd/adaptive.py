@@ -927,7 +927,6 @@ def _make_emissivity_tracer(m, corona, d, *, ensemble=None, t_max=1_000_000.0, *
     for q in range(4):
         pf.u_src[q] = v_src[q]
     cfg = config.abi_config()
-    L = _lib.load()
     keep = {"config": config, "cfg": cfg, "pf": pf, "keep_pf": keep_pf, "ensemble": ens, "x_src": x_src, "v_src": v_src,
             "Mx": Mx, "launches": []}
 
@@ -941,13 +940,7 @@ def _make_emissivity_tracer(m, corona, d, *, ensemble=None, t_max=1_000_000.0, *
             cells.Mx[q] = val
         cells.cos_theta, cells.phi, cells.n = cosθ.ctypes.data, ϕ.ctypes.data, cosθ.size
         out = np.empty(cosθ.size, dtype=SKY_DTYPE)
-        if ens.multi:
-            ctx_arr, ctx_stats = _lib.ctx_array(ens.contexts)
-            _lib.check(L.gr_sky_cells_multi(ctx_arr, len(ens.contexts), C.byref(cfg), C.byref(cells), C.byref(pf), out.ctypes.data, ctx_stats))
-            st = _lib.merge_stats(ctx_stats)
-        else:
-            st = _lib.gr_stats()
-            _lib.check(L.gr_sky_cells(ens.ctx.handle, C.byref(cfg), C.byref(cells), C.byref(pf), out.ctypes.data, C.byref(st)))
+        st = ens.call("gr_sky_cells", C.byref(cfg), C.byref(cells), C.byref(pf), out.ctypes.data)
         keep["launches"].append((int(cosθ.size), float(st.call_ms)))
         return out
 
@@ -973,21 +966,12 @@ def _make_plane_tracer(m, x, d, *, ensemble=None, t_max=None, **solver_opts):
         plane.x_obs[q] = x[q]
     for q, val in enumerate(np.ascontiguousarray(lnr_momentum_to_global_velocity_matrix(m, x)).ravel()):
         plane.Mx[q] = val
-    L = _lib.load()
     keep = {"config": config, "cfg": cfg, "plane": plane, "ensemble": ens, "x_obs": x, "launches": []}
 
     def calc_values(α, β):
         α, β = np.ascontiguousarray(α, dtype=np.float64), np.ascontiguousarray(β, dtype=np.float64)
         out = np.zeros(α.size, dtype=_lib.POINT_DTYPE)
-        if ens.multi:
-            ctx_arr, ctx_stats = _lib.ctx_array(ens.contexts)
-            _lib.check(L.gr_plane_cells_multi(ctx_arr, len(ens.contexts), C.byref(cfg), C.byref(plane), α.ctypes.data, β.ctypes.data, α.size,
-                                              out.ctypes.data, ctx_stats))
-            st = _lib.merge_stats(ctx_stats)
-        else:
-            st = _lib.gr_stats()
-            _lib.check(L.gr_plane_cells(ens.ctx.handle, C.byref(cfg), C.byref(plane), α.ctypes.data, β.ctypes.data, α.size, out.ctypes.data,
-                                        C.byref(st)))
+        st = ens.call("gr_plane_cells", C.byref(cfg), C.byref(plane), α.ctypes.data, β.ctypes.data, α.size, out.ctypes.data)
         keep["launches"].append((int(α.size), float(st.call_ms)))
         return out
 

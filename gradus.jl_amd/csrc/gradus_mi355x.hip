@@ -216,7 +216,7 @@ struct gr_ctx {
     hipStream_t tables_stream = nullptr;
     bool tables_busy = false;
     // host-buffer entry points that return 152 B per ray: the result goes back in bands on a second stream while later
-    // bands are still being traced (see copy_back_in_bands)
+    // bands are still being traced (see Bands)
     hipStream_t copy_stream = nullptr;
     hipStream_t band_stream = nullptr;     // odd bands are traced here, even ones on `stream`: the tail of one band's launch
                                            // (SIMDs draining) overlaps the head of the next
@@ -225,7 +225,6 @@ struct gr_ctx {
     bool lpt_suspend = false;              // banded launches do not learn / use a tile order (their ranges differ)
     int64_t pipeline = 4;                  // bands of the end-point return (0 / 1: one launch + one copy)
     bool counted = false;                  // this context is in g_live_ctx
-    bool multi_direct = false;             // *_multi: this context's kernel stores into the caller's pinned block itself (no copy in phase 2)
 };
 
 namespace {
@@ -2071,27 +2070,16 @@ int32_t gr_rayset_endpoints_device(gr_ctx* ctx, const gr_config* cfg, const gr_r
 
 // ---- host-buffer variants: stage through the context, block until done ----
 
-// Touch every page of an output buffer from a few threads (its content is about to be overwritten).  A freshly
-// allocated destination -- numpy's `empty`, Julia's `Vector{GeodesicPoint}(undef, n)` -- is not backed by pages yet, and
-// taking those faults inside the device-to-host copy costs as much again as the copy (637 MB of end points at 2048²:
-// 35 ms into touched memory, 60 ms into fresh memory); taken here they overlap the kernel that is already running.
-static void prefault_output(void* dst, size_t bytes, bool huge)
+namespace {
+// first touch of every page of a buffer from up to 8 threads (its content is about to be overwritten)
+void prefault_threads(char* base, size_t bytes)
 {
-    if (bytes < ((size_t)64 << 20)) return;
-    if (huge) {   // ask for transparent huge pages on the 2 MB-aligned interior: 300 faults instead of 155 000 for 637 MB
-        // (measured on the GPU box, THP mode "madvise": 10.7 ms instead of 27-64 ms with 8 threads; errors are ignored;
-        // gr_ctx_set(ctx, "hugepages", 0) leaves the caller's mapping alone)
-        const size_t two = (size_t)2 << 20;
-        const size_t a0 = ((size_t)dst + two - 1) / two * two, a1 = ((size_t)dst + bytes) / two * two;
-        if (a1 > a0) (void)madvise((void*)a0, a1 - a0, MADV_HUGEPAGE);
-    }
     unsigned nt = std::thread::hardware_concurrency();
     nt = nt == 0 ? 4 : (nt > 8 ? 8 : nt);
     const size_t page = 4096;
-    char* base = (char*)dst;
     std::vector<std::thread> th;
     // thread creation can throw (std::system_error: out of threads) and nothing may unwind through the C ABI: pre-faulting
-    // is an optimisation, so whatever threads exist do their stripes and the copy faults the rest in itself
+    // is an optimisation, so whatever threads exist do their stripes and the copy (or the registration) faults the rest in itself
     try {
         th.reserve(nt);
         for (unsigned t = 0; t < nt; ++t)
@@ -2103,23 +2091,22 @@ static void prefault_output(void* dst, size_t bytes, bool huge)
     }
     for (auto& x : th) x.join();
 }
-namespace {
-void prefault_threads(char* base, size_t bytes)
-{
-    unsigned nt = std::thread::hardware_concurrency();
-    nt = nt == 0 ? 4 : (nt > 8 ? 8 : nt);
-    const size_t page = 4096;
-    std::vector<std::thread> th;
-    try {       // nothing may unwind through the C ABI: whatever threads exist do their stripes, the registration faults in the rest
-        th.reserve(nt);
-        for (unsigned t = 0; t < nt; ++t)
-            th.emplace_back([=]() {
-                for (size_t off = (size_t)t * page; off < bytes; off += (size_t)nt * page) ((volatile char*)base)[off] = 0;
-            });
-    } catch (...) {
-    }
-    for (auto& x : th) x.join();
 }
+// Touch every page of an output buffer (from 64 MB up).  A freshly allocated destination -- numpy's `empty`, Julia's
+// `Vector{GeodesicPoint}(undef, n)` -- is not backed by pages yet, and taking those faults inside the device-to-host copy
+// costs as much again as the copy (637 MB of end points at 2048²: 35 ms into touched memory, 60 ms into fresh memory); taken
+// here they overlap the kernel that is already running.
+static void prefault_output(void* dst, size_t bytes, bool huge)
+{
+    if (bytes < ((size_t)64 << 20)) return;
+    if (huge) {   // ask for transparent huge pages on the 2 MB-aligned interior: 300 faults instead of 155 000 for 637 MB
+        // (measured on the GPU box, THP mode "madvise": 10.7 ms instead of 27-64 ms with 8 threads; errors are ignored;
+        // gr_ctx_set(ctx, "hugepages", 0) leaves the caller's mapping alone)
+        const size_t two = (size_t)2 << 20;
+        const size_t a0 = ((size_t)dst + two - 1) / two * two, a1 = ((size_t)dst + bytes) / two * two;
+        if (a1 > a0) (void)madvise((void*)a0, a1 - a0, MADV_HUGEPAGE);
+    }
+    prefault_threads((char*)dst, bytes);
 }
 struct BackgroundPrefault {
     static constexpr unsigned kMax = 8;
@@ -2236,34 +2223,6 @@ static bool plane_on_lane_kernel(gr_ctx* ctx, const gr_config* cfg, const gr_pla
     return resolve_kernel(ctx, range->count, cd, cfg->metric_id) == 0;
 }
 
-int32_t gr_render(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const gr_pointfunction* pf,
-                  const gr_range* range, double* image, gr_stats* stats)
-{
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (!range) return fail(GR_ERR_INVALID_ARGUMENT, "range is null");
-    if (!image && range->count > 0) return fail(GR_ERR_INVALID_ARGUMENT, "image is null");
-    GR_HIP(hipSetDevice(ctx->device));      // before any allocation: ensure() mallocs on the current device
-    int32_t rc;
-    const size_t bytes = sizeof(double) * (size_t)(range->count > 0 ? range->count : 0);
-    // an image in a block the library pinned is written by the kernel itself (as gr_render_endpoints does): no D2H copy
-    if (ctx->direct_host && bytes && is_pinned(image, bytes) && plane_on_lane_kernel(ctx, cfg, plane, range, 0)) {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, image, 0) == hipSuccess && dp) {
-            if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-            if ((rc = gr_render_device(ctx, cfg, plane, pf, range, (double*)dp,
-                                       stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream)) != GR_OK) return rc;
-            return end_host_call(ctx, stats);
-        }
-        (void)hipGetLastError();
-    }
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if ((rc = gr_render_device(ctx, cfg, plane, pf, range, (double*)ctx->d_scratch,
-                               stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream)) != GR_OK) return rc;
-    if (bytes) GR_HIP(hipMemcpyAsync(image, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return end_host_call(ctx, stats);
-}
-
 // ---------------------------------------------------------------------------------------
 // ONE host thread, SEVERAL devices (include/gradus_mi355x.h, "*_multi"): enqueue on every context, queue the copies home,
 // wait for all.
@@ -2287,6 +2246,17 @@ int32_t validate_ctxs(gr_ctx* const* ctxs, int32_t n)
     return GR_OK;
 }
 
+// Wait for everything a host call may have queued on a context -- its stream and, once a banded return has made them, the two
+// streams beside it: nothing may be in flight, reading or writing the caller's buffers, when a failed call returns.  Errors are
+// ignored and the message of the failure that brought us here is left alone (nothing below sets one).
+void drain(gr_ctx* ctx)
+{
+    (void)hipSetDevice(ctx->device);
+    if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
+    if (ctx->band_stream) (void)hipStreamSynchronize(ctx->band_stream);
+    (void)hipStreamSynchronize(ctx->stream);
+}
+
 // The one path of a host call that has a *_multi form: the one-context entry point is the same implementation on `&ctx, 1`.
 // enq(k): stage and launch context k's share (begins with begin_host_call, before it stages: kernel_ms / call_ms count the
 // staging); copy(k): queue its copy home -- no enq queues a copy to the host, so every share is queued before any is waited for.
@@ -2306,18 +2276,8 @@ int32_t multi_drive(gr_ctx* const* ctxs, int32_t n, gr_stats* stats, Enqueue enq
     for (int k = 0; k < n && rc == GR_OK; ++k) rc = copy(k);
     for (int k = 0; k < started; ++k) {
         gr_stats* st = stats ? &stats[k] : nullptr;
-        int32_t e;
-        if (rc == GR_OK) {
-            e = end_host_call(ctxs[k], st);
-        } else {
-            // an earlier failure: keep its message, just make sure nothing of this call is still in flight
-            const std::string keep = g_last_error;
-            (void)hipSetDevice(ctxs[k]->device);
-            (void)hipStreamSynchronize(ctxs[k]->stream);
-            g_last_error = keep;
-            e = GR_OK;
-        }
-        if (rc == GR_OK) rc = e;
+        if (rc == GR_OK) rc = end_host_call(ctxs[k], st);
+        else drain(ctxs[k]);      // an earlier failure: its message stands
         if (st && rc == GR_OK) st->enqueue_ms = k < 64 ? t_enq[k] : 0.0;
     }
     return rc;
@@ -2368,6 +2328,168 @@ void contiguous_share(int64_t n_rays, int32_t n, int k, int64_t* off, int64_t* c
 }  // namespace
 }  // extern "C++"
 
+// ---- the image plane: gr_render, gr_render_endpoints and their *_multi forms are one implementation ----
+extern "C++" {
+namespace {
+// banded launches do not learn / use a tile order (their ranges differ)
+struct LptSuspend {
+    gr_ctx* ctx;
+    explicit LptSuspend(gr_ctx* c) : ctx(c) { ctx->lpt_suspend = true; }
+    ~LptSuspend() { ctx->lpt_suspend = false; }
+    LptSuspend(const LptSuspend&) = delete;
+    LptSuspend& operator=(const LptSuspend&) = delete;
+};
+
+// ONE context returns the end points of a contiguous range of a large plane in bands of whole 8-column tile strips: band k is
+// copied back on a second stream while bands k+1.. are traced (2048²: 20 ms of kernel + 15 ms of copy become 25 ms), and the
+// destination's pages are faulted in by helper threads meanwhile.  It is one context's enqueue and copy strategy and is not
+// offered to several: whether bands help when several devices share a link has never been measured (the test box has one).
+struct Bands {
+    int64_t j0[9];      // band k is rays j0[k] ... j0[k + 1] of the range
+    int used = 0;       // 0: the range goes out in one launch and one copy
+
+    // the launches, on two streams; begin_host_call has run
+    int32_t enqueue(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const gr_range* range, int nb, int64_t unit, gr_stats* d_stats)
+    {
+        int32_t rc;
+        if ((rc = ensure_copy_stream(ctx)) != GR_OK) return rc;
+        // equal bands except the last, which is half a band: its copy is the only one nothing overlaps
+        const int64_t per = ((2 * range->count / (2 * nb - 1) + unit - 1) / unit) * unit;
+        for (int64_t j = 0; j < range->count && used < 8; j += per) j0[used++] = j;
+        j0[used] = range->count;
+        {
+            LptSuspend no_tile_order(ctx);
+            // Bands alternate between two streams: a launch ends when its slowest wave does, and on ONE stream the next band would
+            // only start then (four bands: 22.5 ms of kernels against 19.6 ms for the plane in one launch).  Side by side the next
+            // band's waves fill the SIMDs the draining one leaves idle.  The second stream starts behind the call's begin marker
+            // (the statistics counters are zeroed on the first).
+            GR_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+            GR_HIP(hipStreamWaitEvent(ctx->band_stream, ctx->ev_fork, 0));
+            for (int k = 0; k < used; ++k) {
+                hipStream_t s = (k & 1) ? ctx->band_stream : ctx->stream;
+                const gr_range band{ range->first + j0[k], j0[k + 1] - j0[k], j0[k + 1] - j0[k], 1 };
+                if ((rc = gr_render_endpoints_device(ctx, cfg, plane, &band, (gr_point*)ctx->d_scratch + j0[k], d_stats, s)) != GR_OK) return rc;
+                GR_HIP(hipEventRecord(ctx->ev_band[k], s));
+            }
+        }
+        // join: everything the second stream did is ordered before the call's end marker on the first
+        if (used > 1) GR_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_band[(used - 1) & 1 ? used - 1 : used - 2], 0));
+        GR_HIP(hipEventRecord(ctx->ev_k, ctx->stream));
+        return GR_OK;
+    }
+
+    // the copies, each behind its band, on a third stream; all of them have landed when this returns
+    int32_t copy(gr_ctx* ctx, gr_point* points, bool pinned) const
+    {
+        BackgroundPrefault pf;
+        if (!pinned) pf.start(points, sizeof(gr_point) * (size_t)j0[used], ctx->hugepages != 0);
+        for (int k = 0; k < used; ++k) {
+            pf.wait_until(sizeof(gr_point) * (size_t)j0[k + 1]);
+            GR_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_band[k], 0));
+            GR_HIP(hipMemcpyAsync(points + j0[k], (gr_point*)ctx->d_scratch + j0[k], sizeof(gr_point) * (size_t)(j0[k + 1] - j0[k]),
+                                  hipMemcpyDeviceToHost, ctx->copy_stream));
+        }
+        GR_HIP(hipStreamSynchronize(ctx->copy_stream));
+        return GR_OK;
+    }
+};
+
+// One row per ray of an image plane -- a pixel (out_mode 0, 8 bytes) or an end-point record (out_mode 1, 152 bytes) -- for one
+// context or several.  Context k traces `first` moved on by k * step rays.
+//   dealt = false (the one-context calls): `out` holds the rows of the range alone, in the range's order, and they go home with
+//           one contiguous copy -- or, end points of a large contiguous range, in Bands;
+//   dealt = true (the *_multi calls): `out` is the whole plane, context k's blocks go to their places in it with one 2-D copy.
+// Into a block the library pinned (gr_host_alloc) the kernels store the rows themselves: no staging copy in HBM, no copy engine,
+// nothing for the host to wait on but the kernels.  The wave-transposed stores of records (points_epilogue, hence lds_points)
+// cross the link as full-size packets -- 637 MB spread over the 20 ms of the 2048² trace is about half the link's rate.  A dealt
+// kernel then addresses the plane globally (out_global).
+int32_t plane_rows(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_plane* plane, const gr_pointfunction* pf,
+                   const gr_range& first, int64_t step, bool dealt, int out_mode, void* out, gr_stats* stats)
+{
+    const bool records = out_mode == 1;
+    const size_t row = records ? sizeof(gr_point) : sizeof(double);
+    const int64_t count = first.count > 0 ? first.count : 0;
+    const size_t bytes = row * (size_t)count;                                                 // of one context's rows
+    const size_t extent = dealt ? row * (size_t)(plane->width * plane->height) : bytes;       // of the caller's buffer
+    auto range_of = [&](int k) {
+        gr_range rg = first;
+        rg.first += (int64_t)k * step;
+        return rg;
+    };
+    const bool pinned = is_pinned(out, extent);
+    // the direct route is all contexts' or none's: only waves of the lane kernel store whole runs (plane_on_lane_kernel)
+    bool direct = pinned && extent;
+    for (int k = 0; k < n && direct; ++k) {
+        const gr_range rg = range_of(k);
+        direct = ctxs[k]->direct_host && (!records || ctxs[k]->lds_points) && plane_on_lane_kernel(ctxs[k], cfg, plane, &rg, out_mode);
+    }
+    int nb = 1;
+    const int64_t unit = plane ? 8 * plane->height : 0;
+    if (n == 1 && !dealt && records && unit > 0 && first.first % unit == 0 && (first.stride_blocks == 1 || first.count <= first.block))
+        nb = band_count(ctxs[0], first.count, unit, pinned);
+    Bands bands;
+    bool global[64] = {};      // context k's kernel stores into the caller's block itself: nothing of its to copy
+    auto enq = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        int32_t r;
+        GR_HIP(hipSetDevice(c->device));      // before any allocation: ensure() mallocs on the current device
+        void* dst = direct ? pinned_device_pointer(out) : nullptr;
+        global[k] = dst != nullptr;
+        if (!dst) {      // only the staged routes need the copy of the rows in HBM (637 MB of records at 2048²)
+            if ((r = ensure(&c->d_scratch, &c->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return r;
+            dst = c->d_scratch;
+        }
+        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
+        const gr_range rg = range_of(k);
+        gr_stats* d_stats = stats ? (gr_stats*)c->d_stats : nullptr;
+        if (!global[k] && nb > 1) return bands.enqueue(c, cfg, plane, &rg, nb, unit, d_stats);
+        return records ? render_endpoints_device_impl(c, cfg, plane, &rg, (gr_point*)dst, d_stats, c->stream, global[k] && dealt)
+                       : render_device_impl(c, cfg, plane, pf, &rg, (double*)dst, d_stats, c->stream, global[k] && dealt);
+    };
+    bool faulted = false;
+    auto copy = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        if (global[k] || count == 0) return GR_OK;
+        GR_HIP(hipSetDevice(c->device));
+        if (bands.used) return bands.copy(c, (gr_point*)out, pinned);
+        // every kernel is running by now: the pages of a fresh pageable destination are faulted in under them, once
+        if (records && !faulted && !pinned) prefault_output(out, extent, c->hugepages != 0);
+        faulted = true;
+        if (!dealt) {
+            GR_HIP(hipMemcpyAsync(out, c->d_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            // local block b of context k is block b * n + k of the plane: one 2-D copy places all of them
+            const gr_range rg = range_of(k);
+            GR_HIP(hipMemcpy2DAsync((char*)out + row * (size_t)rg.first, row * (size_t)(rg.stride_blocks * rg.block), c->d_scratch,
+                                    row * (size_t)rg.block, row * (size_t)rg.block, (size_t)(rg.count / rg.block),
+                                    hipMemcpyDeviceToHost, c->stream));
+        }
+        return GR_OK;
+    };
+    return multi_drive(ctxs, n, stats, enq, copy);
+}
+
+// the *_multi forms: the block-cyclic deal of the plane's columns
+int32_t plane_rows_dealt(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_plane* plane, const gr_pointfunction* pf,
+                         int64_t block_cols, int out_mode, void* out, gr_stats* stats)
+{
+    int32_t rc;
+    int64_t block, n_blocks, count;
+    if ((rc = plane_deal(plane, n, block_cols, &block, &n_blocks, &count)) != GR_OK) return rc;
+    return plane_rows(ctxs, n, cfg, plane, pf, gr_range{ 0, count, block, (int64_t)n }, block, true, out_mode, out, stats);
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t gr_render(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const gr_pointfunction* pf,
+                  const gr_range* range, double* image, gr_stats* stats)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!range) return fail(GR_ERR_INVALID_ARGUMENT, "range is null");
+    if (!image && range->count > 0) return fail(GR_ERR_INVALID_ARGUMENT, "image is null");
+    return one_context(plane_rows(&ctx, 1, cfg, plane, pf, *range, 0, false, 0, image, stats), stats);
+}
+
 int32_t gr_render_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_plane* plane,
                         const gr_pointfunction* pf, int64_t block_cols, double* image, gr_stats* stats)
 {
@@ -2375,43 +2497,16 @@ int32_t gr_render_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, co
     if ((rc = validate_ctxs(ctxs, n)) != GR_OK) return rc;
     if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
     if (!image) return fail(GR_ERR_INVALID_ARGUMENT, "image is null");
-    int64_t block, n_blocks, count;
-    if ((rc = plane_deal(plane, n, block_cols, &block, &n_blocks, &count)) != GR_OK) return rc;
-    const size_t bytes = sizeof(double) * (size_t)count;
-    // An image in a block the library pinned: every device's kernel stores its pixels at their final place, across the link
-    // (what gr_render does for one device) -- no staging image, no copy, nothing for the host to wait on but the kernels.
-    bool direct = is_pinned(image, sizeof(double) * (size_t)(plane->width * plane->height));
-    for (int k = 0; k < n && direct; ++k) {
-        const gr_range rg{ (int64_t)k * block, count, block, (int64_t)n };
-        direct = ctxs[k]->direct_host && plane_on_lane_kernel(ctxs[k], cfg, plane, &rg, 0);
-    }
-    auto enq = [&](int k) -> int32_t {
-        gr_ctx* c = ctxs[k];
-        int32_t r;
-        GR_HIP(hipSetDevice(c->device));      // context k's scratch image must live on device k
-        double* dst = nullptr;
-        if (direct) dst = (double*)pinned_device_pointer(image);
-        const bool global = dst != nullptr;
-        if (!global) {
-            if ((r = ensure(&c->d_scratch, &c->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return r;
-            dst = (double*)c->d_scratch;
-        }
-        c->multi_direct = global;
-        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
-        const gr_range rg{ (int64_t)k * block, count, block, (int64_t)n };
-        return render_device_impl(c, cfg, plane, pf, &rg, dst, stats ? (gr_stats*)c->d_stats : nullptr, c->stream, global);
-    };
-    auto copy = [&](int k) -> int32_t {
-        gr_ctx* c = ctxs[k];
-        if (c->multi_direct || count == 0) return GR_OK;
-        GR_HIP(hipSetDevice(c->device));
-        // local block b of context k is image block b*n + k: one 2-D copy places all of them
-        GR_HIP(hipMemcpy2DAsync(image + (size_t)k * block, sizeof(double) * (size_t)(n * block), c->d_scratch,
-                                sizeof(double) * (size_t)block, sizeof(double) * (size_t)block, (size_t)n_blocks,
-                                hipMemcpyDeviceToHost, c->stream));
-        return GR_OK;
-    };
-    return multi_drive(ctxs, n, stats, enq, copy);
+    return plane_rows_dealt(ctxs, n, cfg, plane, pf, block_cols, 0, image, stats);
+}
+
+int32_t gr_render_endpoints(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const gr_range* range,
+                            gr_point* points, gr_stats* stats)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!range) return fail(GR_ERR_INVALID_ARGUMENT, "range is null");
+    if (!points && range->count > 0) return fail(GR_ERR_INVALID_ARGUMENT, "points is null");
+    return one_context(plane_rows(&ctx, 1, cfg, plane, nullptr, *range, 0, false, 1, points, stats), stats);
 }
 
 int32_t gr_render_endpoints_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_plane* plane,
@@ -2421,146 +2516,26 @@ int32_t gr_render_endpoints_multi(gr_ctx* const* ctxs, int32_t n, const gr_confi
     if ((rc = validate_ctxs(ctxs, n)) != GR_OK) return rc;
     if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
     if (!points) return fail(GR_ERR_INVALID_ARGUMENT, "points is null");
-    int64_t block, n_blocks, count;
-    if ((rc = plane_deal(plane, n, block_cols, &block, &n_blocks, &count)) != GR_OK) return rc;
-    const size_t bytes = sizeof(gr_point) * (size_t)count;
-    const size_t total = sizeof(gr_point) * (size_t)(plane->width * plane->height);
-    bool direct = is_pinned(points, total);
-    for (int k = 0; k < n && direct; ++k) {
-        const gr_range rg{ (int64_t)k * block, count, block, (int64_t)n };
-        direct = ctxs[k]->direct_host && ctxs[k]->lds_points && plane_on_lane_kernel(ctxs[k], cfg, plane, &rg, 1);
-    }
-    const bool pinned = direct || is_pinned(points, total);
-    auto enq = [&](int k) -> int32_t {
-        gr_ctx* c = ctxs[k];
-        int32_t r;
-        GR_HIP(hipSetDevice(c->device));
-        gr_point* dst = nullptr;
-        if (direct) dst = (gr_point*)pinned_device_pointer(points);
-        const bool global = dst != nullptr;
-        if (!global) {
-            if ((r = ensure(&c->d_scratch, &c->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return r;
-            dst = (gr_point*)c->d_scratch;
-        }
-        c->multi_direct = global;
-        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
-        const gr_range rg{ (int64_t)k * block, count, block, (int64_t)n };
-        return render_endpoints_device_impl(c, cfg, plane, &rg, dst, stats ? (gr_stats*)c->d_stats : nullptr, c->stream, global);
-    };
-    bool faulted = false;
-    auto copy = [&](int k) -> int32_t {
-        gr_ctx* c = ctxs[k];
-        if (c->multi_direct || count == 0) return GR_OK;
-        // every kernel is running by now: the pages of a fresh pageable destination are faulted in under them, once
-        if (!faulted && !pinned) prefault_output(points, total, c->hugepages != 0);
-        faulted = true;
-        GR_HIP(hipSetDevice(c->device));
-        GR_HIP(hipMemcpy2DAsync(points + (size_t)k * block, sizeof(gr_point) * (size_t)(n * block), c->d_scratch,
-                                sizeof(gr_point) * (size_t)block, sizeof(gr_point) * (size_t)block, (size_t)n_blocks,
-                                hipMemcpyDeviceToHost, c->stream));
-        return GR_OK;
-    };
-    return multi_drive(ctxs, n, stats, enq, copy);
+    return plane_rows_dealt(ctxs, n, cfg, plane, nullptr, block_cols, 1, points, stats);
 }
 
-int32_t gr_render_endpoints(gr_ctx* ctx, const gr_config* cfg, const gr_plane* plane, const gr_range* range,
-                            gr_point* points, gr_stats* stats)
+// n items in, n doubles out on one context: stage the items, `launch(d_in, d_out)`, copy the doubles home, wait
+extern "C++" {
+template <class Launch>
+static int32_t items_to_doubles(gr_ctx* ctx, const void* in, size_t item_bytes, int64_t n, double* out, Launch launch)
 {
-    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (!range) return fail(GR_ERR_INVALID_ARGUMENT, "range is null");
-    if (!points && range->count > 0) return fail(GR_ERR_INVALID_ARGUMENT, "points is null");
-    GR_HIP(hipSetDevice(ctx->device));      // before any allocation: ensure() mallocs on the current device
     int32_t rc;
-    const size_t bytes = sizeof(gr_point) * (size_t)(range->count > 0 ? range->count : 0);
-    // A contiguous range of a large plane goes out in bands of whole 8-column tile strips: band k is copied back on a
-    // second stream while bands k+1.. are traced (2048²: 20 ms of kernel + 15 ms of copy become 25 ms), and the
-    // destination's pages are faulted in by helper threads meanwhile.
-    // Into a block the library pinned (gr_host_alloc) the kernel stores the records itself: one launch, no staging copy in
-    // HBM, no copy engine.  The wave-transposed stores (points_epilogue) cross the link as full-size packets, 637 MB spread
-    // over the 20 ms of the 2048² trace is about half the link's rate, and the call ends when the kernel does.
-    if (ctx->direct_host && ctx->lds_points && bytes && is_pinned(points, bytes) && plane_on_lane_kernel(ctx, cfg, plane, range, 1)) {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, points, 0) == hipSuccess && dp) {
-            if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-            if ((rc = gr_render_endpoints_device(ctx, cfg, plane, range, (gr_point*)dp,
-                                                 stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream)) != GR_OK) return rc;
-            return end_host_call(ctx, stats);
-        }
-        (void)hipGetLastError();
-    }
-    // only the staged routes need the copy of the records in HBM (637 MB at 2048²)
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    const bool contiguous = plane && (range->stride_blocks == 1 || range->count <= range->block);
-    const int64_t unit = plane ? 8 * plane->height : 0;
-    const int nb = (contiguous && unit > 0 && range->first % unit == 0) ? band_count(ctx, range->count, unit, is_pinned(points, bytes)) : 1;
-    if ((rc = begin_host_call(ctx, stats)) != GR_OK) return rc;
-    if (nb <= 1) {
-        if ((rc = gr_render_endpoints_device(ctx, cfg, plane, range, (gr_point*)ctx->d_scratch,
-                                             stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream)) != GR_OK) return rc;
-        if (!is_pinned(points, bytes)) prefault_output(points, bytes, ctx->hugepages != 0);
-        if (bytes) GR_HIP(hipMemcpyAsync(points, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        return end_host_call(ctx, stats);
-    }
-    if ((rc = ensure_copy_stream(ctx)) != GR_OK) return rc;
-    // equal bands except the last, which is half a band: its copy is the only one nothing overlaps
-    const int64_t per = ((2 * range->count / (2 * nb - 1) + unit - 1) / unit) * unit;
-    int64_t j0[9];
-    int used = 0;
-    for (int64_t j = 0; j < range->count && used < 8; j += per) j0[used++] = j;
-    j0[used] = range->count;
-    ctx->lpt_suspend = true;
-    // Bands alternate between two streams: a launch ends when its slowest wave does, and on ONE stream the next band would
-    // only start then (four bands: 22.5 ms of kernels against 19.6 ms for the plane in one launch).  Side by side the next
-    // band's waves fill the SIMDs the draining one leaves idle.  The second stream starts behind the call's begin marker
-    // (the statistics counters are zeroed on the first).
-    hipError_t fe = hipEventRecord(ctx->ev_fork, ctx->stream);
-    if (fe == hipSuccess) fe = hipStreamWaitEvent(ctx->band_stream, ctx->ev_fork, 0);
-    if (fe != hipSuccess) { ctx->lpt_suspend = false; return fail(GR_ERR_HIP, std::string("band stream fork: ") + hipGetErrorString(fe)); }
-    for (int k = 0; k < used && rc == GR_OK; ++k) {
-        hipStream_t s = (k & 1) ? ctx->band_stream : ctx->stream;
-        const gr_range band{ range->first + j0[k], j0[k + 1] - j0[k], j0[k + 1] - j0[k], 1 };
-        rc = gr_render_endpoints_device(ctx, cfg, plane, &band, (gr_point*)ctx->d_scratch + j0[k],
-                                        stats ? (gr_stats*)ctx->d_stats : nullptr, s);
-        if (rc == GR_OK && hipEventRecord(ctx->ev_band[k], s) != hipSuccess) rc = fail(GR_ERR_HIP, "hipEventRecord failed");
-    }
-    ctx->lpt_suspend = false;
-    // join: everything the second stream did is ordered before the call's end marker on the first
-    if (used > 1 && rc == GR_OK) {
-        const int last_odd = (used - 1) & 1 ? used - 1 : used - 2;
-        if (hipStreamWaitEvent(ctx->stream, ctx->ev_band[last_odd], 0) != hipSuccess) rc = fail(GR_ERR_HIP, "hipStreamWaitEvent failed");
-    }
-    if (rc == GR_OK && hipEventRecord(ctx->ev_k, ctx->stream) != hipSuccess) rc = fail(GR_ERR_HIP, "hipEventRecord failed");
-    if (rc != GR_OK) { (void)hipStreamSynchronize(ctx->band_stream); (void)hipStreamSynchronize(ctx->stream); return rc; }
-    BackgroundPrefault pf;
-    if (!is_pinned(points, bytes)) pf.start(points, bytes, ctx->hugepages != 0);
-    hipError_t ce = hipSuccess;
-    const char* what = "";
-    for (int k = 0; k < used && ce == hipSuccess; ++k) {
-        pf.wait_until(sizeof(gr_point) * (size_t)j0[k + 1]);
-        ce = hipStreamWaitEvent(ctx->copy_stream, ctx->ev_band[k], 0);
-        what = "hipStreamWaitEvent";
-        if (ce != hipSuccess) break;
-        ce = hipMemcpyAsync(points + j0[k], (gr_point*)ctx->d_scratch + j0[k], sizeof(gr_point) * (size_t)(j0[k + 1] - j0[k]),
-                            hipMemcpyDeviceToHost, ctx->copy_stream);
-        what = "hipMemcpyAsync (band)";
-    }
-    if (ce != hipSuccess) {
-        // bands already queued are still writing into the caller's memory: nothing may be in flight when the call returns
-        (void)hipStreamSynchronize(ctx->copy_stream);
-        (void)hipStreamSynchronize(ctx->band_stream);
-        (void)hipStreamSynchronize(ctx->stream);
-        return fail(GR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(ce));
-    }
-    {
-        const hipError_t se = hipStreamSynchronize(ctx->copy_stream);
-        if (se != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->band_stream);
-            (void)hipStreamSynchronize(ctx->stream);
-            return fail(GR_ERR_HIP, std::string("hipStreamSynchronize(copy_stream): ") + hipGetErrorString(se));
-        }
-    }
-    return end_host_call(ctx, stats);
+    const size_t in_bytes = item_bytes * (size_t)n, out_bytes = sizeof(double) * (size_t)n;
+    GR_HIP(hipSetDevice(ctx->device));      // before any allocation: ensure() mallocs on the current device
+    if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, in_bytes ? in_bytes : 8)) != GR_OK) return rc;
+    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, out_bytes ? out_bytes : 8)) != GR_OK) return rc;
+    if (n > 0) GR_HIP(hipMemcpyAsync(ctx->d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = launch(ctx->d_in, (double*)ctx->d_scratch)) != GR_OK) return rc;
+    if (n > 0) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    GR_HIP(hipStreamSynchronize(ctx->stream));
+    return GR_OK;
 }
+}  // extern "C++"
 
 int32_t gr_apply_pointfunction(gr_ctx* ctx, const gr_config* cfg, const gr_pointfunction* pf, const gr_point* points,
                                int64_t n, double max_time, double* out)
@@ -2568,17 +2543,9 @@ int32_t gr_apply_pointfunction(gr_ctx* ctx, const gr_config* cfg, const gr_point
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "n must be non-negative");
     if (n > 0 && (!points || !out)) return fail(GR_ERR_INVALID_ARGUMENT, "points/out is null");
-    int32_t rc;
-    const size_t in_bytes = sizeof(gr_point) * (size_t)n, out_bytes = sizeof(double) * (size_t)n;
-    GR_HIP(hipSetDevice(ctx->device));      // before any allocation: ensure() mallocs on the current device
-    if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, in_bytes ? in_bytes : 8)) != GR_OK) return rc;
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, out_bytes ? out_bytes : 8)) != GR_OK) return rc;
-    if (n > 0) GR_HIP(hipMemcpyAsync(ctx->d_in, points, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = gr_apply_pointfunction_device(ctx, cfg, pf, (const gr_point*)ctx->d_in, n, max_time,
-                                            (double*)ctx->d_scratch, ctx->stream)) != GR_OK) return rc;
-    if (n > 0) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    GR_HIP(hipStreamSynchronize(ctx->stream));
-    return GR_OK;
+    return items_to_doubles(ctx, points, sizeof(gr_point), n, out, [&](const void* d_in, double* d_out) {
+        return gr_apply_pointfunction_device(ctx, cfg, pf, (const gr_point*)d_in, n, max_time, d_out, ctx->stream);
+    });
 }
 
 int32_t gr_disc_area_factor(gr_ctx* ctx, const gr_config* cfg, const gr_pointfunction* pf, const double* r, int64_t n, double* out)
@@ -2586,16 +2553,9 @@ int32_t gr_disc_area_factor(gr_ctx* ctx, const gr_config* cfg, const gr_pointfun
     if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
     if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "n must be non-negative");
     if (n > 0 && (!r || !out)) return fail(GR_ERR_INVALID_ARGUMENT, "r/out is null");
-    int32_t rc;
-    const size_t bytes = sizeof(double) * (size_t)n;
-    GR_HIP(hipSetDevice(ctx->device));
-    if ((rc = ensure(&ctx->d_in, &ctx->in_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    if ((rc = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return rc;
-    if (n > 0) GR_HIP(hipMemcpyAsync(ctx->d_in, r, bytes, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = gr_disc_area_factor_device(ctx, cfg, pf, (const double*)ctx->d_in, n, (double*)ctx->d_scratch, ctx->stream)) != GR_OK) return rc;
-    if (n > 0) GR_HIP(hipMemcpyAsync(out, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    GR_HIP(hipStreamSynchronize(ctx->stream));
-    return GR_OK;
+    return items_to_doubles(ctx, r, sizeof(double), n, out, [&](const void* d_in, double* d_out) {
+        return gr_disc_area_factor_device(ctx, cfg, pf, (const double*)d_in, n, d_out, ctx->stream);
+    });
 }
 
 // stage a host rayset on the device: alpha | beta | area | height contiguous in ctx->d_in

@@ -180,9 +180,6 @@ def lineprofile(bins, ε, m, u, d, method=None, *, λ_max=None, redshift_pf=None
     keep = []
     rs, areas = _rayset(config, plane, keep)
     pf, keep_pf = abi_pointfunction(redshift_pf)
-    st = _lib.gr_stats()
-    L = _lib.load()
-    h = config.ensemble.ctx.handle
     # The library takes caller-ordered ray sets to the persistent kernel (neighbours may differ wildly).  Rays handed
     # over in tiles are as coherent as an image plane, and then one ray per lane wins while a ray is long: measured
     # on C5 (4096² rays) -4 % at tolerance 1e-9, -6 % at 1e-7, even at 1e-5, +18 % at 1e-3 (21 vs 18 ms: with 14
@@ -190,12 +187,12 @@ def lineprofile(bins, ε, m, u, d, method=None, *, λ_max=None, redshift_pf=None
     ens = config.ensemble
     lane = getattr(rs, "_tiled", False) and ens.knobs.get("kernel", 2) == 2 and max(config.abstol, config.reltol) <= 1e-6
     fused = isinstance(ε, PowerLawEmissivity) or _emissivity_table(ε) is not None
-    ctxs = ens.contexts if (ens.multi and fused) else [ens.ctx]       # the (g, ρ) route for callable emissivities: one device
+    ctxs = ens.contexts if (ens.multi and fused) else [ens.ctx]       # the contexts _lineprofile_call runs on
     if lane:
         for c in ctxs:
             c.set("kernel", 0)
     try:
-        return _lineprofile_call(L, h, cfg, rs, pf, st, ε, bins, minrₑ, maxrₑ, areas, stats, ctxs=ctxs)
+        return _lineprofile_call(ens, cfg, rs, pf, ε, bins, minrₑ, maxrₑ, areas, stats)
     finally:
         if lane:
             for c in ctxs:
@@ -214,7 +211,7 @@ def _emissivity_table(ε):
     return r, v
 
 
-def _lineprofile_call(L, h, cfg, rs, pf, st, ε, bins, minrₑ, maxrₑ, areas, stats, ctxs=None):
+def _lineprofile_call(ens, cfg, rs, pf, ε, bins, minrₑ, maxrₑ, areas, stats):
     table = None if isinstance(ε, PowerLawEmissivity) else _emissivity_table(ε)
     if isinstance(ε, PowerLawEmissivity) or table is not None:
         b = _lib.gr_binning(float(minrₑ), float(maxrₑ), ε.q if table is None else 0.0, bins.size, bins.ctypes.data)
@@ -222,19 +219,14 @@ def _lineprofile_call(L, h, cfg, rs, pf, st, ε, bins, minrₑ, maxrₑ, areas, 
             # an emissivity profile is a table: interpolated on the device like the power law is evaluated there
             b.eps_r, b.eps_v, b.eps_n = table[0].ctypes.data, table[1].ctypes.data, table[0].size
         flux = np.zeros(bins.size)
-        if ctxs is not None and len(ctxs) > 1:
-            # the plane's rays dealt over the devices, one histogram each, added by the host (gr_lineprofile_multi)
-            arr, sts = _lib.ctx_array(ctxs)
-            _lib.check(L.gr_lineprofile_multi(arr, len(ctxs), C.byref(cfg), C.byref(rs), C.byref(pf), C.byref(b),
-                                              flux.ctypes.data, sts))
-            st = _lib.merge_stats(sts)
-        else:
-            _lib.check(L.gr_lineprofile(h, C.byref(cfg), C.byref(rs), C.byref(pf), C.byref(b), flux.ctypes.data,
-                                        C.byref(st)))
+        # several devices: the plane's rays dealt over them, one histogram each, added by the host (gr_lineprofile_multi)
+        st = ens.call("gr_lineprofile", C.byref(cfg), C.byref(rs), C.byref(pf), C.byref(b), flux.ctypes.data)
     else:
+        # the (g, ρ) route for callable emissivities: one device
         pairs = np.zeros((rs.n, 2))
-        _lib.check(L.gr_redshift_radius(h, C.byref(cfg), C.byref(rs), C.byref(pf), float(minrₑ), float(maxrₑ),
-                                        pairs.ctypes.data, C.byref(st)))
+        st = _lib.gr_stats()
+        _lib.check(_lib.load().gr_redshift_radius(ens.ctx.handle, C.byref(cfg), C.byref(rs), C.byref(pf), float(minrₑ), float(maxrₑ),
+                                                  pairs.ctypes.data, C.byref(st)))
         I = np.flatnonzero(~np.isnan(pairs[:, 0]))
         g, r = pairs[I, 0], pairs[I, 1]
         f = (ε(r) if callable(ε) else ε.emissivity_at(r)) * (g * g * g) * areas[I]

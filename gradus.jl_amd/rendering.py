@@ -93,18 +93,13 @@ def render_into_image(config: TracingConfiguration, pf=None, stats=False):
     if pf.fusable:
         cfg, pl = config.abi_config(), config.abi_plane()
         s, keep = abi_pointfunction(pf)
-        multi = ens.multi
         img = _lib.result_image(ens.ctx, n)      # >= 8 MiB: written by the kernel(s) across the link, each pixel at its place
-        if multi:
-            ctxs = ens.contexts_for_width(pl.width)
-            arr, sts = _lib.ctx_array(ctxs)
-            _lib.check(_lib.load().gr_render_multi(arr, len(ctxs), C.byref(cfg), C.byref(pl), C.byref(s), 0,
-                                                   img.ctypes.data, sts))
-            st = _lib.merge_stats(sts)
+        if ens.multi:
+            st = ens.call("gr_render", C.byref(cfg), C.byref(pl), C.byref(s), 0, img.ctypes.data,
+                          contexts=ens.contexts_for_width(pl.width))
         else:
             rg = _lib.gr_range(0, n, max(n, 1), 1)
-            _lib.check(_lib.load().gr_render(ens.ctx.handle, C.byref(cfg), C.byref(pl), C.byref(s), C.byref(rg),
-                                             img.ctypes.data, C.byref(st)))
+            st = ens.call("gr_render", C.byref(cfg), C.byref(pl), C.byref(s), C.byref(rg), img.ctypes.data)
     else:
         pts = ensemble_solve_tracing_problem(ens, config)
         img = _apply_host(pf, config.metric, pts, config.λ_domain[1])

@@ -229,6 +229,23 @@ class EnsembleMI355X:
             k -= 1
         return ctxs[:k]
 
+    def call(self, name, *args, stats=True, contexts=None):
+        """Make the host call `name` of the library on this ensemble: `name(ctx, *args, &stats)` with one context,
+        `name_multi(ctxs, n, *args, stats[n])` with several (`contexts`: a subset of them, contexts_for_width).  Returns the
+        call's gr_stats (merge_stats of the contexts').  `stats=False`: the caller does not want them (one context is then
+        handed a null pointer and None comes back); `stats=None`: the entry point has no statistics argument."""
+        L = _lib.load()
+        if not self.multi:
+            st = _lib.gr_stats() if stats else None
+            last = () if stats is None else (C.byref(st) if stats else None,)
+            _lib.check(getattr(L, name)(self.ctx.handle, *args, *last))
+            return st
+        ctxs = self.contexts if contexts is None else contexts
+        arr, sts = _lib.ctx_array(ctxs)
+        last = () if stats is None else (sts,)
+        _lib.check(getattr(L, name + "_multi")(arr, len(ctxs), *args, *last))
+        return _lib.merge_stats(sts) if stats else None
+
     def set(self, key, value):
         self.knobs[key] = value
         if self._ctx is not None:
@@ -504,49 +521,23 @@ def tracing_configuration(
 def ensemble_solve_tracing_problem(ensemble: EnsembleMI355X, config: TracingConfiguration, *, stats: bool = False):
     """THE DROP-IN BOUNDARY (src/tracing/tracing.jl:151-196): returns the GeodesicPoint records
     (numpy structured array, 152-byte layout of src/solution-processing.jl:15-32)."""
-    L = _lib.load()
     cfg = config.abi_config()
-    st = _lib.gr_stats()
-    if ensemble.multi:
-        # several devices, one host thread: the same three input shapes through the *_multi entry points
-        ctxs = ensemble.contexts
-        arr, sts = _lib.ctx_array(ctxs)
-        if isinstance(config.velocity, RenderVelocity):
-            pl = config.abi_plane()
-            ctxs = ensemble.contexts_for_width(pl.width)
-            arr, sts = _lib.ctx_array(ctxs)
-            n = pl.width * pl.height
-            out = _lib.result_points(ensemble.ctx, n)   # pinned from 64 MiB up: every device's kernel stores its records there itself
-            _lib.check(L.gr_render_endpoints_multi(arr, len(ctxs), C.byref(cfg), C.byref(pl), 0, out.ctypes.data, sts))
-        elif isinstance(config.velocity, PlaneVelocity):
-            rs, keep = separable_rayset(config.metric, config.position, config.velocity.plane, tiled=False)
-            out = np.zeros(rs.n, dtype=_lib.POINT_DTYPE)
-            _lib.check(L.gr_rayset_endpoints_multi(arr, len(ctxs), C.byref(cfg), C.byref(rs), out.ctypes.data, sts))
-        else:
-            v = np.ascontiguousarray(config.velocity, dtype=np.float64)
-            x = np.ascontiguousarray(config.position, dtype=np.float64)
-            n = v.shape[0]
-            stride = 0 if x.ndim == 1 else 4
-            if stride == 4 and x.shape[0] != n:
-                raise ValueError("positions and velocities must have the same length")
-            out = np.zeros(n, dtype=_lib.POINT_DTYPE)
-            _lib.check(L.gr_trace_endpoints_multi(arr, len(ctxs), C.byref(cfg), x.ctypes.data, stride, v.ctypes.data, n,
-                                                  out.ctypes.data, sts))
-        st = _lib.merge_stats(sts)
-        return (out, st.asdict()) if stats else out
     if isinstance(config.velocity, RenderVelocity):
         pl = config.abi_plane()
         n = pl.width * pl.height
-        rg = _lib.gr_range(0, n, max(n, 1), 1)
-        out = _lib.result_points(ensemble.ctx, n)       # >= 64 MiB: a block the library pinned (as the Julia shim does)
-        _lib.check(L.gr_render_endpoints(ensemble.ctx.handle, C.byref(cfg), C.byref(pl), C.byref(rg),
-                                         out.ctypes.data, C.byref(st)))
+        # >= 64 MiB: a block the library pinned (as the Julia shim does) -- every device's kernel stores its records there itself
+        out = _lib.result_points(ensemble.ctx, n)
+        if ensemble.multi:
+            st = ensemble.call("gr_render_endpoints", C.byref(cfg), C.byref(pl), 0, out.ctypes.data,
+                               contexts=ensemble.contexts_for_width(pl.width))
+        else:
+            rg = _lib.gr_range(0, n, max(n, 1), 1)
+            st = ensemble.call("gr_render_endpoints", C.byref(cfg), C.byref(pl), C.byref(rg), out.ctypes.data)
     elif isinstance(config.velocity, PlaneVelocity):
         # the plane's rays formed on the device, column-major like vec(αs): no (x, v) arrays to build or to send
         rs, keep = separable_rayset(config.metric, config.position, config.velocity.plane, tiled=False)
-        n = rs.n
-        out = np.zeros(n, dtype=_lib.POINT_DTYPE)
-        _lib.check(L.gr_rayset_endpoints(ensemble.ctx.handle, C.byref(cfg), C.byref(rs), out.ctypes.data, C.byref(st)))
+        out = np.zeros(rs.n, dtype=_lib.POINT_DTYPE)
+        st = ensemble.call("gr_rayset_endpoints", C.byref(cfg), C.byref(rs), out.ctypes.data)
     else:
         v = np.ascontiguousarray(config.velocity, dtype=np.float64)
         x = np.ascontiguousarray(config.position, dtype=np.float64)
@@ -555,8 +546,7 @@ def ensemble_solve_tracing_problem(ensemble: EnsembleMI355X, config: TracingConf
         if stride == 4 and x.shape[0] != n:
             raise ValueError("positions and velocities must have the same length")
         out = np.zeros(n, dtype=_lib.POINT_DTYPE)
-        _lib.check(L.gr_trace_endpoints(ensemble.ctx.handle, C.byref(cfg), x.ctypes.data, stride, v.ctypes.data, n,
-                                        out.ctypes.data, C.byref(st)))
+        st = ensemble.call("gr_trace_endpoints", C.byref(cfg), x.ctypes.data, stride, v.ctypes.data, n, out.ctypes.data)
     return (out, st.asdict()) if stats else out
 
 

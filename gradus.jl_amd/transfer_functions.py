@@ -62,14 +62,12 @@ BRACKET_RAYS = 16384        # ... and more levels for small groups, while a laun
 LAUNCH_LOG = None
 
 
-def _logged(name, n):
-    """(gr_stats to pass to the call or None, function to call after it)"""
-    from . import _lib
-
-    if LAUNCH_LOG is None:
-        return None, lambda: None
-    st = _lib.gr_stats()
-    return st, lambda: LAUNCH_LOG.append((name, int(n), st.kernel_ms, st.call_ms))
+def _launch(ens, name, n, *args):
+    """The host call `name` over `n` rays on the ensemble (one context, or shares of the rays on several); a one-context
+    launch goes into LAUNCH_LOG when there is one."""
+    st = ens.call(name, *args, stats=LAUNCH_LOG is not None)
+    if st is not None and not ens.multi:
+        LAUNCH_LOG.append((name, int(n), st.kernel_ms, st.call_ms))
 
 
 def device_tracer(m, x, max_time, chart, redshift_pf, ensemble, geometry=None, callback=None, **solver_opts):
@@ -89,7 +87,6 @@ def device_tracer(m, x, max_time, chart, redshift_pf, ensemble, geometry=None, c
                                    callback=callback, **solver_opts)
     cfg = config.abi_config()
     pf, keep_pf = abi_pointfunction(redshift_pf)
-    L = _lib.load()
     from .tracing import lnr_momentum_to_global_velocity_matrix
 
     Mx = lnr_momentum_to_global_velocity_matrix(m, config.position)
@@ -112,23 +109,12 @@ def device_tracer(m, x, max_time, chart, redshift_pf, ensemble, geometry=None, c
             keep += (h,)
         return rs, keep
 
-    # an ensemble over several devices: the same launches through the *_multi entry points (contiguous shares of the rays)
     ens_ = config.ensemble
-    many = ens_.multi
-    if many:
-        ctx_arr, ctx_stats = _lib.ctx_array(ens_.contexts)
-        n_ctx = len(ens_.contexts)
 
     def trace(α, β, heights=None):
         rs, keep = rayset(α, β, heights)
         out = np.zeros((rs.n, 4))
-        if many:
-            _lib.check(L.gr_ray_summary_multi(ctx_arr, n_ctx, C.byref(cfg), C.byref(rs), C.byref(pf), out.ctypes.data, ctx_stats))
-        else:
-            st, done = _logged("gr_ray_summary", rs.n)
-            _lib.check(L.gr_ray_summary(config.ensemble.ctx.handle, C.byref(cfg), C.byref(rs), C.byref(pf), out.ctypes.data,
-                                        C.byref(st) if st is not None else None))
-            done()
+        _launch(ens_, "gr_ray_summary", rs.n, C.byref(cfg), C.byref(rs), C.byref(pf), out.ctypes.data)
         pts = np.zeros(rs.n, dtype=SUMMARY_DTYPE)
         pts["status"] = out[:, 3].astype(np.int32)
         pts["x"][:, 0], pts["x"][:, 1], pts["x"][:, 2] = out[:, 2], out[:, 1], math.pi / 2
@@ -137,13 +123,7 @@ def device_tracer(m, x, max_time, chart, redshift_pf, ensemble, geometry=None, c
     def endpoints(α, β, heights=None):
         rs, keep = rayset(α, β, heights)
         pts = np.zeros(rs.n, dtype=_lib.POINT_DTYPE)
-        if many:
-            _lib.check(L.gr_rayset_endpoints_multi(ctx_arr, n_ctx, C.byref(cfg), C.byref(rs), pts.ctypes.data, ctx_stats))
-            return pts
-        st, done = _logged("gr_rayset_endpoints", rs.n)
-        _lib.check(L.gr_rayset_endpoints(config.ensemble.ctx.handle, C.byref(cfg), C.byref(rs), pts.ctypes.data,
-                                         C.byref(st) if st is not None else None))
-        done()
+        _launch(ens_, "gr_rayset_endpoints", rs.n, C.byref(cfg), C.byref(rs), pts.ctypes.data)
         return pts
 
     def tangent(α, β, heights=None):
@@ -158,13 +138,7 @@ def device_tracer(m, x, max_time, chart, redshift_pf, ensemble, geometry=None, c
         prev = ens_.knobs.get("tangent_pairs", 2)
         ens_.set("tangent_pairs", 1)
         try:
-            if many:
-                _lib.check(L.gr_ray_tangent_multi(ctx_arr, n_ctx, C.byref(cfg), C.byref(rs), C.byref(pf), out.ctypes.data, ctx_stats))
-            else:
-                st, done = _logged("gr_ray_tangent", rs.n)
-                _lib.check(L.gr_ray_tangent(config.ensemble.ctx.handle, C.byref(cfg), C.byref(rs), C.byref(pf), out.ctypes.data,
-                                            C.byref(st) if st is not None else None))
-                done()
+            _launch(ens_, "gr_ray_tangent", rs.n, C.byref(cfg), C.byref(rs), C.byref(pf), out.ctypes.data)
         finally:
             ens_.set("tangent_pairs", prev)
         return out

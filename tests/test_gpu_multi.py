@@ -285,11 +285,13 @@ def test_one_context_call_is_its_multi_form_on_one_context(G, ens, multi4):
     cfg = config.abi_config()
     pf, keep_pf = abi_pointfunction(G.ConstPointFunctions.redshift(m, X_FAR))
 
-    def both(what, single, multi, out):
-        """single(out, stats) and multi(ctxs, 1, out, stats) -> the bytes both wrote"""
+    def both(what, single, multi, out, pinned=False):
+        """single(out, stats) and multi(ctxs, 1, out, stats) -> the bytes both wrote (into pageable memory or gr_host_alloc blocks)"""
         st, sts = _lib.gr_stats(), (_lib.gr_stats * 1)()
         st.enqueue_ms = -1.0
-        a, b = np.full_like(out, 0xFF), np.full_like(out, 0xFF)
+        a, b = _dest(L, ens.ctx, out.size, pinned), _dest(L, ens.ctx, out.size, pinned)
+        a[:] = 0xFF
+        b[:] = 0xFF
         _lib.check(single(a.ctypes.data, C.byref(st)))
         _lib.check(multi(one_ctx, 1, b.ctypes.data, sts))
         assert a.tobytes() == b.tobytes(), what
@@ -346,6 +348,132 @@ def test_one_context_call_is_its_multi_form_on_one_context(G, ens, multi4):
                  lambda a, k, o, s: L.gr_plane_cells_multi(a, k, C.byref(cfg), C.byref(pl), al.ctypes.data, be.ctypes.data, n, o, s),
                  np.zeros(152 * n, dtype=np.uint8))
     assert st.rays == n
+
+    # the image plane: pixels and end-point records, into pageable memory and into a block the library pinned; the bytes are
+    # those of the *_device entry points.  64 columns are dealt in blocks of 8; 68 in blocks of 4 to one context and of 1 to
+    # four, and 44 rows leave a ragged last row of tiles.
+    for W, H in ((64, 64), (68, 44)):
+        ref = _plane_reference(G, ens, W, H)
+        pcfg, ppl = ref["config"].abi_config(), ref["config"].abi_plane()
+        s, keep_s = abi_pointfunction(ref["pf"])
+        n_px = W * H
+        rg = _lib.gr_range(0, n_px, n_px, 1)
+        for pinned in (False, True):
+            st, img = both(f"gr_render {W}x{H} pinned={pinned}",
+                           lambda o, q: L.gr_render(h, C.byref(pcfg), C.byref(ppl), C.byref(s), C.byref(rg), o, q),
+                           lambda a, k, o, q: L.gr_render_multi(a, k, C.byref(pcfg), C.byref(ppl), C.byref(s), 0, o, q),
+                           ref["image"], pinned)
+            assert img.tobytes() == ref["image"].tobytes() and st.rays == n_px, (W, H, pinned)
+            st, pts = both(f"gr_render_endpoints {W}x{H} pinned={pinned}",
+                           lambda o, q: L.gr_render_endpoints(h, C.byref(pcfg), C.byref(ppl), C.byref(rg), o, q),
+                           lambda a, k, o, q: L.gr_render_endpoints_multi(a, k, C.byref(pcfg), C.byref(ppl), 0, o, q),
+                           ref["points"], pinned)
+            assert pts.tobytes() == ref["points"].tobytes() and st.rays == n_px, (W, H, pinned)
+            arr, sts = _ctxs(multi4, 4)
+            raw = _dest(L, multi4.ctx, 8 * n_px, pinned)
+            raw[:] = 0xFF
+            _lib.check(L.gr_render_multi(arr, 4, C.byref(pcfg), C.byref(ppl), C.byref(s), 0, raw.ctypes.data, sts))
+            assert raw.tobytes() == ref["image"].tobytes() and sum(x.rays for x in sts) == n_px, (W, H, pinned)
+            raw = _dest(L, multi4.ctx, 152 * n_px, pinned)
+            raw[:] = 0xFF
+            _lib.check(L.gr_render_endpoints_multi(arr, 4, C.byref(pcfg), C.byref(ppl), 0, raw.ctypes.data, sts))
+            assert raw.tobytes() == ref["points"].tobytes() and sum(x.rays for x in sts) == n_px, (W, H, pinned)
+
+
+_PLANE_REFERENCE = {}
+
+
+def _plane_reference(G, ens, W, H):
+    """The whole W x H plane from gr_render_device and gr_render_endpoints_device into torch memory, copied to the host: the
+    image's and the records' bytes (read-only uint8 arrays) and the counters of the two launches.  The host-buffer calls are
+    compared with this, never with one another alone."""
+    if (W, H) not in _PLANE_REFERENCE:
+        import torch
+        from gradus_jl_amd import device as gdev
+
+        m, config = _render_config(G, ens, W, H)
+        pf = G.ConstPointFunctions.redshift(m, X_FAR) @ G.ConstPointFunctions.filter_intersected()
+        dev = torch.device("cuda", 0)
+        img = torch.empty(W * H, dtype=torch.float64, device=dev)
+        raw = torch.empty(152 * W * H, dtype=torch.uint8, device=dev)
+        st_img, st_pts = gdev.new_stats(dev), gdev.new_stats(dev)
+        gdev.render_device(config, pf, img, stats=st_img)
+        gdev.render_endpoints_device(config, raw, stats=st_pts)
+        torch.cuda.synchronize()
+        image, points = img.cpu().numpy().view(np.uint8), raw.cpu().numpy()
+        image.setflags(write=False)
+        points.setflags(write=False)
+        assert np.isfinite(image.view(np.float64)).sum() > W * H // 10
+        _PLANE_REFERENCE[(W, H)] = {"config": config, "pf": pf, "image": image, "points": points,
+                                    "image_stats": gdev.stats_dict(st_img), "points_stats": gdev.stats_dict(st_pts)}
+    return _PLANE_REFERENCE[(W, H)]
+
+
+@pytest.mark.parametrize("pinned", [False, True])
+@pytest.mark.parametrize("W,H", [(64, 64), (68, 44)])
+def test_one_context_renders_of_a_part_of_the_plane(G, ens, W, H, pinned):
+    """gr_render and gr_render_endpoints on one context and a range that is not the whole plane write that range's rows, in
+    the range's order, to the start of the caller's buffer: a contiguous range of whole 8-column strips (the shape a banded
+    return takes) and the two strided halves of a deal over two (rays k block ... of every second block).  The rows are the
+    matching ones of the whole plane from the *_device entry points."""
+    from gradus_jl_amd import _lib
+    from gradus_jl_amd.rendering import abi_pointfunction
+
+    L = _lib.load()
+    h = ens.ctx.handle
+    ref = _plane_reference(G, ens, W, H)
+    cfg, pl = ref["config"].abi_config(), ref["config"].abi_plane()
+    s, keep_s = abi_pointfunction(ref["pf"])
+    bc = 8
+    while W % (2 * bc):
+        bc //= 2
+    block = bc * H
+    ranges = [("strips", _lib.gr_range(8 * H, 16 * H, 16 * H, 1), np.arange(8 * H, 24 * H))]
+    for k in (0, 1):
+        rows = np.arange(W * H).reshape(-1, block)[k::2].ravel()
+        ranges.append((f"every second block from {k}", _lib.gr_range(k * block, rows.size, block, 2), rows))
+    for what, rg, rows in ranges:
+        st = _lib.gr_stats()
+        raw = _dest(L, ens.ctx, 8 * rows.size, pinned)
+        raw[:] = 0xFF
+        _lib.check(L.gr_render(h, C.byref(cfg), C.byref(pl), C.byref(s), C.byref(rg), raw.ctypes.data, C.byref(st)))
+        assert raw.tobytes() == ref["image"].reshape(-1, 8)[rows].tobytes(), (what, "gr_render")
+        assert st.rays == rows.size and st.enqueue_ms == 0.0
+        raw = _dest(L, ens.ctx, 152 * rows.size, pinned)
+        raw[:] = 0xFF
+        _lib.check(L.gr_render_endpoints(h, C.byref(cfg), C.byref(pl), C.byref(rg), raw.ctypes.data, C.byref(st)))
+        assert raw.tobytes() == ref["points"].reshape(-1, 152)[rows].tobytes(), (what, "gr_render_endpoints")
+        assert st.rays == rows.size and st.enqueue_ms == 0.0
+
+
+@pytest.mark.parametrize("pinned", [False, True])
+def test_a_refused_render_leaves_the_context_as_it_was(G, ens, pinned):
+    """gr_render_endpoints refuses a range that reaches past the image only once the call has begun on the context (the plane
+    is checked where the launch is prepared).  Nothing of the refused call stays behind: the next call on the same context
+    returns the plane's records and the counters of one call -- those of the *_device launch of the same plane."""
+    from gradus_jl_amd import _lib
+
+    L = _lib.load()
+    h = ens.ctx.handle
+    W, H = 68, 44
+    n = W * H
+    ref = _plane_reference(G, ens, W, H)
+    cfg, pl = ref["config"].abi_config(), ref["config"].abi_plane()
+    raw = _dest(L, ens.ctx, 152 * (n + 64), pinned)
+    raw[:] = 0xFF
+    st = _lib.gr_stats()
+    too_long = _lib.gr_range(0, n + 64, n + 64, 1)
+    assert L.gr_render_endpoints(h, C.byref(cfg), C.byref(pl), C.byref(too_long), raw.ctypes.data, C.byref(st)) == -1      # GR_ERR_INVALID_ARGUMENT
+    assert L.gr_last_error()
+    assert (raw == 0xFF).all()
+    rg = _lib.gr_range(0, n, n, 1)
+    _lib.check(L.gr_render_endpoints(h, C.byref(cfg), C.byref(pl), C.byref(rg), raw.ctypes.data, C.byref(st)))
+    assert raw[:152 * n].tobytes() == ref["points"].tobytes() and (raw[152 * n:] == 0xFF).all()
+    want = ref["points_stats"]
+    assert st.rays == n == want["rays"]
+    assert (st.accepted_steps, st.rejected_steps) == (want["accepted_steps"], want["rejected_steps"])
+    assert list(st.status_count) == want["status_count"]
+    assert st.enqueue_ms == 0.0 and st.kernel_ms > 0.0 and st.call_ms >= st.kernel_ms
 
 
 @pytest.mark.parametrize("pinned", [False, True])
