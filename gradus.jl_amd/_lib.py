@@ -217,6 +217,42 @@ class gr_rayset(C.Structure):
     ]
 
 
+class gr_offset_problems(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64),
+        ("r_target", C.c_void_p),
+        ("cos_theta", C.c_void_p),
+        ("sin_theta", C.c_void_p),
+        ("height", C.c_void_p),
+        ("alpha0", C.c_double),
+        ("beta0", C.c_double),
+        ("zero_atol", C.c_double),
+        ("r_min", C.c_double),
+        ("max_iter", C.c_int64),
+        ("contrapoint_bias", C.c_double),
+        ("per_wave", C.c_int64),
+    ]
+
+
+class gr_offset_searches(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64),
+        ("r_target", C.c_void_p),
+        ("lower", C.c_void_p),
+        ("upper", C.c_void_p),
+        ("sign", C.c_void_p),
+        ("height", C.c_void_p),
+        ("alpha0", C.c_double),
+        ("beta0", C.c_double),
+        ("zero_atol", C.c_double),
+        ("r_min", C.c_double),
+        ("max_iter", C.c_int64),
+        ("contrapoint_bias", C.c_double),
+        ("per_wave", C.c_int64),
+        ("iterations", C.c_int64),
+    ]
+
+
 class gr_binning(C.Structure):
     _fields_ = [
         ("r_min", C.c_double),
@@ -419,6 +455,10 @@ EXPORTS = [
     "gr_ray_summary",
     "gr_ray_tangent_device",
     "gr_ray_tangent",
+    "gr_offset_solve_device",
+    "gr_offset_solve",
+    "gr_offset_search_device",
+    "gr_offset_search",
     "gr_rayset_endpoints_device",
     "gr_rayset_endpoints",
     "gr_apply_pointfunction_device",
@@ -464,6 +504,8 @@ EXPORTS = [
     "gr_rayset_endpoints_multi",
     "gr_ray_summary_multi",
     "gr_ray_tangent_multi",
+    "gr_offset_solve_multi",
+    "gr_offset_search_multi",
     "gr_redshift_radius_multi",
     "gr_lineprofile_multi",
     "gr_metric_grid_plan",
@@ -517,6 +559,13 @@ def load():
     L.gr_ray_summary.argtypes = [vp, cfgp, rsp, pfp, vp, stp]
     L.gr_ray_tangent_device.argtypes = [vp, cfgp, rsp, pfp, vp, vp, vp]
     L.gr_ray_tangent.argtypes = [vp, cfgp, rsp, pfp, vp, stp]
+    opp, osp = C.POINTER(gr_offset_problems), C.POINTER(gr_offset_searches)
+    L.gr_offset_solve_device.argtypes = [vp, cfgp, rsp, pfp, opp, vp, vp, vp]
+    L.gr_offset_solve.argtypes = [vp, cfgp, rsp, pfp, opp, vp, stp]
+    L.gr_offset_search_device.argtypes = [vp, cfgp, rsp, pfp, osp, vp, vp, vp]
+    L.gr_offset_search.argtypes = [vp, cfgp, rsp, pfp, osp, vp, stp]
+    L.gr_offset_solve_multi.argtypes = [C.POINTER(vp), i32, cfgp, rsp, pfp, opp, vp, vp]
+    L.gr_offset_search_multi.argtypes = [C.POINTER(vp), i32, cfgp, rsp, pfp, osp, vp, vp]
     L.gr_rayset_endpoints_device.argtypes = [vp, cfgp, rsp, vp, vp, vp]
     L.gr_rayset_endpoints.argtypes = [vp, cfgp, rsp, vp, stp]
     L.gr_apply_pointfunction_device.argtypes = [vp, cfgp, pfp, vp, i64, C.c_double, vp, vp]

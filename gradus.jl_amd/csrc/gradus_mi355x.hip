@@ -35,6 +35,7 @@
 #include "gr_ringarm.hpp"
 #include "gr_skygrid.hpp"
 #include "gr_planegrid.hpp"
+#include "gr_offsetsolve.hpp"
 
 using namespace gr;
 
@@ -49,7 +50,8 @@ using namespace gr;
     hipError_t gr64_launch_path_m##ID(const void*, double*, int64_t, unsigned long long*, hipStream_t);                \
     hipError_t gr64_launch_apply_m##ID(const void*, const gr_point*, double, double*, hipStream_t);                     \
     hipError_t gr64_launch_classify_m##ID(const void*, uint8_t*, int64_t, hipStream_t);                                \
-    hipError_t gr64_launch_areafactor_m##ID(const void*, const double*, double*, hipStream_t);
+    hipError_t gr64_launch_areafactor_m##ID(const void*, const double*, double*, hipStream_t);                         \
+    hipError_t grv1_launch_offset_m##ID(const void*, const void*, int, hipStream_t);
 GR_DECLARE_METRIC(0) GR_DECLARE_METRIC(1) GR_DECLARE_METRIC(2) GR_DECLARE_METRIC(3) GR_DECLARE_METRIC(4) GR_DECLARE_METRIC(5)
 GR_DECLARE_METRIC(6) GR_DECLARE_METRIC(7) GR_DECLARE_METRIC(8) GR_DECLARE_METRIC(9) GR_DECLARE_METRIC(10)
 #undef GR_DECLARE_METRIC
@@ -64,6 +66,7 @@ hipError_t gr64_launch_path_m11(const void*, double*, int64_t, unsigned long lon
 hipError_t gr64_launch_apply_m11(const void*, const gr_point*, double, double*, hipStream_t);
 hipError_t gr64_launch_classify_m11(const void*, uint8_t*, int64_t, hipStream_t);
 hipError_t gr64_launch_areafactor_m11(const void*, const double*, double*, hipStream_t);
+hipError_t grv1_launch_offset_m11(const void*, const void*, int, hipStream_t);
 static_assert(GR_METRIC_NOZ == 10 && GR_METRIC_TABULATED == 11, "one kernel object per metric id 0..11: extend the tables below with the catalogue");
 
 namespace {
@@ -79,6 +82,7 @@ typedef hipError_t (*path_fn)(const void*, double*, int64_t, unsigned long long*
 typedef hipError_t (*apply_fn)(const void*, const gr_point*, double, double*, hipStream_t);
 typedef hipError_t (*classify_fn)(const void*, uint8_t*, int64_t, hipStream_t);
 typedef hipError_t (*areafactor_fn)(const void*, const double*, double*, hipStream_t);
+typedef hipError_t (*offset_fn)(const void*, const void*, int, hipStream_t);
 #define GR_ROW(F, LAST) { F##0, F##1, F##2, F##3, F##4, F##5, F##6, F##7, F##8, F##9, F##10, LAST }
 const trace_fn kTrace64[12] = GR_ROW(gr64_launch_trace_m, gr64_launch_trace_m11);
 const trace_fn kTrace32[12] = GR_ROW(gr32_launch_trace_m, gr32_launch_trace_m11);
@@ -90,6 +94,7 @@ const path_fn kPath64[12] = GR_ROW(gr64_launch_path_m, gr64_launch_path_m11);
 const apply_fn kApply64[12] = GR_ROW(gr64_launch_apply_m, gr64_launch_apply_m11);
 const classify_fn kClassify64[12] = GR_ROW(gr64_launch_classify_m, gr64_launch_classify_m11);      // the live-first tile order's flags (gr_tile_order.hpp)
 const areafactor_fn kAreaFactor64[12] = GR_ROW(gr64_launch_areafactor_m, gr64_launch_areafactor_m11);      // γ(r) A(r) of the disc (kernelsarea_m<id>.o)
+const offset_fn kOffsetSolve1[12] = GR_ROW(grv1_launch_offset_m, grv1_launch_offset_m11);      // k_offset_solve / k_offset_search (kernelssolve1_m<id>.o)
 #undef GR_ROW
 // Metric::kEscapeRadiusM per metric id, in units of params[0] (escape_cull_radius)
 #define GR_ESC(ID) MetricOf<ID>::type::kEscapeRadiusM
@@ -171,6 +176,8 @@ struct gr_ctx {
     size_t scratch_bytes = 0;
     void* d_in = nullptr;
     size_t in_bytes = 0;
+    double* d_offset_work = nullptr;       // gr_offset_solve / gr_offset_search: α | β | row of the ray every problem is tracing
+    size_t offset_work_bytes = 0;
     // knobs
     int64_t kernel = 2;                    // 0 lane, 1 persistent, 2 auto (by launch depth)
     int64_t lpt_lane = 0;                  // also order tiles longest-first for the lane kernel
@@ -1225,6 +1232,7 @@ int32_t gr_ctx_destroy(gr_ctx* c)
     if (c->d_plunge) (void)hipFree(c->d_plunge);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->d_in) (void)hipFree(c->d_in);
+    if (c->d_offset_work) (void)hipFree(c->d_offset_work);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_k) (void)hipEventDestroy(c->ev_k);
@@ -1906,6 +1914,149 @@ int32_t gr_ray_tangent_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset
     cd.lp_pairs = d_out;
     p.stats = (unsigned long long*)d_stats;
     return launch_trace(ctx, p, cd, stream);
+}
+
+// ---- gr_offset_solve / gr_offset_search: the iterations around gr_ray_tangent's rays, one problem per lane pair (gr_offsetsolve.hpp) ----
+extern "C++" {
+namespace {
+// gr_offset_problems and gr_offset_searches as one: a (cos θ, sin θ | lower, upper), sign for a search alone
+struct OffsetCall {
+    int64_t n;
+    const double *r_target, *a, *b, *sign, *height;
+    gr_os::Setup st;
+    int64_t max_iter, iterations, per_wave;
+    bool search;
+    int64_t out_stride() const { return search ? gr_os::search_stride(iterations) : gr_os::kSolveOut; }
+};
+int32_t offset_call(const gr_offset_problems* q, OffsetCall& c)
+{
+    if (!q) return fail(GR_ERR_INVALID_ARGUMENT, "gr_offset_solve: problems is null");
+    c = OffsetCall{ q->n, q->r_target, q->cos_theta, q->sin_theta, nullptr, q->height,
+                    gr_os::Setup{ q->alpha0, q->beta0, q->zero_atol, q->r_min, q->contrapoint_bias, 0, 0 }, q->max_iter, 0, q->per_wave, false };
+    return GR_OK;
+}
+int32_t offset_call(const gr_offset_searches* q, OffsetCall& c)
+{
+    if (!q) return fail(GR_ERR_INVALID_ARGUMENT, "gr_offset_search: searches is null");
+    c = OffsetCall{ q->n, q->r_target, q->lower, q->upper, q->sign, q->height,
+                    gr_os::Setup{ q->alpha0, q->beta0, q->zero_atol, q->r_min, q->contrapoint_bias, 0, 0 }, q->max_iter, q->iterations, q->per_wave, true };
+    return GR_OK;
+}
+// what every form refuses before anything touches the device
+int32_t offset_check(const gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf, OffsetCall& c, const void* out)
+{
+    const std::string who = c.search ? "gr_offset_search" : "gr_offset_solve";
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!rays) return fail(GR_ERR_INVALID_ARGUMENT, "rayset is null");
+    if (rays->sky_sampler || rays->sky_rows) return fail(GR_ERR_UNSUPPORTED, who + ": the rays leave an observer's image plane, not a source's sky");
+    int32_t rc;
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if (cfg->disc_id != GR_DISC_THIN && cfg->disc_id != GR_DISC_DATUM)
+        return fail(GR_ERR_UNSUPPORTED, who + ": the offsets are solved against a thin disc or a datum plane (disc_id " + std::to_string(cfg->disc_id) + ")");
+    if (ctx->precision == 32) return fail(GR_ERR_UNSUPPORTED, who + ": the tangent kernels are fp64 (precision 32 is set)");
+    if (c.n < 0 || c.n > (int64_t)INT32_MAX) return fail(GR_ERR_INVALID_ARGUMENT, who + ": n in 0 ... 2^31 - 1");
+    if (c.n > 0 && (!c.r_target || !c.a || !c.b || (c.search && !c.sign) || !out)) return fail(GR_ERR_INVALID_ARGUMENT, who + ": a null pointer");
+    if (c.max_iter < 0 || c.max_iter > (int64_t)1 << 20) return fail(GR_ERR_INVALID_ARGUMENT, who + ": max_iter in 0 ... 2^20");
+    if (c.iterations < 0 || c.iterations > 4096) return fail(GR_ERR_INVALID_ARGUMENT, who + ": iterations in 0 ... 4096");
+    if (c.per_wave < 0 || c.per_wave > 32) return fail(GR_ERR_INVALID_ARGUMENT, who + ": per_wave in 0 ... 32");
+    if (!pf || pf->pf_id != GR_PF_REDSHIFT) return fail(GR_ERR_INVALID_ARGUMENT, who + ": needs the redshift point function");
+    c.st.max_iter = (int32_t)c.max_iter;
+    c.st.iterations = (int32_t)c.iterations;
+    return GR_OK;
+}
+
+// the launch: every pointer of `c` and `d_out` on the device
+int32_t offset_launch(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf, const OffsetCall& c,
+                      double* d_out, gr_stats* d_stats, hipStream_t stream)
+{
+    if (c.n == 0) return GR_OK;
+    int32_t rc;
+    // The work block -- α, β and the row of the ray every problem is tracing -- is the context's, like its staged tables: a launch on
+    // another stream waits for the one that used it last.
+    if ((rc = tables_acquire(ctx, stream)) != GR_OK) return rc;
+    const size_t n = (size_t)c.n;
+    if ((rc = ensure((void**)&ctx->d_offset_work, &ctx->offset_work_bytes, sizeof(double) * 10 * n)) != GR_OK) return rc;
+    gr_os::OffsetDev d;
+    d.r_target = c.r_target; d.a = c.a; d.b = c.b; d.sign = c.sign;
+    d.alpha = ctx->d_offset_work; d.beta = d.alpha + n; d.rows = d.alpha + 2 * n;
+    d.out = d_out;
+    d.st = c.st;
+    // problems per wave: full waves.  Measured on the default line profile's 8000 solves (DESIGN_measurements.md §M38): 63 ms at 32
+    // and at 16 pairs per wave, 77 at 8 (one wave on every SIMD), 104 at 4, 207 at 1; its 200 searches take the same time at every
+    // value.  A wave's step costs the same for one pair as for thirty-two, and fewer waves share a CU's caches.
+    d.per_wave = (int32_t)(c.per_wave > 0 ? c.per_wave : 32);
+
+    Params p;
+    Cold cd;
+    std::memset(&p, 0, sizeof p);
+    std::memset(&cd, 0, sizeof cd);
+    p.cfg = *cfg;
+    p.n = c.n;
+    cd.src_mode = 2;
+    cd.out_mode = 5;
+    std::memcpy(cd.plane.x_obs, rays->x_obs, sizeof cd.plane.x_obs);
+    std::memcpy(cd.plane.Mx, rays->Mx, sizeof cd.plane.Mx);
+    cd.plane.width = c.n; cd.plane.height = 1;
+    cd.range = gr_range{ 0, c.n, c.n, 1 };
+    cd.alpha = d.alpha; cd.beta = d.beta;
+    cd.height = cfg->disc_id == GR_DISC_DATUM ? c.height : nullptr;
+    cd.lp_rmin = 0.0; cd.lp_rmax = INFINITY; cd.lp_pairs = d.rows;
+    cd.winding_plane = p.cfg.winding_plane;
+    if ((rc = stage_pf(ctx, cfg, pf, cd.pf, stream)) != GR_OK) return rc;
+    if (p.cfg.metric_id == GR_METRIC_TABULATED) {      // as launch_trace: the observer must lie inside the table
+        const double r_obs = rays->x_obs[1], t_min = p.cfg.metric_table[gr_tab::H_RMIN], t_max = p.cfg.metric_table[gr_tab::H_RMAX];
+        if (!(r_obs >= t_min - 1e-9 * std::fabs(t_min) - 1e-12) || !(r_obs <= t_max + 1e-9 * std::fabs(t_max)))
+            return fail(GR_ERR_INVALID_ARGUMENT, "GR_METRIC_TABULATED: the rays start at r = " + std::to_string(r_obs) + ", outside the radial range of the "
+                                                 "metric table [" + std::to_string(t_min) + ", " + std::to_string(t_max) + "]");
+    }
+    if ((rc = stage_disc_table(ctx, p, stream)) != GR_OK) return rc;
+    Cold* slot = ctx->d_cold + ctx->cold_next;
+    ctx->cold_next = (ctx->cold_next + 1) % ctx->queue_slots;
+    p.cold = slot;
+    // one-wave workgroups: the plunging table is staged per workgroup while 8 copies fit a CU's LDS (launch_trace)
+    p.lds_plunge_rows = (ctx->lds && cd.pf.n_plunge > 0 && cd.pf.n_plunge <= 640) ? (int32_t)cd.pf.n_plunge : 0;
+    derive_params(p);      // every cull off, as for gr_ray_tangent
+    p.tangent_norm = ctx->tangent_norm ? 1 : 0;
+    GR_HIP(hipMemcpyAsync(slot, &cd, sizeof(Cold), hipMemcpyHostToDevice, stream));
+    unsigned long long* const caller_stats = (unsigned long long*)d_stats;
+    if (caller_stats) {
+        p.stats = ctx->d_stat_part + (size_t)ctx->stat_next * gr_fold::kStatWords;
+        ctx->stat_next = (ctx->stat_next + 1) % ctx->queue_slots;
+    }
+    const hipError_t le = kOffsetSolve1[p.cfg.metric_id](&p, &d, c.search ? 1 : 0, stream);
+    if (le != hipSuccess) return fail(GR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(le));
+    if (caller_stats) {
+        hipLaunchKernelGGL(k_stats_fold, dim3(1), dim3(64), 0, stream, p.stats, caller_stats);
+        GR_HIP(hipGetLastError());
+    }
+    if (stream == ctx->stream) GR_HIP(hipEventRecord(ctx->ev_k, stream));
+    return tables_release(ctx, stream);
+}
+
+template <class Q>
+int32_t offset_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf, const Q* q, double* d_out,
+                      gr_stats* d_stats, void* hip_stream)
+{
+    OffsetCall c;
+    int32_t rc;
+    if ((rc = offset_call(q, c)) != GR_OK) return rc;
+    if ((rc = offset_check(ctx, cfg, rays, pf, c, d_out)) != GR_OK) return rc;
+    GR_HIP(hipSetDevice(ctx->device));
+    return offset_launch(ctx, cfg, rays, pf, c, d_out, d_stats, (hipStream_t)hip_stream);
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t gr_offset_solve_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                               const gr_offset_problems* problems, double* d_out, gr_stats* d_stats, void* hip_stream)
+{
+    return offset_device(ctx, cfg, rays, pf, problems, d_out, d_stats, hip_stream);
+}
+
+int32_t gr_offset_search_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                                const gr_offset_searches* searches, double* d_out, gr_stats* d_stats, void* hip_stream)
+{
+    return offset_device(ctx, cfg, rays, pf, searches, d_out, d_stats, hip_stream);
 }
 
 // ---- the cells of a source's adaptive sky (AdaptiveSky, adaptive-sample.jl:43-81): gr_sky_cells ----
@@ -4267,6 +4418,90 @@ int32_t gr_ray_tangent_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
                              double* out, gr_stats* stats)
 {
     return ray_tangent_on(ctxs, n, cfg, rays, pf, out, stats, "gr_ray_tangent_multi");
+}
+
+// ---- gr_offset_solve / gr_offset_search: host buffers; one context, or contiguous shares of the problems over several ----
+extern "C++" {
+namespace {
+template <class Q>
+int32_t offset_on(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf, const Q* q,
+                  double* out, gr_stats* stats)
+{
+    int32_t rc;
+    if ((rc = validate_ctxs(ctxs, n)) != GR_OK) return rc;
+    if (n > 64) return fail(GR_ERR_INVALID_ARGUMENT, "at most 64 contexts");
+    OffsetCall all;
+    if ((rc = offset_call(q, all)) != GR_OK) return rc;
+    for (int k = 0; k < n; ++k)
+        if ((rc = offset_check(ctxs[k], cfg, rays, pf, all, out)) != GR_OK) return rc;
+    const size_t row_bytes = sizeof(double) * (size_t)all.out_stride();
+    const size_t total = row_bytes * (size_t)all.n;
+    const bool pinned = is_pinned(out, total);
+    auto enq = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        int64_t off, cnt;
+        contiguous_share(all.n, n, k, &off, &cnt);
+        int32_t r;
+        GR_HIP(hipSetDevice(c->device));
+        if ((r = begin_host_call(c, stats ? &stats[k] : nullptr)) != GR_OK) return r;
+        if (cnt == 0) return GR_OK;
+        // r_target | a | b | sign | height, cnt each, in the context's input block; the results in its scratch block
+        const size_t m = (size_t)cnt;
+        if ((r = ensure(&c->d_in, &c->in_bytes, sizeof(double) * 5 * m)) != GR_OK) return r;
+        if ((r = ensure(&c->d_scratch, &c->scratch_bytes, row_bytes * m)) != GR_OK) return r;
+        double* base = (double*)c->d_in;
+        OffsetCall share = all;
+        share.n = cnt;
+        const double* src[5] = { all.r_target, all.a, all.b, all.sign, all.height };
+        const double** dst[5] = { &share.r_target, &share.a, &share.b, &share.sign, &share.height };
+        for (int f = 0; f < 5; ++f) {
+            if (!src[f]) continue;
+            GR_HIP(hipMemcpyAsync(base + f * m, src[f] + off, sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
+            *dst[f] = base + f * m;
+        }
+        // a search that ends early leaves its later records unwritten: NaN (all bits set) is what the caller finds there
+        if (share.search) GR_HIP(hipMemsetAsync(c->d_scratch, 0xff, row_bytes * m, c->stream));
+        return offset_launch(c, cfg, rays, pf, share, (double*)c->d_scratch, stats ? (gr_stats*)c->d_stats : nullptr, c->stream);
+    };
+    bool faulted = false;
+    auto copy = [&](int k) -> int32_t {
+        gr_ctx* c = ctxs[k];
+        int64_t off, cnt;
+        contiguous_share(all.n, n, k, &off, &cnt);
+        if (cnt == 0) return GR_OK;
+        if (!faulted && !pinned) prefault_output(out, total, c->hugepages != 0);
+        faulted = true;
+        GR_HIP(hipSetDevice(c->device));
+        GR_HIP(hipMemcpyAsync((char*)out + row_bytes * (size_t)off, c->d_scratch, row_bytes * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        return GR_OK;
+    };
+    return multi_drive(ctxs, n, stats, enq, copy);
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t gr_offset_solve_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                              const gr_offset_problems* problems, double* out, gr_stats* stats)
+{
+    return offset_on(ctxs, n, cfg, rays, pf, problems, out, stats);
+}
+
+int32_t gr_offset_solve(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                        const gr_offset_problems* problems, double* out, gr_stats* stats)
+{
+    return one_context(offset_on(&ctx, 1, cfg, rays, pf, problems, out, stats), stats);
+}
+
+int32_t gr_offset_search_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                               const gr_offset_searches* searches, double* out, gr_stats* stats)
+{
+    return offset_on(ctxs, n, cfg, rays, pf, searches, out, stats);
+}
+
+int32_t gr_offset_search(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                         const gr_offset_searches* searches, double* out, gr_stats* stats)
+{
+    return one_context(offset_on(&ctx, 1, cfg, rays, pf, searches, out, stats), stats);
 }
 
 static int32_t redshift_radius_on(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,

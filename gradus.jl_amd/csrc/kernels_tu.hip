@@ -6,6 +6,7 @@
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN1 -c kernels_tu.hip -o kernelstan1_m<id>.o                   (tangent, a pair of lanes per ray)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN[1] -DGR_TU_SKY -c kernels_tu.hip -o kernelssky[1]_m<id>.o    (the two tangent shapes for sky cells)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_AREA -c kernels_tu.hip -o kernelsarea_m<id>.o                   (fp64, k_disc_area_factor alone)
+//     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN1 -DGR_TU_SOLVE -c kernels_tu.hip -o kernelssolve1_m<id>.o    (pairs; k_offset_solve, k_offset_search alone)
 //
 // so that every metric's kernels hold only that metric's component function (gr_device.hpp, GenericMetricT) and the
 // library builds on all cores at once (__graft_entry__.build_hip).  The fp32 objects are the same source with
@@ -15,7 +16,7 @@
 //
 // Exports (plain signatures: the host unit, gradus_mi355x.hip, passes its gr::Params by address -- gr32::Params has the
 // same layout, its fields are double / integer / pointers only):
-//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>, gr64_launch_areafactor_m<ID> (-DGR_TU_AREA)      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>      grts_launch_trace_m<ID>      grts1_launch_trace_m<ID>
+//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>, gr64_launch_areafactor_m<ID> (-DGR_TU_AREA)      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>      grts_launch_trace_m<ID>      grts1_launch_trace_m<ID>      grv1_launch_offset_m<ID> (-DGR_TU_SOLVE)
 #ifndef GR_TU_METRIC
 #error "compile with -DGR_TU_METRIC=<metric id>"
 #endif
@@ -44,7 +45,10 @@
 #endif
 #if defined(GR_TU_TAN1)
 #define GR_TAN_W 1
-#if defined(GR_TU_SKY)
+#if defined(GR_TU_SOLVE)
+#define GR_NS grv1
+#define GR_TU_PREFIX grv1
+#elif defined(GR_TU_SKY)
 #define GR_NS grts1
 #define GR_TU_PREFIX grts1
 #else
@@ -74,6 +78,9 @@
 #include <hip/hip_runtime.h>
 
 #include "gr_kernels.hpp"
+#if defined(GR_TU_SOLVE)
+#include "gr_offsetsolve.hpp"
+#endif
 
 #define GR_CAT3_(a, b, c) a##b##c
 #define GR_CAT3(a, b, c) GR_CAT3_(a, b, c)
@@ -90,6 +97,15 @@ typedef GR_NS::MetricOf<GR_TU_METRIC>::type TuMetric;
 hipError_t GR_TU_NAME(_launch_areafactor_m)(const void* params, const double* r, double* out, hipStream_t stream)
 {
     return GR_NS::launch_areafactor_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), r, out, stream);
+}
+#elif defined(GR_TU_SOLVE)
+// The offset solve and the extremum search of the transfer functions, one problem per lane pair (gr_offsetsolve.hpp: k_offset_solve,
+// k_offset_search).  An object of its own (the GR_TU_SKY precedent): the pair-shape trace kernel of kernelstan1_m<id>.o stays as
+// it is, and this object carries no trace kernel.  `dev` is a gr_os::OffsetDev.
+hipError_t GR_TU_NAME(_launch_offset_m)(const void* params, const void* dev, int search, hipStream_t stream)
+{
+    GR_NS::Params p = *reinterpret_cast<const GR_NS::Params*>(params);
+    return GR_NS::launch_offset_metric<TuMetric>(p, *reinterpret_cast<const gr_os::OffsetDev*>(dev), search != 0, stream);
 }
 #else
 hipError_t GR_TU_NAME(_launch_trace_m)(int kernel, int block, int n_cu, int waves_per_simd, unsigned long long* queue,

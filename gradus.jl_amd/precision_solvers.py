@@ -45,12 +45,19 @@ def _datum_tracer(m, x, ensemble, max_time, chart, redshift_pf, solver_opts):
 
 
 def find_offset_for_radius(m, x, d, rₑ, θₒ, *, zero_atol=1e-7, α0=0.0, β0=0.0, max_time=None, chart=None,
-                           redshift_pf=None, ensemble=None, return_points=False, **solver_opts):
+                           redshift_pf=None, ensemble=None, return_points=False, root_finder="polished", **solver_opts):
     """find_offset_for_radius(m, x, d, rₑ, θₒ; zero_atol, α₀, β₀) (precision-solvers.jl:238-277): the
     offset r on the observer's image plane, α = r cos θₒ + α₀, β = r sin θₒ + β₀, whose geodesic meets
     the disc at emission radius rₑ; NaN where there is none.  `rₑ` and `θₒ` broadcast: any number of
     problems is solved in the same launches.  Thin discs are the datum plane z = 0, thick discs the
-    plane z = cross_section(d, rₑ) of each problem."""
+    plane z = cross_section(d, rₑ) of each problem.
+
+    `root_finder="polished"` (default): the lock-step safeguarded Newton of transfer_functions.find_offsets_for_radius, every root
+    polished to the integrator's noise floor.  `"device"`: the reference's own iteration (Newton on the dual-number derivative, exit
+    at the first |ρ - rₑ| <= zero_atol), every problem carried from start to finish inside ONE launch (`trace.solve`,
+    gr_offset_solve)."""
+    if root_finder not in ("polished", "device"):
+        raise ValueError(f'root_finder must be "polished" or "device", not {root_finder!r}')
     scalar = np.ndim(rₑ) == 0 and np.ndim(θₒ) == 0
     rₑ, θₒ = (np.array(a, dtype=np.float64).ravel() for a in np.broadcast_arrays(rₑ, θₒ))
     trace, _, _ = _datum_tracer(m, x, ensemble, max_time, chart, redshift_pf, solver_opts)
@@ -61,7 +68,10 @@ def find_offset_for_radius(m, x, d, rₑ, θₒ, *, zero_atol=1e-7, α0=0.0, β0
         heights = np.full(rₑ.size, float(d.height))
     elif not isinstance(d, ThinDisc):
         raise NotImplementedError(f"find_offset_for_radius: no implementation for {type(d).__name__}")
-    r, pts, g = find_offsets_for_radius(trace, rₑ, θₒ, r_min=m.inner_radius(), α0=α0, β0=β0, zero_atol=zero_atol, heights=heights)
+    if root_finder == "device":
+        r, pts, g, _, _ = trace.solve(rₑ, θₒ, heights, r_min=m.inner_radius(), α0=α0, β0=β0, zero_atol=zero_atol)
+    else:
+        r, pts, g = find_offsets_for_radius(trace, rₑ, θₒ, r_min=m.inner_radius(), α0=α0, β0=β0, zero_atol=zero_atol, heights=heights)
     if return_points:
         return (r[0], pts[0], g[0]) if scalar else (r, pts, g)
     return float(r[0]) if scalar else r
@@ -94,7 +104,7 @@ def _cartesian_surface_normal(d, ρ, ϕ=None):
 
 
 def impact_parameters_for_radius_obscured(m, x, d, radius, *, N=500, α0=0.0, β0=0.0, max_time=None, chart=None,
-                                          redshift_pf=None, ensemble=None, **solver_opts):
+                                          redshift_pf=None, ensemble=None, root_finder="polished", **solver_opts):
     """impact_parameters_for_radius_obscured (:347-380): as above for a thick disc, with NaN for the
     part of the ring the disc itself hides: every ray is traced again against the disc and counts as
     visible when it ends where the datum-plane ray did (`_is_visible`, :382-399: squared Cartesian
@@ -103,7 +113,7 @@ def impact_parameters_for_radius_obscured(m, x, d, radius, *, N=500, α0=0.0, β
         raise TypeError("impact_parameters_for_radius_obscured needs a thick disc")
     x = np.asarray(x, dtype=np.float64)
     α, β = impact_parameters_for_radius(m, x, d, radius, N=N, α0=α0, β0=β0, max_time=max_time, chart=chart,
-                                        redshift_pf=redshift_pf, ensemble=ensemble, **solver_opts)
+                                        redshift_pf=redshift_pf, ensemble=ensemble, root_finder=root_finder, **solver_opts)
     ok = np.isfinite(α)
     trace, max_time, chart = _datum_tracer(m, x, ensemble, max_time, chart, redshift_pf, solver_opts)
     thick = device_tracer(m, x, max_time, chart, _redshift_pf(m, x, ensemble, redshift_pf), ensemble, geometry=d, **solver_opts)

@@ -62,12 +62,40 @@ BRACKET_RAYS = 16384        # ... and more levels for small groups, while a laun
 LAUNCH_LOG = None
 
 
+# csrc/gr_offsetsolve.hpp: doubles per problem of a solve (r, the row the iteration ended on, rays traced) and per evaluation of a
+# search (θ after the pole nudge, r, row, rays traced, failure flag)
+SOLVE_ROW = 10
+SEARCH_RECORD = 12
+
+
+def unpack_solve(out):
+    """n x SOLVE_ROW of `gr_offset_solve` -> (r, summaries, g, rows, rays traced): `find_offsets_for_radius_newton_ad`'s tuple plus
+    the counts."""
+    rows = out[:, 1:9].copy()
+    pts = np.zeros(out.shape[0], dtype=SUMMARY_DTYPE)
+    pts["status"] = rows[:, 7].astype(np.int32)
+    pts["x"][:, 0], pts["x"][:, 1], pts["x"][:, 2] = rows[:, 6], rows[:, 1], math.pi / 2
+    return out[:, 0].copy(), pts, rows[:, 0].copy(), rows, out[:, 9].astype(np.int64)
+
+
+def unpack_search(out, iterations):
+    """n x (SEARCH_RECORD (iterations + 1) + 1) of `gr_offset_search` -> (θ, r, rows, rays traced, failed, minima): the first five
+    with one entry per search and evaluation, in call order; an evaluation the search did not reach (it ends at its first root
+    solve without an acceptable offset) is NaN, 0 rays, not failed."""
+    n, K = out.shape[0], iterations + 1
+    rec = out[:, :SEARCH_RECORD * K].reshape(n, K, SEARCH_RECORD)
+    n_rays = np.where(np.isnan(rec[:, :, 10]), 0.0, rec[:, :, 10]).astype(np.int64)
+    return rec[:, :, 0].copy(), rec[:, :, 1].copy(), rec[:, :, 2:10].copy(), n_rays, rec[:, :, 11] == 1.0, out[:, -1].copy()
+
+
 def _launch(ens, name, n, *args):
     """The host call `name` over `n` rays on the ensemble (one context, or shares of the rays on several); a one-context
     launch goes into LAUNCH_LOG when there is one."""
     st = ens.call(name, *args, stats=LAUNCH_LOG is not None)
     if st is not None and not ens.multi:
-        LAUNCH_LOG.append((name, int(n), st.kernel_ms, st.call_ms))
+        # (an offset solve / search traces as many rays per problem as its iteration needs: the launch's own count)
+        rays = int(st.rays) if name.startswith("gr_offset_") else int(n)
+        LAUNCH_LOG.append((name, rays, st.kernel_ms, st.call_ms))
 
 
 def device_tracer(m, x, max_time, chart, redshift_pf, ensemble, geometry=None, callback=None, **solver_opts):
@@ -143,6 +171,48 @@ def device_tracer(m, x, max_time, chart, redshift_pf, ensemble, geometry=None, c
             ens_.set("tangent_pairs", prev)
         return out
 
+    def offset_problems(cls, r_target, heights, *, r_min, α0=0.0, β0=0.0, zero_atol=1e-7, max_iter=50, contrapoint_bias=2.0,
+                        per_wave=0):
+        """the fields gr_offset_problems and gr_offset_searches share (`per_wave`: problems a wave carries, 0 = the library's choice)"""
+        q = cls()
+        q.per_wave = int(per_wave)
+        r_target = np.ascontiguousarray(r_target, dtype=np.float64)
+        q.n, q.r_target = r_target.size, r_target.ctypes.data
+        keep = (r_target,)
+        if heights is not None:
+            if not isinstance(plane, DatumPlane):
+                raise ValueError("per-problem heights need a DatumPlane")
+            h = np.ascontiguousarray(np.broadcast_to(heights, r_target.shape), dtype=np.float64)
+            q.height = h.ctypes.data
+            keep += (h,)
+        q.alpha0, q.beta0, q.zero_atol, q.r_min = float(α0), float(β0), float(zero_atol), float(r_min)
+        q.max_iter, q.contrapoint_bias = int(max_iter), float(contrapoint_bias)
+        return q, keep
+
+    def solve(r_target, θ, heights=None, **setup):
+        """`find_offsets_for_radius_newton_ad` with every problem carried from its cold start to its accepted root by one lane pair
+        of ONE launch (`gr_offset_solve`, csrc/gr_offsetsolve.hpp): -> (r, summaries, g, rows, rays traced per problem)."""
+        θ = np.asarray(θ, dtype=np.float64)
+        cθ, sθ = np.ascontiguousarray(np.cos(θ)), np.ascontiguousarray(np.sin(θ))
+        q, keep = offset_problems(_lib.gr_offset_problems, r_target, heights, **setup)
+        q.cos_theta, q.sin_theta = cθ.ctypes.data, sθ.ctypes.data
+        rs, _ = rayset(np.zeros(0), np.zeros(0), None)
+        out = np.full((q.n, SOLVE_ROW), np.nan)
+        _launch(ens_, "gr_offset_solve", q.n, C.byref(cfg), C.byref(rs), C.byref(pf), C.byref(q), out.ctypes.data)
+        return unpack_solve(out)
+
+    def search(r_target, lower, upper, sign, iterations, heights=None, **setup):
+        """`_golden_section_batch` at depth 1 over `find_offsets_for_radius_newton_ad`, every search -- its iterations + 1 root finds
+        -- carried from start to finish by one lane pair of ONE launch (`gr_offset_search`): -> (θ after the pole nudge, r, rows,
+        rays traced, failure flags), each with one entry per search and evaluation in call order, and the minima found."""
+        q, keep = offset_problems(_lib.gr_offset_searches, r_target, heights, **setup)
+        lower, upper, sign = (np.ascontiguousarray(np.broadcast_to(a, (q.n,)), dtype=np.float64) for a in (lower, upper, sign))
+        q.lower, q.upper, q.sign, q.iterations = lower.ctypes.data, upper.ctypes.data, sign.ctypes.data, int(iterations)
+        rs, _ = rayset(np.zeros(0), np.zeros(0), None)
+        out = np.full((q.n, SEARCH_RECORD * (int(iterations) + 1) + 1), np.nan)
+        _launch(ens_, "gr_offset_search", q.n, C.byref(cfg), C.byref(rs), C.byref(pf), C.byref(q), out.ctypes.data)
+        return unpack_search(out, int(iterations))
+
     # `pf` holds raw pointers into the plunging table's arrays: they live as long as the tracer does, whoever built the point
     # function (a caller that passes a temporary `ConstPointFunctions.redshift(...)` would otherwise leave them dangling)
     trace._keep = (keep_pf, redshift_pf, config, cfg)
@@ -150,6 +220,9 @@ def device_tracer(m, x, max_time, chart, redshift_pf, ensemble, geometry=None, c
     # (every metric has the tangent build of its kernels -- a tabulated one since ABI 8: the tangents ride through the table's own
     # polynomials, as the reference's Duals ride through a user's metric_components)
     trace.tangent = tangent
+    # the whole iteration on the device: root_finder="device"
+    trace.solve = solve
+    trace.search = search
     # rays are nearly free next to a launch's latency here: the solvers may trace points they might not need
     # (BRACKET_DEPTH, GOLDEN_DEPTH); tracers without this mark (the CPU tests' oracle-driven ones) get one level at a time
     trace.speculate = True
@@ -579,7 +652,10 @@ def cunningham_transfer_functions(m, x, d, radii, *, N=80, N_extrema=17, θ_offs
     accepted ray.  `"polished"` (and any tracer without `.tangent`): safeguarded Newton with a difference quotient,
     every root polished to the integrator's noise floor, Jacobians by central differences.  The two agree to 1e-3 in
     the recorded statistics wherever those are well-conditioned; the reference-faithful one reproduces them to
-    1e-5 ... 1e-7 there (tests/test_transfer_functions_host.py)."""
+    1e-5 ... 1e-7 there (tests/test_transfer_functions_host.py).  `"device"` (needs a tracer with `.solve` and `.search`, which the
+    device tracer has; thin discs and datum planes): the `"reference"` iteration and the golden-section searches around it carried
+    problem by problem inside TWO launches (`gr_offset_solve`, `gr_offset_search`) instead of one launch per round -- the same
+    roots, the same samples in the same columns, the same error for the first sample without an offset."""
     thick = hasattr(d, "cross_section")
     if not thick and not isinstance(d, (ThinDisc, DatumPlane)):
         raise NotImplementedError(f"transfer functions: no implementation for {type(d).__name__}")
@@ -592,6 +668,12 @@ def cunningham_transfer_functions(m, x, d, radii, *, N=80, N_extrema=17, θ_offs
             redshift_pf = ConstPointFunctions.redshift(m, x, **({"ensemble": ensemble} if m.metric_id != 0 else {}))
         tracer = device_tracer(m, x, max_time, chart, redshift_pf, ensemble, **solver_opts)
     setup = dict(α0=float(α0), β0=float(β0), zero_atol=float(zero_atol), polish=bool(polish), root_finder=root_finder)
+    if root_finder == "device":
+        if thick:
+            raise NotImplementedError('root_finder="device": a thick disc\'s transfer functions re-trace every root against the disc '
+                                      'and keep the polished lock-step finder')
+        if getattr(tracer, "solve", None) is None or getattr(tracer, "search", None) is None:
+            raise ValueError('root_finder="device" needs a tracer with .solve and .search (device_tracer has them)')
     if thick:
         from .tracing import domain_upper_hemisphere
 
@@ -609,6 +691,11 @@ def cunningham_transfer_functions(m, x, d, radii, *, N=80, N_extrema=17, θ_offs
     θs0 = np.concatenate([np.linspace(-2 * θ_offset, 2 * θ_offset, K), np.linspace(-math.pi / 2, 3 * math.pi / 2, N - 2 * K),
                           np.linspace(math.pi - 2 * θ_offset, math.pi + 2 * θ_offset, K)])
     data = np.full((R, 4, M), np.nan)           # rows: θ, g, J, t  (utils.jl:1-30)
+    if root_finder == "device":
+        gmin_c, gmax_c = _device_route(tracer, m.inner_radius(), setup, radii, θs0, θ_offset, N, M, data)
+        if _raw is not None:
+            _raw.append((data.copy(), gmin_c.copy(), gmax_c.copy()))
+        return _transfer_data(data, gmin_c, gmax_c, radii)
     g, J, t = work(np.repeat(radii, N), np.tile(θs0, R))
     data[:, 0, :N] = θs0
     data[:, 1, :N] = g.reshape(R, N)
@@ -646,7 +733,57 @@ def cunningham_transfer_functions(m, x, d, radii, *, N=80, N_extrema=17, θ_offs
     gmin_c, gmax_c = best[:R], -best[R:]
     if _raw is not None:
         _raw.append((data.copy(), gmin_c.copy(), gmax_c.copy()))
+    return _transfer_data(data, gmin_c, gmax_c, radii)
 
+
+def _device_route(tracer, r_min, setup, radii, θs0, θ_offset, N, M, data):
+    """`root_finder="device"`: what the lock-step route above does in some 200 launches with numpy between them, in two -- one
+    `trace.solve` for the R·N first samples, one `trace.search` for the 2R extremum searches (csrc/gr_offsetsolve.hpp: the same
+    iteration, one problem per lane pair).  Fills `data` in the columns the lock-step route fills and returns (g_min, g_max) as the
+    searches found them."""
+    R = radii.size
+    opts = dict(r_min=r_min, α0=setup["α0"], β0=setup["β0"], zero_atol=setup["zero_atol"])
+
+    def failed(rₑ, θ):
+        return RuntimeError(f"Transfer function integration failed (rₑ={rₑ}, θ={θ}).")
+
+    def gJt(rows):
+        with np.errstate(all="ignore"):
+            J = np.abs(1.0 / (rows[..., 4] * rows[..., 3] - rows[..., 5] * rows[..., 2]))
+        return rows[..., 0], J, rows[..., 6]
+
+    rₑ, θ = np.repeat(radii, N), np.tile(θs0, R)
+    r, _, _, rows, _ = tracer.solve(rₑ, θ, **opts)
+    if np.any(np.isnan(r)):
+        k = int(np.nonzero(np.isnan(r))[0][0])
+        raise failed(rₑ[k], θ[k])
+    data[:, 0, :N] = θs0
+    for row, v in zip((1, 2, 3), gJt(rows)):
+        data[:, row, :N] = v.reshape(R, N)
+
+    # searches 0..R-1: g_min about θ = 0, R..2R-1: g_max about θ = π of radius idx - R; evaluation k of a g_min search is column
+    # N + k, of a g_max search column M - 1 - k
+    n_iter = (M - N) // 2 - 1
+    rr2 = np.concatenate([radii, radii])
+    sign = np.concatenate([np.ones(R), -np.ones(R)])
+    lower = np.concatenate([np.full(R, -θ_offset), np.full(R, math.pi - θ_offset)])
+    upper = np.concatenate([np.full(R, θ_offset), np.full(R, math.pi + θ_offset)])
+    θ2, _, rows2, _, bad, best = tracer.search(rr2, lower, upper, sign, n_iter, **opts)
+    if bad.any():
+        # the first failing sample in call order: the lock-step route evaluates iteration k of every search before iteration k + 1
+        k = int(np.nonzero(bad.any(axis=0))[0][0])
+        j = int(np.nonzero(bad[:, k])[0][0])
+        raise failed(rr2[j], θ2[j, k])
+    g2, J2, t2 = gJt(rows2)
+    for k in range(n_iter + 1):
+        for half, col in ((slice(0, R), N + k), (slice(R, 2 * R), M - 1 - k)):
+            data[:, 0, col], data[:, 1, col], data[:, 2, col], data[:, 3, col] = θ2[half, k], g2[half, k], J2[half, k], t2[half, k]
+    return best[:R], -best[R:]
+
+
+def _transfer_data(data, gmin_c, gmax_c, radii):
+    """the samples of every radius, sorted by θ, and its extrema -> CunninghamTransferData (cunningham-transfer-functions.jl:337-387)"""
+    R = radii.size
     out = []
     for k in range(R):
         dk = data[k][:, ~np.isnan(data[k, 0])]

@@ -553,6 +553,67 @@ int32_t gr_ray_tangent_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset
 int32_t gr_ray_tangent(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays,
                        const gr_pointfunction* pf, double* out /* host, n x 8 */, gr_stats* stats);
 
+/* ---- THE ITERATIONS AROUND THOSE RAYS, on the device (ABI 8): the emission-radius offset solve and the redshift-extremum search of
+ * the Cunningham transfer functions, every problem carried from start to finish by one lane pair of ONE launch (gr_offsetsolve.hpp).
+ *
+ * gr_offset_solve: _find_offset_for_radius (src/tracing/precision-solvers.jl:135-236) for n problems (r_target, θ) -- the offset r
+ * along the image-plane direction (cos θ, sin θ) from (alpha0, beta0) whose ray meets the geometry at ρ = r_target: the cold start
+ * max(20, r_target), Newton with dρ/dr from the dual numbers, the contrapoint and the biased bisection step, the "converge failed"
+ * stop, the six-entry cycle test, the bracket finish (at most 60 bisections), the late bracket after max_iter rounds, the exit at the
+ * first |ρ - r_target| <= zero_atol.  cos_theta / sin_theta come from the caller, so that a host route that forms them itself works
+ * on the same bits.  `rays` gives the observer (x_obs, Mx); its per-ray fields are not read.  out: n x 10 doubles
+ *     r (NaN: no acceptable offset -- r >= 0, |ρ - r_target| <= 1e-4 r_target, the ray met the geometry), the 8 doubles of
+ *     gr_ray_tangent for the ray the iteration ended on, the number of rays the iteration traced.
+ * gr_offset_search: _search_extremal! (src/transfer-functions/cunningham-transfer-functions.jl:390-438), Optim's golden section over
+ * θ on sign·g, for n searches (r_target, lower, upper, sign): the first point lower + GOLDEN (upper - lower), then `iterations` steps;
+ * every visited θ is nudged by +1e-4 when within 1e-4 of 0 or ±π, cos θ and sin θ are formed on the device, and every evaluation is
+ * one whole offset solve.  out: n x (12 (iterations + 1) + 1) doubles -- per evaluation, in call order,
+ *     θ after the nudge, r, the 8 doubles of the ray, rays traced, failure flag (1: no acceptable offset: the search ends there, its
+ *     later records are not written -- the host forms return them as NaN -- and its minimum is NaN),
+ * then the minimum of sign·g found.
+ * A solve's result does not depend on which other problems share its launch or its context.  gr_stats as for gr_ray_tangent.
+ * GR_ERR_UNSUPPORTED for a set with sky rows, for cfg->disc_id other than GR_DISC_THIN / GR_DISC_DATUM and with "precision" 32;
+ * GR_ERR_INVALID_ARGUMENT for a null pointer, a negative n, iterations outside 0 ... 4096, per_wave outside 0 ... 32. */
+typedef struct gr_offset_problems {
+    int64_t n;
+    const double* r_target;   /* n */
+    const double* cos_theta;  /* n */
+    const double* sin_theta;  /* n */
+    const double* height;     /* GR_DISC_DATUM only: n plane heights, one DatumPlane per problem, or NULL for cfg->disc_params[0] */
+    double alpha0, beta0;
+    double zero_atol;         /* the reference's 1e-7 */
+    double r_min;             /* inner_radius(m): a ray that ends within r_min + 1 of it falls short */
+    int64_t max_iter;         /* the reference's 50 */
+    double contrapoint_bias;  /* the reference's 2 */
+    int64_t per_wave;         /* problems a wave carries, 1 ... 32; 0 = the library's choice */
+} gr_offset_problems;
+typedef struct gr_offset_searches {
+    int64_t n;
+    const double* r_target;   /* n */
+    const double* lower;      /* n */
+    const double* upper;      /* n */
+    const double* sign;       /* n: +1 searches the minimum of g, -1 its maximum */
+    const double* height;     /* as above */
+    double alpha0, beta0;
+    double zero_atol;
+    double r_min;
+    int64_t max_iter;
+    double contrapoint_bias;
+    int64_t per_wave;
+    int64_t iterations;       /* golden-section steps behind the first point */
+} gr_offset_searches;
+int32_t gr_offset_solve_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                               const gr_offset_problems* problems /* device arrays */, double* d_out /* n x 10 */,
+                               gr_stats* d_stats, void* hip_stream);
+int32_t gr_offset_solve(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                        const gr_offset_problems* problems, double* out /* host, n x 10 */, gr_stats* stats);
+int32_t gr_offset_search_device(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                                const gr_offset_searches* searches /* device arrays */,
+                                double* d_out /* n x (12 (iterations + 1) + 1) */, gr_stats* d_stats, void* hip_stream);
+int32_t gr_offset_search(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, const gr_pointfunction* pf,
+                         const gr_offset_searches* searches, double* out /* host, n x (12 (iterations + 1) + 1) */,
+                         gr_stats* stats);
+
 /* ---- end points of an impact-parameter ray set: tracegeodesics(m, x, i -> map_impact_parameters(m, x,
  * α[i], β[i]), d, ...; ensemble = EnsembleEndpointThreads()) as impact_parameters_for_radius_obscured
  * (src/tracing/precision-solvers.jl:363-372) and the thick-disc transfer-function workhorse
@@ -999,6 +1060,14 @@ int32_t gr_ray_tangent_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cf
 int32_t gr_redshift_radius_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays,
                                  const gr_pointfunction* pf, double r_min, double r_max,
                                  double* pairs /* host, rays->n x 2 */, gr_stats* stats);
+/* gr_offset_solve / gr_offset_search: the problems are dealt in contiguous shares (multiples of 64), the results land at the
+ * caller's indices and are the bytes one context gives. */
+int32_t gr_offset_solve_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays,
+                              const gr_pointfunction* pf, const gr_offset_problems* problems,
+                              double* out /* host, problems->n x 10 */, gr_stats* stats);
+int32_t gr_offset_search_multi(gr_ctx* const* ctxs, int32_t n, const gr_config* cfg, const gr_rayset* rays,
+                               const gr_pointfunction* pf, const gr_offset_searches* searches,
+                               double* out /* host, searches->n x (12 (iterations + 1) + 1) */, gr_stats* stats);
 /* lineprofile(bins, ε, m, x, d, BinningMethod(); plane) (src/line-profiles.jl:152-198): the rays are dealt block-cyclically
  * (a separable plane: one block = one strip of 8 x 8 tiles, all radii of 8 neighbouring angles, so every device sees every
  * radius; ray arrays: contiguous shares), each device bins its own rays into its own histogram and the host adds the n

@@ -3,7 +3,10 @@
 samples per radius ("a handful of seconds" on the reference's CPU path, docs/src/lineprofiles.md:66) -- on the device
 tracer, with the wall time split into kernel launches and host work.
 
-    python scripts/lineprofile_tf_time.py [root_finder=default|reference]"""
+    python scripts/lineprofile_tf_time.py [root_finder=default|reference|device]
+
+`device`: the offset solves and the extremum searches run problem by problem inside two launches (gr_offset_solve,
+gr_offset_search); their "rays" are the rays the iterations traced, as the launch statistics count them."""
 import json
 import math
 import os
@@ -23,8 +26,8 @@ x = np.array([0.0, 1000.0, math.radians(60), 0.0])        # the documentation's 
 d = G.ThinDisc(0.0, float("inf"))
 bins = np.linspace(0.1, 1.5, 180)
 kw = {}
-if len(sys.argv) > 1 and sys.argv[1] == "reference":
-    kw["root_finder"] = "reference"
+if len(sys.argv) > 1 and sys.argv[1] in ("reference", "device"):
+    kw["root_finder"] = sys.argv[1]
 out = {}
 for rep in range(3):
     TF.LAUNCH_LOG = []
