@@ -55,6 +55,21 @@ class GradusMI355XError(RuntimeError):
         self.code = code
 
 
+class gr_user_module_info_t(C.Structure):
+    """What a compiled metric's kernel module says about itself (its `gr_user_module_info`)."""
+
+    _fields_ = [("abi_version", C.c_int32), ("metric_id", C.c_int32), ("build_id", C.c_int64), ("header_hash", C.c_int64 * 4)]
+
+
+class gr_metric_resources(C.Structure):
+    _fields_ = [("vgprs", C.c_int32), ("scratch_bytes", C.c_int32), ("lds_bytes", C.c_int32), ("max_threads", C.c_int32)]
+
+
+GR_METRIC_COMPILED = 12
+GR_METRIC_MODULE_SLOTS = 16
+MODULE_KERNELS = ("trace_lane", "trace_persistent", "tangent", "tangent_pairs")      # GR_MODULE_KERNEL_*
+
+
 class gr_disc_component(C.Structure):
     _fields_ = [("disc_id", C.c_int32), ("_pad", C.c_int32), ("disc_r_in", C.c_double), ("disc_r_out", C.c_double),
                 ("disc_params", C.c_double * 4)]
@@ -431,6 +446,10 @@ assert POINT_DTYPE.itemsize == 152
 
 # every symbol include/gradus_mi355x.h declares
 EXPORTS = [
+    "gr_metric_module_load",
+    "gr_metric_module_unload",
+    "gr_metric_module_build_id",
+    "gr_metric_module_resources",
     "gr_abi_version",
     "gr_last_error",
     "gr_ctx_create",
@@ -624,6 +643,10 @@ def load():
     L.gr_metric_grid_nodes.argtypes = [gdp, vp, vp]
     L.gr_metric_table_fit.argtypes = [gdp, vp, vp, dp]
     L.gr_metric_table_eval.argtypes = [vp, i64, C.c_double, C.c_double, dp, dp, dp]
+    L.gr_metric_module_load.argtypes = [C.c_char_p, C.POINTER(i64)]
+    L.gr_metric_module_unload.argtypes = [i32]
+    L.gr_metric_module_build_id.argtypes = [i32, C.POINTER(i64)]
+    L.gr_metric_module_resources.argtypes = [i32, cfgp, C.POINTER(gr_metric_resources)]
     for name in EXPORTS:
         if name not in ("gr_last_error",):
             getattr(L, name).restype = i32

@@ -877,8 +877,12 @@ def _plunging_table(m, ensemble):
     from .special_radii import interpolate_plunging_velocities
 
     try:
-        key = (type(m).__name__, int(m.metric_id)) + tuple(float(p) for p in m.abi_params())
-        if m.metric_id == 11:
+        if hasattr(m, "cache_key"):
+            # a compiled metric: its module's build id, not its metric id -- a module slot is reused after an unload
+            key = (type(m).__name__,) + tuple(m.cache_key())
+        else:
+            key = (type(m).__name__, int(m.metric_id)) + tuple(float(p) for p in m.abi_params())
+        if not hasattr(m, "cache_key") and m.metric_id == 11:
             key += (float(m.table[8]),)          # the table's build id (unique per fit; an id() is reused once its object is gone)
     except Exception:          # a metric without flat parameters: no reuse
         return tuple(interpolate_plunging_velocities(m, ensemble=ensemble))

@@ -10,6 +10,7 @@
 //                           counts differ ~4x between rays.
 // Output is one double per ray (fused PointFunction) or one 152-byte GeodesicPoint per ray.
 #include <hip/hip_runtime.h>
+#include <dlfcn.h>
 #include <sys/mman.h>
 
 #include <algorithm>
@@ -106,6 +107,77 @@ const double kEscapeRadiusM[12] = { GR_ESC(0), GR_ESC(1), GR_ESC(2), GR_ESC(3), 
 namespace {
 
 thread_local std::string g_last_error;
+int32_t fail(int32_t code, const std::string& msg);
+
+// ---- GR_METRIC_COMPILED: kernel modules loaded at run time (gr_metric_module_load; kernels_tu.hip -DGR_TU_USER) ----
+// what was hashed into this unit at build time (__graft_entry__.csrc_hash): a module compiled against other sources is refused
+#ifndef GR_CSRC_HASH
+#define GR_CSRC_HASH 0, 0, 0, 0
+#endif
+const int64_t kCsrcHash[4] = { GR_CSRC_HASH };
+std::string hash_hex(const int64_t* w)
+{
+    char buf[65];
+    std::snprintf(buf, sizeof buf, "%016llx%016llx%016llx%016llx", (unsigned long long)w[0], (unsigned long long)w[1],
+                  (unsigned long long)w[2], (unsigned long long)w[3]);
+    return buf;
+}
+typedef hipError_t (*attrs_fn)(int, int, hipFuncAttributes*);
+// the launchers of one metric: a row of the tables above, or a module's
+struct MetricKernels {
+    trace_fn trace64 = nullptr, trace32 = nullptr, tan = nullptr, tan1 = nullptr, sky = nullptr, sky1 = nullptr;
+    path_fn path = nullptr;
+    apply_fn apply = nullptr;
+    classify_fn classify = nullptr;
+    areafactor_fn area = nullptr;
+    offset_fn offset = nullptr;
+    attrs_fn attrs64 = nullptr, attrs_tan = nullptr, attrs_tan1 = nullptr;      // modules only
+    int64_t build_id = 0;                                                       // modules only: what caches key on
+};
+struct ModuleSlot {
+    bool used = false;
+    void* handle = nullptr;
+    MetricKernels k;
+};
+std::mutex g_modules_mu;
+ModuleSlot g_modules[GR_METRIC_MODULE_SLOTS];
+
+// THE accessor of every per-metric dispatch: false for an id that names neither a catalogue metric nor a loaded module
+bool metric_kernels(int32_t id, MetricKernels& out)
+{
+    if (id >= GR_METRIC_KERR && id <= GR_METRIC_TABULATED) {
+        out = MetricKernels{};
+        out.trace64 = kTrace64[id]; out.trace32 = kTrace32[id]; out.tan = kTraceTan[id]; out.tan1 = kTraceTan1[id];
+        out.sky = kTraceSky[id]; out.sky1 = kTraceSky1[id]; out.path = kPath64[id]; out.apply = kApply64[id];
+        out.classify = kClassify64[id]; out.area = kAreaFactor64[id]; out.offset = kOffsetSolve1[id];
+        return true;
+    }
+    if (id < GR_METRIC_COMPILED || id >= GR_METRIC_COMPILED + GR_METRIC_MODULE_SLOTS) return false;
+    std::lock_guard<std::mutex> lock(g_modules_mu);
+    const ModuleSlot& m = g_modules[id - GR_METRIC_COMPILED];
+    if (!m.used) return false;
+    out = m.k;
+    return true;
+}
+bool metric_known(int32_t id)
+{
+    MetricKernels k;
+    return metric_kernels(id, k);
+}
+// the build id of a compiled metric's module, 0 for the catalogue: part of every cache key that holds a metric (slots are reused)
+int64_t metric_build_id(int32_t id)
+{
+    MetricKernels k;
+    return (id >= GR_METRIC_COMPILED && metric_kernels(id, k)) ? k.build_id : 0;
+}
+// Metric::kEscapeRadiusM of a metric id: a compiled metric is never culled (GenericMetricT)
+double metric_escape_radius_m(int32_t id) { return (id >= 0 && id <= GR_METRIC_TABULATED) ? kEscapeRadiusM[id] : HUGE_VAL; }
+// a flavour the metric has no kernel for (a module without the tangent objects, say)
+#define GR_NEED_KERNEL(fn, what)                                                                                       \
+    do {                                                                                                               \
+        if (!(fn)) return fail(GR_ERR_UNSUPPORTED, std::string("this metric has no ") + (what) + " kernels");         \
+    } while (0)
+
 std::atomic<int> g_live_ctx{ 0 };     // contexts alive: the pool of page-locked blocks is emptied when the last one goes
 
 int32_t fail(int32_t code, const std::string& msg)
@@ -265,8 +337,9 @@ int32_t tables_release(gr_ctx* ctx, hipStream_t stream)
 int32_t validate_cfg(const gr_config* cfg)
 {
     if (!cfg) return fail(GR_ERR_INVALID_ARGUMENT, "config is null");
-    if (cfg->metric_id < GR_METRIC_KERR || cfg->metric_id > GR_METRIC_TABULATED)
-        return fail(GR_ERR_UNSUPPORTED, "unknown metric_id " + std::to_string(cfg->metric_id));
+    if (!metric_known(cfg->metric_id))      // the catalogue, or a module that is loaded now (gr_metric_module_load)
+        return fail(GR_ERR_UNSUPPORTED, "unknown metric_id " + std::to_string(cfg->metric_id)
+                                        + (cfg->metric_id >= GR_METRIC_COMPILED ? " (no kernel module is loaded under it)" : ""));
     if (cfg->metric_id == GR_METRIC_TABULATED) {
         const int32_t trc = gr_metric_table_check(cfg->metric_table, cfg->metric_table_n);
         if (trc != GR_OK) return trc;
@@ -467,10 +540,17 @@ int32_t lpt_prepare(gr_ctx* ctx, const Params& p, Cold& cold, hipStream_t stream
     if (ctx->lpt == 1 && tiles >= (tab ? 24 : 6) * resident_waves) return GR_OK;
     // (a tabulated metric: the table's build id is part of the key -- the config itself holds only a pointer, and two metrics
     // fitted into the same buffer on the same grid would otherwise share one learned order)
-    std::vector<unsigned char> key(sizeof(gr_config) + sizeof(gr_plane) + sizeof(gr_range) + sizeof(double));
+    // (a compiled metric: its module's build id is part of the key and its slot number is not -- a slot is reused after an unload)
+    std::vector<unsigned char> key(sizeof(gr_config) + sizeof(gr_plane) + sizeof(gr_range) + sizeof(double) + sizeof(int64_t));
     const double table_id = tab && p.cfg.metric_table ? p.cfg.metric_table[gr_tab::H_BUILD_ID] : 0.0;
+    const int64_t module_id = metric_build_id(p.cfg.metric_id);
     std::memcpy(key.data() + sizeof(gr_config) + sizeof(gr_plane) + sizeof(gr_range), &table_id, sizeof(double));
-    std::memcpy(key.data(), &p.cfg, sizeof(gr_config));
+    std::memcpy(key.data() + sizeof(gr_config) + sizeof(gr_plane) + sizeof(gr_range) + sizeof(double), &module_id, sizeof(int64_t));
+    {
+        gr_config keyed = p.cfg;
+        if (keyed.metric_id >= GR_METRIC_COMPILED) keyed.metric_id = GR_METRIC_COMPILED;
+        std::memcpy(key.data(), &keyed, sizeof(gr_config));
+    }
     std::memcpy(key.data() + sizeof(gr_config), &cold.plane, sizeof(gr_plane));
     std::memcpy(key.data() + sizeof(gr_config) + sizeof(gr_plane), &cold.range, sizeof(gr_range));
     if (key != ctx->lpt_key) {
@@ -877,14 +957,22 @@ static double escape_cull_radius(const gr_ctx* ctx, const Params& p, const Cold&
     if (tangent || ctx->precision == 32) return off;
     const bool misses_ignored = (cold.out_mode == 0 && cold.pf.filter_id == GR_FILTER_INTERSECTED) || cold.out_mode == 2 || cold.out_mode == 3;
     const gr_config& c = p.cfg;
-    if (!misses_ignored || c.metric_id < 0 || c.metric_id > GR_METRIC_TABULATED) return off;
-    return cull_gate_radius(c, kEscapeRadiusM[c.metric_id]);      // the conditions on the configuration: gr_device.hpp
+    if (!misses_ignored || c.metric_id < 0) return off;
+    const double esc = metric_escape_radius_m(c.metric_id);
+    if (!(esc < HUGE_VAL)) return off;      // never culled: every compiled metric, and what the table above says
+    return cull_gate_radius(c, esc);      // the conditions on the configuration: gr_device.hpp
 }
 
 int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t stream)
 {
     Cold cold = cold_in;
     cold.winding_plane = p.cfg.winding_plane;
+    // the metric's launchers: a row of the catalogue's tables or a loaded module's (validate_cfg has seen the id; a module may have
+    // been unloaded since by another thread -- refused here, not crashed on)
+    MetricKernels mk;
+    if (!metric_kernels(p.cfg.metric_id, mk)) return fail(GR_ERR_UNSUPPORTED, "unknown metric_id " + std::to_string(p.cfg.metric_id));
+    if (p.cfg.metric_id >= GR_METRIC_COMPILED && ctx->precision == 32)
+        return fail(GR_ERR_UNSUPPORTED, "a compiled metric has no fp32 kernels (\"precision\" 32): trace it with the fp64 kernels");
     if (p.cfg.metric_id == GR_METRIC_TABULATED && cold_in.src_mode != 1 && !(cold_in.src_mode == 3 && ctx->sky_rows)) {
         // (validate_cfg has compared the chart with the table's range; p.cfg.metric_table is still the caller's host table here.)
         // The observer / source position the rays start from must lie inside the table as well.  (A sky source with sky_rows has no
@@ -988,7 +1076,8 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
     }
     GR_HIP(hipMemcpyAsync(slot, &cold, sizeof(Cold), hipMemcpyHostToDevice, stream));
     if (live_flags) {
-        const hipError_t ce = kClassify64[p.cfg.metric_id](&p, live_flags, tiles, stream);
+        GR_NEED_KERNEL(mk.classify, "tile classification");
+        const hipError_t ce = mk.classify(&p, live_flags, tiles, stream);
         if (ce != hipSuccess) return fail(GR_ERR_HIP, std::string("tile classification launch: ") + hipGetErrorString(ce));
         hipLaunchKernelGGL(k_tile_partition, dim3((unsigned)((tiles + gr_order::kPartitionThreads - 1) / gr_order::kPartitionThreads)),
                            dim3(gr_order::kPartitionThreads), 0, stream, live_flags, tiles,
@@ -1004,7 +1093,8 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
     // on 4 SIMDs per CU -- cannot keep the SIMDs busy either way and is as long as its longest ray: it takes the pairs.
     const bool pairs = tangent && (ctx->tangent_pairs == 1 || (ctx->tangent_pairs == 2 && 2 * p.n <= (int64_t)ctx->n_cu * 4 * 64));
     const bool skycell = cold.out_mode == 6;
-    const trace_fn fn = (skycell ? (pairs ? kTraceSky1 : kTraceSky) : tangent ? (pairs ? kTraceTan1 : kTraceTan) : ctx->precision == 32 ? kTrace32 : kTrace64)[p.cfg.metric_id];
+    const trace_fn fn = skycell ? (pairs ? mk.sky1 : mk.sky) : tangent ? (pairs ? mk.tan1 : mk.tan) : ctx->precision == 32 ? mk.trace32 : mk.trace64;
+    GR_NEED_KERNEL(fn, skycell ? "sky-cell" : tangent ? "tangent" : ctx->precision == 32 ? "fp32" : "fp64 trace");
     p.tangent_norm = (tangent && ctx->tangent_norm) ? 1 : 0;
 #ifdef GR_WAVE_TIMELINE
     p.queue = g_debug_timeline;      // debug builds: 4 x u64 per wave of a one-ray-per-lane launch (gr_kernels.hpp)
@@ -1154,6 +1244,113 @@ int32_t gr_debug_tile_order(gr_ctx* c, uint32_t* perm, int64_t cap, int64_t* til
 }
 
 const char* gr_last_error(void) { return g_last_error.c_str(); }
+
+// ---- GR_METRIC_COMPILED: the registry of kernel modules (include/gradus_mi355x.h, "compiled metrics") ----
+int32_t gr_metric_module_load(const char* path, int64_t* metric_id)
+{
+    if (!path || !metric_id) return fail(GR_ERR_INVALID_ARGUMENT, "gr_metric_module_load: path or metric_id is null");
+    *metric_id = -1;
+    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!h) {
+        const char* why = dlerror();
+        return fail(GR_ERR_INVALID_ARGUMENT, std::string("gr_metric_module_load: ") + (why ? why : "dlopen failed"));
+    }
+    typedef const gr_user_module_info_t* (*info_fn)(void);
+    const info_fn info_of = reinterpret_cast<info_fn>(dlsym(h, "gr_user_module_info"));
+    if (!info_of) {
+        dlclose(h);
+        return fail(GR_ERR_INVALID_ARGUMENT, std::string("gr_metric_module_load: ") + path + " exports no gr_user_module_info: not a metric module");
+    }
+    const gr_user_module_info_t* info = info_of();
+    if (!info || info->abi_version != GR_ABI_VERSION || info->metric_id != GR_METRIC_COMPILED) {
+        const std::string got = info ? std::to_string(info->abi_version) : std::string("none");
+        dlclose(h);
+        return fail(GR_ERR_INVALID_ARGUMENT, std::string("gr_metric_module_load: ") + path + " was compiled for ABI " + got + ", this library is ABI "
+                                             + std::to_string(GR_ABI_VERSION));
+    }
+    if (std::memcmp(info->header_hash, kCsrcHash, sizeof kCsrcHash) != 0) {
+        const std::string got = hash_hex(info->header_hash);
+        dlclose(h);
+        return fail(GR_ERR_INVALID_ARGUMENT, std::string("gr_metric_module_load: ") + path + " was compiled against other kernel sources (hash " + got
+                                             + ") than this library (" + hash_hex(kCsrcHash) + "): compile it again");
+    }
+    MetricKernels k;
+    k.build_id = info->build_id;
+    k.trace64 = reinterpret_cast<trace_fn>(dlsym(h, "gr64_launch_trace_m12"));
+    k.path = reinterpret_cast<path_fn>(dlsym(h, "gr64_launch_path_m12"));
+    k.apply = reinterpret_cast<apply_fn>(dlsym(h, "gr64_launch_apply_m12"));
+    k.classify = reinterpret_cast<classify_fn>(dlsym(h, "gr64_launch_classify_m12"));
+    k.area = reinterpret_cast<areafactor_fn>(dlsym(h, "gr64_launch_areafactor_m12"));
+    k.tan = reinterpret_cast<trace_fn>(dlsym(h, "grt_launch_trace_m12"));
+    k.tan1 = reinterpret_cast<trace_fn>(dlsym(h, "grt1_launch_trace_m12"));
+    k.sky = reinterpret_cast<trace_fn>(dlsym(h, "grts_launch_trace_m12"));
+    k.sky1 = reinterpret_cast<trace_fn>(dlsym(h, "grts1_launch_trace_m12"));
+    k.offset = reinterpret_cast<offset_fn>(dlsym(h, "grv1_launch_offset_m12"));
+    k.attrs64 = reinterpret_cast<attrs_fn>(dlsym(h, "gr64_kernel_attrs_m12"));
+    k.attrs_tan = reinterpret_cast<attrs_fn>(dlsym(h, "grt_kernel_attrs_m12"));
+    k.attrs_tan1 = reinterpret_cast<attrs_fn>(dlsym(h, "grt1_kernel_attrs_m12"));
+    // the fp64 set is what every entry point needs; the other flavours may be absent (their entry points then refuse the metric)
+    if (!k.trace64 || !k.path || !k.apply || !k.classify) {
+        dlclose(h);
+        return fail(GR_ERR_INVALID_ARGUMENT, std::string("gr_metric_module_load: ") + path + " lacks a launcher of the fp64 set "
+                                             "(gr64_launch_trace_m12, _path_, _apply_, _classify_)");
+    }
+    std::lock_guard<std::mutex> lock(g_modules_mu);
+    for (int slot = 0; slot < GR_METRIC_MODULE_SLOTS; ++slot) {
+        if (g_modules[slot].used) continue;
+        g_modules[slot].used = true;
+        g_modules[slot].handle = h;
+        g_modules[slot].k = k;
+        *metric_id = GR_METRIC_COMPILED + slot;
+        return GR_OK;
+    }
+    dlclose(h);
+    return fail(GR_ERR_UNSUPPORTED, "gr_metric_module_load: all " + std::to_string(GR_METRIC_MODULE_SLOTS) + " module slots are taken: unload one");
+}
+
+int32_t gr_metric_module_unload(int32_t metric_id)
+{
+    std::lock_guard<std::mutex> lock(g_modules_mu);
+    const int slot = metric_id - GR_METRIC_COMPILED;
+    if (slot < 0 || slot >= GR_METRIC_MODULE_SLOTS || !g_modules[slot].used)
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_metric_module_unload: no module is loaded under metric_id " + std::to_string(metric_id));
+    // the slot is free; the code stays mapped (no dlclose): a launch in flight may still run it, and its kernels stay registered
+    g_modules[slot] = ModuleSlot{};
+    return GR_OK;
+}
+
+int32_t gr_metric_module_build_id(int32_t metric_id, int64_t* build_id)
+{
+    if (!build_id) return fail(GR_ERR_INVALID_ARGUMENT, "gr_metric_module_build_id: build_id is null");
+    *build_id = 0;
+    MetricKernels k;
+    if (metric_id < GR_METRIC_COMPILED || !metric_kernels(metric_id, k))
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_metric_module_build_id: no module is loaded under metric_id " + std::to_string(metric_id));
+    *build_id = k.build_id;
+    return GR_OK;
+}
+
+int32_t gr_metric_module_resources(int32_t metric_id, const gr_config* cfg, gr_metric_resources* out)
+{
+    if (!out) return fail(GR_ERR_INVALID_ARGUMENT, "gr_metric_module_resources: out is null");
+    std::memset(out, 0, sizeof(gr_metric_resources) * GR_MODULE_KERNEL_COUNT);
+    MetricKernels k;
+    if (metric_id < GR_METRIC_COMPILED || !metric_kernels(metric_id, k))
+        return fail(GR_ERR_INVALID_ARGUMENT, "gr_metric_module_resources: no module is loaded under metric_id " + std::to_string(metric_id));
+    const int disc = cfg ? cfg->disc_id : GR_DISC_THIN;
+    const attrs_fn fns[GR_MODULE_KERNEL_COUNT] = { k.attrs64, k.attrs64, k.attrs_tan, k.attrs_tan1 };
+    for (int q = 0; q < GR_MODULE_KERNEL_COUNT; ++q) {
+        if (!fns[q]) continue;
+        hipFuncAttributes a;
+        std::memset(&a, 0, sizeof(a));
+        GR_HIP(fns[q](q == GR_MODULE_KERNEL_TRACE_PERSISTENT ? 1 : 0, disc, &a));
+        out[q].vgprs = a.numRegs;
+        out[q].scratch_bytes = (int32_t)a.localSizeBytes;
+        out[q].lds_bytes = (int32_t)a.sharedSizeBytes;
+        out[q].max_threads = a.maxThreadsPerBlock;
+    }
+    return GR_OK;
+}
 
 int32_t gr_ctx_create(int32_t device, gr_ctx** out)
 {
@@ -1601,7 +1798,12 @@ int32_t gr_apply_pointfunction_device(gr_ctx* ctx, const gr_config* cfg, const g
     ctx->cold_next = (ctx->cold_next + 1) % ctx->queue_slots;
     GR_HIP(hipMemcpyAsync(slot, &cd, sizeof(Cold), hipMemcpyHostToDevice, stream));
     p.cold = slot;
-    GR_HIP(kApply64[cfg->metric_id](&p, d_points, max_time, d_out, stream));
+    {
+        MetricKernels mk;
+        if (!metric_kernels(cfg->metric_id, mk)) return fail(GR_ERR_UNSUPPORTED, "unknown metric_id " + std::to_string(cfg->metric_id));
+        GR_NEED_KERNEL(mk.apply, "point-function");
+        GR_HIP(mk.apply(&p, d_points, max_time, d_out, stream));
+    }
     GR_HIP(hipGetLastError());
     if ((cd.pf.n_plunge > 0 || cfg->metric_id == GR_METRIC_TABULATED) && (rc = tables_release(ctx, stream)) != GR_OK) return rc;
     return GR_OK;
@@ -1635,7 +1837,12 @@ int32_t gr_disc_area_factor_device(gr_ctx* ctx, const gr_config* cfg, const gr_p
     ctx->cold_next = (ctx->cold_next + 1) % ctx->queue_slots;
     GR_HIP(hipMemcpyAsync(slot, &cd, sizeof(Cold), hipMemcpyHostToDevice, stream));
     p.cold = slot;
-    GR_HIP(kAreaFactor64[cfg->metric_id](&p, d_r, d_out, stream));
+    {
+        MetricKernels mk;
+        if (!metric_kernels(cfg->metric_id, mk)) return fail(GR_ERR_UNSUPPORTED, "unknown metric_id " + std::to_string(cfg->metric_id));
+        GR_NEED_KERNEL(mk.area, "area-factor");
+        GR_HIP(mk.area(&p, d_r, d_out, stream));
+    }
     GR_HIP(hipGetLastError());
     if (tables && (rc = tables_release(ctx, stream)) != GR_OK) return rc;
     return GR_OK;
@@ -1685,7 +1892,12 @@ int32_t gr_trace_paths(gr_ctx* ctx, const gr_config* cfg, const double* x, int64
     ctx->cold_next = (ctx->cold_next + 1) % ctx->queue_slots;
     GR_HIP(hipMemcpyAsync(slot, &cd, sizeof(Cold), hipMemcpyHostToDevice, ctx->stream));
     p.cold = slot;
-    GR_HIP(kPath64[cfg->metric_id](&p, d_path, cap, d_n, ctx->stream));
+    {
+        MetricKernels mk;
+        if (!metric_kernels(cfg->metric_id, mk)) return fail(GR_ERR_UNSUPPORTED, "unknown metric_id " + std::to_string(cfg->metric_id));
+        GR_NEED_KERNEL(mk.path, "path");
+        GR_HIP(mk.path(&p, d_path, cap, d_n, ctx->stream));
+    }
     GR_HIP(hipGetLastError());
     if ((p.disc_table || p.chart_table || cfg->metric_id == GR_METRIC_TABULATED) && (rc = tables_release(ctx, ctx->stream)) != GR_OK) return rc;
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "row counters are copied as int64");
@@ -2023,7 +2235,10 @@ int32_t offset_launch(gr_ctx* ctx, const gr_config* cfg, const gr_rayset* rays, 
         p.stats = ctx->d_stat_part + (size_t)ctx->stat_next * gr_fold::kStatWords;
         ctx->stat_next = (ctx->stat_next + 1) % ctx->queue_slots;
     }
-    const hipError_t le = kOffsetSolve1[p.cfg.metric_id](&p, &d, c.search ? 1 : 0, stream);
+    MetricKernels mk;
+    if (!metric_kernels(p.cfg.metric_id, mk)) return fail(GR_ERR_UNSUPPORTED, "unknown metric_id " + std::to_string(p.cfg.metric_id));
+    GR_NEED_KERNEL(mk.offset, "offset-solve");
+    const hipError_t le = mk.offset(&p, &d, c.search ? 1 : 0, stream);
     if (le != hipSuccess) return fail(GR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(le));
     if (caller_stats) {
         hipLaunchKernelGGL(k_stats_fold, dim3(1), dim3(64), 0, stream, p.stats, caller_stats);

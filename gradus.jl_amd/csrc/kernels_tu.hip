@@ -7,6 +7,8 @@
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN[1] -DGR_TU_SKY -c kernels_tu.hip -o kernelssky[1]_m<id>.o    (the two tangent shapes for sky cells)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_AREA -c kernels_tu.hip -o kernelsarea_m<id>.o                   (fp64, k_disc_area_factor alone)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN1 -DGR_TU_SOLVE -c kernels_tu.hip -o kernelssolve1_m<id>.o    (pairs; k_offset_solve, k_offset_search alone)
+//     hipcc ... -DGR_TU_METRIC=12 -DGR_TU_USER -DGR_USER_COMPONENTS_FILE=\"<body>\" [one of the flag sets above but fp32] ...  (a user's metric:
+//               gr_usermetric.hpp; the seven objects are linked into a module of their own, not into the library -- metrics.CompiledMetric)
 //
 // so that every metric's kernels hold only that metric's component function (gr_device.hpp, GenericMetricT) and the
 // library builds on all cores at once (__graft_entry__.build_hip).  The fp32 objects are the same source with
@@ -81,10 +83,21 @@
 #if defined(GR_TU_SOLVE)
 #include "gr_offsetsolve.hpp"
 #endif
+#if defined(GR_TU_USER)
+// GR_METRIC_COMPILED: the component function of GenericMetricT<12> comes from the file named on the compile line.  Its explicit
+// specialisation has to stand before the launchers below instantiate the kernels with it.
+#include "gr_usermetric.hpp"
+#endif
 
 #define GR_CAT3_(a, b, c) a##b##c
 #define GR_CAT3(a, b, c) GR_CAT3_(a, b, c)
 #define GR_TU_NAME(what) GR_CAT3(GR_TU_PREFIX, what, GR_TU_METRIC)
+// the library's own objects are linked with the host unit (C++ names); a module is found by dlsym: C names
+#if defined(GR_TU_USER)
+#define GR_TU_EXPORT extern "C"
+#else
+#define GR_TU_EXPORT
+#endif
 
 namespace {
 typedef GR_NS::MetricOf<GR_TU_METRIC>::type TuMetric;
@@ -94,7 +107,7 @@ typedef GR_NS::MetricOf<GR_TU_METRIC>::type TuMetric;
 // γ(r) A(r) of the disc at n radii (k_disc_area_factor): the emissivity weight of a resident sky's (r, ϕ) map (gr_sky_bin_grid).
 // An object of its own (the GR_TU_SKY precedent): inside the fp64 object it left every trace kernel as it was but moved the
 // operands of k_tile_classify (47 of 2004 instructions, Kerr; scripts/isa_compare.py).
-hipError_t GR_TU_NAME(_launch_areafactor_m)(const void* params, const double* r, double* out, hipStream_t stream)
+GR_TU_EXPORT hipError_t GR_TU_NAME(_launch_areafactor_m)(const void* params, const double* r, double* out, hipStream_t stream)
 {
     return GR_NS::launch_areafactor_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), r, out, stream);
 }
@@ -102,13 +115,13 @@ hipError_t GR_TU_NAME(_launch_areafactor_m)(const void* params, const double* r,
 // The offset solve and the extremum search of the transfer functions, one problem per lane pair (gr_offsetsolve.hpp: k_offset_solve,
 // k_offset_search).  An object of its own (the GR_TU_SKY precedent): the pair-shape trace kernel of kernelstan1_m<id>.o stays as
 // it is, and this object carries no trace kernel.  `dev` is a gr_os::OffsetDev.
-hipError_t GR_TU_NAME(_launch_offset_m)(const void* params, const void* dev, int search, hipStream_t stream)
+GR_TU_EXPORT hipError_t GR_TU_NAME(_launch_offset_m)(const void* params, const void* dev, int search, hipStream_t stream)
 {
     GR_NS::Params p = *reinterpret_cast<const GR_NS::Params*>(params);
     return GR_NS::launch_offset_metric<TuMetric>(p, *reinterpret_cast<const gr_os::OffsetDev*>(dev), search != 0, stream);
 }
 #else
-hipError_t GR_TU_NAME(_launch_trace_m)(int kernel, int block, int n_cu, int waves_per_simd, unsigned long long* queue,
+GR_TU_EXPORT hipError_t GR_TU_NAME(_launch_trace_m)(int kernel, int block, int n_cu, int waves_per_simd, unsigned long long* queue,
                                        const void* params, hipStream_t stream)
 {
     GR_NS::Params p = *reinterpret_cast<const GR_NS::Params*>(params);
@@ -118,19 +131,35 @@ hipError_t GR_TU_NAME(_launch_trace_m)(int kernel, int block, int n_cu, int wave
 #endif
 
 #if !defined(GR_TU_F32) && !defined(GR_TU_TAN) && !defined(GR_TU_TAN1) && !defined(GR_TU_AREA)
-hipError_t GR_TU_NAME(_launch_path_m)(const void* params, double* d_path, int64_t cap, unsigned long long* d_n, hipStream_t stream)
+GR_TU_EXPORT hipError_t GR_TU_NAME(_launch_path_m)(const void* params, double* d_path, int64_t cap, unsigned long long* d_n, hipStream_t stream)
 {
     return GR_NS::launch_path_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), d_path, cap, d_n, stream);
 }
 
-hipError_t GR_TU_NAME(_launch_apply_m)(const void* params, const gr_point* pts, double max_time, double* out, hipStream_t stream)
+GR_TU_EXPORT hipError_t GR_TU_NAME(_launch_apply_m)(const void* params, const gr_point* pts, double max_time, double* out, hipStream_t stream)
 {
     return GR_NS::launch_apply_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), pts, max_time, out, stream);
 }
 
 // the live-first tile order's flags for the launch `params` describes (gr_tile_order.hpp); an error for a metric without the start cull
-hipError_t GR_TU_NAME(_launch_classify_m)(const void* params, uint8_t* flags, int64_t tiles, hipStream_t stream)
+GR_TU_EXPORT hipError_t GR_TU_NAME(_launch_classify_m)(const void* params, uint8_t* flags, int64_t tiles, hipStream_t stream)
 {
     return GR_NS::launch_classify_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), flags, tiles, stream);
 }
+#endif
+
+#if defined(GR_TU_USER) && !defined(GR_TU_AREA) && !defined(GR_TU_SOLVE) && !defined(GR_TU_SKY)
+// a module's trace kernels answer for their registers and scratch (gr_metric_module_resources): kernel 0 = lane, 1 = persistent
+GR_TU_EXPORT hipError_t GR_TU_NAME(_kernel_attrs_m)(int kernel, int disc_id, hipFuncAttributes* out)
+{
+    return GR_NS::kernel_attrs_metric<TuMetric>(kernel, disc_id, out);
+}
+#if !defined(GR_TU_TAN) && !defined(GR_TU_TAN1)
+// ... and the fp64 unit says what the module was made from (include/gradus_mi355x.h)
+extern "C" const gr_user_module_info_t* gr_user_module_info(void)
+{
+    static const gr_user_module_info_t info = { GR_ABI_VERSION, GR_METRIC_COMPILED, GR_USER_BUILD_ID, { GR_CSRC_HASH } };
+    return &info;
+}
+#endif
 #endif

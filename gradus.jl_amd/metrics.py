@@ -842,6 +842,15 @@ class TabulatedMetric(AbstractStaticAxisSymmetric):
         return generic_isco(self)
 
 
+def __getattr__(name):
+    # metrics.CompiledMetric / metrics.UntraceableMetric live in compiled_metric.py (which imports this module)
+    if name in ("CompiledMetric", "UntraceableMetric"):
+        from . import compiled_metric
+
+        return getattr(compiled_metric, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def kerr_isco(M, a):
     """__BoyerLindquistFO.isco -- Bardeen et al. (1972) eq. 2.21; kerr-metric-first-order.jl:297-337."""
     x = a / M

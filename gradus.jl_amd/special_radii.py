@@ -70,6 +70,14 @@ class Jet:
         d = 0.5 * self.d / s
         return Jet(s, d, (0.5 * self.dd - d * d) / s)
 
+    def exp(self):
+        e = np.exp(self.v)
+        return Jet(e, e * self.d, e * (self.dd + self.d * self.d))
+
+    def log(self):
+        i = 1.0 / self.v
+        return Jet(np.log(self.v), self.d * i, (self.dd - self.d * self.d * i) * i)
+
 
 def _energy_jet(m, r):
     """CircularOrbits.energy(m, r) = -u_t with its r-derivative (circular-orbits.jl:11-48)."""

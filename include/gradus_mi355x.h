@@ -75,8 +75,14 @@ enum {
      * the samples into piecewise polynomials (total degree 5 on patches geometric in r - r0 and uniform in θ), and the kernels
      * evaluate the five components and their (∂r, ∂θ) derivatives from that table (gr_config.metric_table; params unused).
      * See "tabulated metrics" below.  Every flavour of the kernels ("precision" 32: the table stays fp64 and is evaluated in double, the step is fp32). */
-    GR_METRIC_TABULATED = 11
+    GR_METRIC_TABULATED = 11,
+    /* A metric whose component function was compiled into a kernel module of its own and loaded at run time
+     * (gr_metric_module_load, "compiled metrics" below): ids GR_METRIC_COMPILED ... GR_METRIC_COMPILED + GR_METRIC_MODULE_SLOTS - 1,
+     * one per loaded module.  params = the P[0..5] the module's component function reads.  fp64 and tangent kernels only:
+     * GR_ERR_UNSUPPORTED with "precision" 32. */
+    GR_METRIC_COMPILED = 12
 };
+#define GR_METRIC_MODULE_SLOTS 16
 
 /* accretion geometry
  *   THIN             ThinDisc        src/geometry/discs/thin-disc.jl:9-26       disc_r_in, disc_r_out, gtol
@@ -1047,6 +1053,54 @@ int32_t gr_metric_table_fit(const gr_metric_grid* grid, const double* samples /*
  * table against the caller's own Jacobian (Julia: Gradus.metric_jacobian) before tracing with it */
 int32_t gr_metric_table_eval(const double* table, int64_t table_n, double r, double theta, double* g /* 5 */, double* dr /* 5 */,
                              double* dth /* 5 */);
+
+/* ---- compiled metrics (additive within ABI 8; GR_METRIC_COMPILED): a user's component function as kernels of its own ----
+ * The tabulated route carries a metric across this ABI as samples.  This one carries it as CODE: the five components written
+ * as the body of GenericMetricT<GR_METRIC_COMPILED>::components (csrc/gr_usermetric.hpp: + - * on typed dual numbers, inv_,
+ * dsqrt, dexp, dlog, dpowi<N>, sin θ and cos θ as `s` and `c`, run-time parameters as P[0..5], results through dput(g[i], ...)),
+ * compiled with the library's own kernels_tu.hip (-DGR_TU_METRIC=12 -DGR_TU_USER -DGR_USER_COMPONENTS_FILE=\"...\", the seven
+ * flavours fp64 / area factor / two tangent shapes / two sky-cell shapes / offset solve) and linked into ONE shared module that
+ * exports the launchers gr64_launch_{trace,path,apply,classify,areafactor}_m12, grt_, grt1_, grts_, grts1_launch_trace_m12,
+ * grv1_launch_offset_m12 and gr_user_module_info.  The Python host writes the body from a numpy callable
+ * (metrics.CompiledMetric); any tool that emits C expressions can.
+ *
+ *   int64_t id;  gr_metric_module_load("/path/to/module.so", &id);     // GR_METRIC_COMPILED + slot
+ *   cfg.metric_id = (int32_t)id;  cfg.params[0..5] = ...;                        // then every entry point as for the catalogue
+ *   gr_metric_module_unload(id);
+ *
+ * A compiled metric is traced by eval() + the generic contraction like the catalogue's dual-number form, takes no miss cull
+ * (like every metric but Kerr) and has no fp32 flavour.  Learned state that is keyed by a configuration (the longest-first
+ * tile order) keys a compiled metric by its module's BUILD ID, not by its slot: slots are reused after an unload. */
+typedef struct gr_user_module_info_t {
+    int32_t abi_version;      /* GR_ABI_VERSION the module was compiled against */
+    int32_t metric_id;        /* GR_METRIC_COMPILED */
+    int64_t build_id;         /* > 0, unique per generated source + kernel sources + flags + compiler: what caches key on */
+    int64_t header_hash[4];   /* sha256 of the csrc/ sources and this header the module was compiled against, as four words */
+} gr_user_module_info_t;
+/* every module exports `gr_user_module_info`: a C function without arguments that returns a pointer to one of these */
+
+typedef struct gr_metric_resources {
+    int32_t vgprs;            /* vector registers per lane (hipFuncGetAttributes numRegs) */
+    int32_t scratch_bytes;    /* private memory per lane: > 0 means the kernel spills */
+    int32_t lds_bytes;        /* static LDS per workgroup */
+    int32_t max_threads;      /* maxThreadsPerBlock */
+} gr_metric_resources;
+enum { GR_MODULE_KERNEL_TRACE_LANE = 0, GR_MODULE_KERNEL_TRACE_PERSISTENT = 1, GR_MODULE_KERNEL_TANGENT = 2,
+       GR_MODULE_KERNEL_TANGENT_PAIRS = 3, GR_MODULE_KERNEL_COUNT = 4 };
+
+/* dlopen `path` (RTLD_LOCAL), check gr_user_module_info against this library (ABI version and header hash must be equal:
+ * GR_ERR_INVALID_ARGUMENT with both values in the message otherwise; so for a file that is not a module or lacks a launcher of
+ * the fp64 set) and keep it in a process-wide registry of GR_METRIC_MODULE_SLOTS slots.  *metric_id = GR_METRIC_COMPILED + slot.
+ * GR_ERR_UNSUPPORTED when every slot is taken.  Needs no device.  Thread-safe. */
+int32_t gr_metric_module_load(const char* path, int64_t* metric_id);
+/* free the slot (the module's code stays mapped: a launch in flight may still be running it).  A config that names the id
+ * afterwards is refused (GR_ERR_UNSUPPORTED), like any unknown metric_id.  GR_ERR_INVALID_ARGUMENT for an id that is not loaded. */
+int32_t gr_metric_module_unload(int32_t metric_id);
+/* the module's build id (0 and GR_ERR_INVALID_ARGUMENT for an id that is not loaded) */
+int32_t gr_metric_module_build_id(int32_t metric_id, int64_t* build_id);
+/* registers and scratch of the module's trace kernels as compiled for `cfg` (the kernels are instantiated per disc type):
+ * out[GR_MODULE_KERNEL_*].  Needs a device (hipFuncGetAttributes). */
+int32_t gr_metric_module_resources(int32_t metric_id, const gr_config* cfg, gr_metric_resources* out /* GR_MODULE_KERNEL_COUNT */);
 
 /* ---- ONE host thread, SEVERAL devices, ray sets (see gr_render_multi for the shape every *_multi call has) ---- */
 /* Ray sets with one output row per ray (gr_rayset_endpoints, gr_ray_summary, gr_ray_tangent, gr_redshift_radius): contiguous
