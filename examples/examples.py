@@ -1,6 +1,6 @@
 """A selection of the reference's `docs/src/examples.md` -- shadow, redshift image, line profile,
 reverberation (binned and semi-analytic), interpolated redshift, disc geometries, circular orbits,
-ISCO, horizons, transfer functions -- with `ensemble = EnsembleMI355X()`.  Plots are replaced by
+ISCO, horizons, transfer functions, covariant radiative transfer -- with `ensemble = EnsembleMI355X()`.  Plots are replaced by
 printed summaries.   python examples/examples.py   (needs an MI355X)"""
 import math
 import os
@@ -216,3 +216,13 @@ lit = sky.device_occupancy(r_bins, ϕ_bins) != 0
 print(f"adaptive_solve: {iterations} iterations, {sky.n_cells} cells, {lit.mean():.1%} of 500 x 500 (r, ϕ) bins lit ({dt:.2f} s)")
 ε = G.bin_emissivity_grid(m, d, r_bins, ϕ_bins, sky)          # (reads the host mirror, brought up to date here)
 print(f"bin_emissivity_grid on the solved sky: {np.count_nonzero(ε)} bins lit")
+
+# ## Covariant radiative transfer: the intensity carried through a Polish doughnut of constant emissivity
+m = G.KerrMetric(M=1.0, a=1.0)
+x = np.array([0.0, 1000.0, math.radians(80), 0.0])
+d = G.PolishDoughnut(m)
+# (the reference sets `emissivity_coefficient(::AbstractMetric, ::PolishDoughnut, x, ν) = 0.1`; its pf reads gp.aux[1])
+trace = G.TraceRadiativeTransfer(I0=0.0, medium=G.PowerLawMedium(j0=0.1))
+(_, _, img), dt = timed(lambda: G.rendergeodesics(m, x, d, 2000.0, alpha_lims=(-25, 25), beta_lims=(-15, 18), pf=CPF.intensity(),
+                                                  trace=trace, ensemble=ens))
+print(f"radiative transfer: {(img > 0).sum()} of {img.size} pixels see the doughnut, I up to {img.max():.3f} ({dt:.2f} s)")

@@ -201,6 +201,12 @@ class gr_pointfunction(C.Structure):
     ]
 
 
+class gr_transfer(C.Structure):
+    """TraceRadiativeTransfer's launch-uniform block: ν₀, I₀, the power-law medium and the ISCO (include/gradus_mi355x.h)"""
+
+    _fields_ = [(k, C.c_double) for k in ("nu0", "I0", "a0", "j0", "pa", "pj", "sa", "sj", "r_isco", "reserved")]
+
+
 class gr_rayset(C.Structure):
     _fields_ = [
         ("x_obs", C.c_double * 4),
@@ -532,6 +538,9 @@ EXPORTS = [
     "gr_metric_grid_nodes",
     "gr_metric_table_fit",
     "gr_metric_table_eval",
+    "gr_transfer_render_device",
+    "gr_transfer_render",
+    "gr_transfer_endpoints",
 ]
 
 _lib = None
@@ -567,6 +576,10 @@ def load():
     L.gr_render_endpoints.argtypes = [vp, cfgp, plp, rgp, vp, stp]
     L.gr_trace_endpoints_device.argtypes = [vp, cfgp, vp, i64, vp, i64, vp, vp, vp]
     L.gr_trace_endpoints.argtypes = [vp, cfgp, vp, i64, vp, i64, vp, stp]
+    trp = C.POINTER(gr_transfer)
+    L.gr_transfer_render_device.argtypes = [vp, cfgp, trp, plp, pfp, rgp, vp, vp, vp]
+    L.gr_transfer_render.argtypes = [vp, cfgp, trp, plp, pfp, rgp, vp, stp]
+    L.gr_transfer_endpoints.argtypes = [vp, cfgp, trp, vp, i64, vp, i64, vp, vp, stp]
     L.gr_trace_path.argtypes = [vp, cfgp, vp, vp, i64, vp, C.POINTER(i64), vp]
     L.gr_trace_paths.argtypes = [vp, cfgp, vp, i64, vp, i64, i64, vp, vp, vp]
     rsp, bnp = C.POINTER(gr_rayset), C.POINTER(gr_binning)

@@ -2610,8 +2610,15 @@ struct Cold {
     // (gr_sky_cells) and each brings GR_SKYCELL_SEED doubles -- ∂v/∂θ[4], ∂v/∂ϕ[4] of its unconstrained velocity, then sin θ -- or
     // null: rays without a seed.  (Last: nothing before it moves.)
     const double* v_tan;
+#if defined(GR_RADTRANS) || defined(GR_RADTRANS_LAYOUT)
+    // TraceRadiativeTransfer (kernels_tu.hip, GR_TU_RT; the host unit compiles the layout alone): the launch-uniform block of the
+    // medium, and where ray j's intensity goes beside its end-point record (out_mode 1; null: nowhere).  (Last, and behind the
+    // flavour's macro: every other object sees the block as it was.)
+    const gr_transfer* transfer;      // device
+    double* intensity;                // device, n doubles
+#endif
 };
-constexpr int GR_SKYCELL_SEED = 9;     // doubles per ray behind Cold::v_tan
+constexpr int GR_SKYCELL_SEED = 9;    // doubles per ray behind Cold::v_tan
 constexpr int GR_SKYCELL_ROW = 6;      // doubles per ray of out_mode 6: (t, r, ϕ, g, J, status), the reference's CoronaGridValues
 
 // the error norm's scaled residuals in single precision: the fp64 device kernels only (see Ray::step)
@@ -3017,6 +3024,13 @@ struct Ray {
     // that step; and whether the kernel runs the due tests wave-wide after the step (mesh_phase) instead of inside it
     real qprev[3], qnew[3];
     int32_t mesh_need, mesh_cb_term, mesh_coop;
+#ifdef GR_RADTRANS
+    // TraceRadiativeTransfer (radiative-transfer-problem.jl): the ninth state component and its seven stage derivatives (dI[0]
+    // is FSAL like A[0]); whether the ray is inside the geometry (within_geometry[1]); how many surface crossings it has made
+    real I;
+    real dI[7];
+    int32_t within, ncross;
+#endif
 #ifdef GR_HOST_HARNESS
     real dbg_e2;
     real dbg_dmax;          // per attempted step: largest |θ_stage - θ_base| (harness statistics)
@@ -3245,6 +3259,116 @@ struct Ray {
         const real x2 = cb * v2 - sb * c, x3 = sb * v2 + cb * c;     // R = [1 0 0; 0 cβ -sβ; 0 sβ cβ]
         return disc_cond(p, r, sqrt_fast(GR_FMA(v1, v1, x2 * x2)), x3);
     }
+
+    // the ContinuousCallback's condition as the trace poses it: the geometry's distance, and under TraceRadiativeTransfer
+    // `within ? -dist : dist` (intersection_callbacks(…, ::TraceRadiativeTransfer, …), radiative-transfer-problem.jl:112-115) --
+    // positive on the side the ray is on, whichever that is
+    GR_DEV real trace_cond4(const Params& p, real r, real s, real c, real phi) const
+    {
+#ifdef GR_RADTRANS
+        const real d = disc_cond4(p, r, s, c, phi);
+        return within ? -d : d;
+#else
+        return disc_cond4(p, r, s, c, phi);
+#endif
+    }
+
+#ifdef GR_RADTRANS
+    // ---- TraceRadiativeTransfer (src/tracing/radiative-transfer-problem.jl) ----
+    // TERMINATION.  The ray does not end on the surface, so the step loop must end by something else, whatever the medium does:
+    //   * every pass through step() either returns true or adds one to nacc + nrej, and step() returns true once that sum has
+    //     reached maxiters32 (its first test).  A crossing happens inside an ACCEPTED step -- the step that brackets it was counted
+    //     in nacc before the root is looked for -- so every crossing counts against maxiters, also one whose root is Θ = 0;
+    //   * the root finder is a bounded loop (48 iterations);
+    //   * a ray is allowed kMaxCrossings crossings: one more sets GR_FLAG_MAXITERS and ends it.  A grazing ray cannot re-trigger at
+    //     Θ = 0 for ever: it would be ended here after 65 steps, and by maxiters in any case;
+    //   * no test of the loop reads I.  A NaN intensity makes the error norm NaN, which is the rejected branch's GR_FLAG_NAN exit --
+    //     an exit more, never one fewer.
+    static constexpr int kMaxCrossings = 64;
+
+    // fluid_velocity (radiative-transfer-problem.jl:13-20): CircularOrbits.fourvelocity(m, ρ) outside r_isco, and
+    // CircularOrbits.plunging_fourvelocity(m, ρ) at and inside it (circular-orbits.jl:128-148) -- the SAME circular-orbit v^t, v^ϕ at ρ
+    // with v^r = -√|nom / (-g_rr)|, nom = g^tt E² - 2 g^tϕ E L + g^ϕϕ L² + 1 (not the interpolated plunge of redshift_pf).  Where the
+    // circular orbit has no real value the NaN goes through to I.
+    static GR_DEV void rt_fluid_velocity(const Metric& m, real rho, real r_isco, real& vt, real& vr, real& vp)
+    {
+        real g[5], j1[5], j2[5], gi[5];
+        metric_eval(m, rho, (real)1.5707963267948966, (real)1.0, (real)0.0, g, j1, j2, gi);
+        const real Dl = GR_SQRT(j1[4] * j1[4] - j1[0] * j1[3]);
+        const real Om = -(j1[4] - Dl) / j1[3];
+        const real A = -(Om * gi[0] - gi[4]);
+        const real B = (Om * gi[4] - gi[3]);
+        const real den = B * B * gi[0] + 2.0 * A * B * gi[4] + A * A * gi[3];
+        const real d = -(real)sgn(den) * GR_SQRT(1.0 / GR_FABS(den));
+        const real ut = B * d, up = A * d;
+        vt = gi[0] * ut + gi[4] * up;
+        vp = gi[4] * ut + gi[3] * up;
+        vr = 0.0;
+        if (!(rho > r_isco)) {
+            const real E = -ut, L = up;
+            const real nom = gi[0] * E * E - 2.0 * gi[4] * E * L + gi[3] * L * L + 1.0;
+            vr = -GR_SQRT(GR_FABS(nom / (-g[1])));
+        }
+    }
+
+    // radiative_transfer (radiative-transfer-problem.jl:1-11) at position (r, θ) with photon momentum k and intensity Iv:
+    // dI/dλ = s (-a_ν I + j_ν / ν³), s = -g_μν(x) k^μ u^ν with g at the PHOTON's position and u the fluid's velocity at ρ = r |sin θ|,
+    // ν = ν₀ s, a_ν = a0 ρ^-pa ν^-sa, j_ν = j0 ρ^-pj ν^-sj (gr_transfer).  Called only while `within` is set: a wave none of whose lanes is
+    // inside the geometry branches round it, and its stages cost what the plain trace's cost.
+    GR_DEV real rt_rhs(const Metric& m, const Params& p, real r, real th, real s, real c, real kt, real kr, real kp, real Iv) const
+    {
+        const gr_transfer& tr = *cold_of(p).transfer;
+        const real rho = r * GR_FABS(s);
+        real ut, ur, up;
+        rt_fluid_velocity(m, rho, (real)tr.r_isco, ut, ur, up);
+        real g[5];
+        metric_comps(m, r, th, s, c, g);
+        const real ds = -((g[0] * kt + g[4] * kp) * ut + g[1] * kr * ur + (g[4] * kt + g[3] * kp) * up);
+        const real nu = (real)tr.nu0 * ds;
+        const real an = (real)tr.a0 * GR_POW(rho, -(real)tr.pa) * GR_POW(nu, -(real)tr.sa);
+        const real jn = (real)tr.j0 * GR_POW(rho, -(real)tr.pj) * GR_POW(nu, -(real)tr.sj);
+        return ds * (-an * Iv + jn / (nu * nu * nu));
+    }
+
+    // I on the dense output at Θ of the step (x, v, I, h, A, dI still the step's start): the interpolant of a first-order component,
+    // I(Θ) = I + h Σ_i b_i(Θ) dI_i (the velocity components' form, dense_coeffs)
+    GR_DEV real rt_dense_I(real hh, real th) const
+    {
+        real C[4];
+#pragma unroll
+        for (int mm = 0; mm < 4; ++mm) {
+            real acc = 0.0;
+#pragma unroll
+            for (int i = 0; i < 7; ++i)
+                if (Ts::R[i][mm] != 0.0) acc = GR_FMA(Ts::R[i][mm], dI[i], acc);
+            C[mm] = acc;
+        }
+        return dense_eval(I, hh, C, th);
+    }
+
+    // The affect of a surface crossing (radiative-transfer-problem.jl:116-119 behind DiffEqBase's change_t_via_interpolation!):
+    // called from step() on an accepted step whose condition changed sign up to sample ev_top.  Every component, I included, moves
+    // to the root on the dense output (resolve_event); `within` flips; the condition at the new start takes the sign of the side
+    // the ray is now on BY CONSTRUCTION -- its value there is zero to rounding, and a sign read off it would send the next step
+    // straight back through the surface; the FSAL stage is evaluated again there (the medium term has just switched).  Returns
+    // true when the ray has ended: the chart at the crossing, λ1, or one crossing too many (GR_FLAG_MAXITERS).
+    GR_DEV bool rt_cross(const Metric& m, const Params& p, hreal dtnew)
+    {
+        resolve_event(p);      // x, v, I, t at the root; the discrete callbacks there (a status other than NoStatus: one of them ended the ray)
+        if (status != GR_STATUS_NO_STATUS) return true;
+        if (ncross >= kMaxCrossings) { flags |= GR_FLAG_MAXITERS; return true; }
+        ncross += 1;
+        within = within ? 0 : 1;
+        real s, c;
+        accel(m, x[1], x[2], v, A[0], s, c);
+        sth = s; cth = c;
+        dI[0] = within ? rt_rhs(m, p, x[1], x[2], s, c, v[0], v[1], v[3], I) : (real)0.0;
+        const real cn = trace_cond4(p, x[1], s, c, x[3]);
+        cprev = GR_FMAX(GR_FABS(cn), (real)1e-300);      // > 0: the new side (a NaN condition gives 1e-300 as well)
+        dt = GR_FMIN((hreal)p.dtmax, dtnew);
+        return !(t < (real)p.cfg.lambda1);
+    }
+#endif
 
     // ---- CompositeGeometry (src/geometry/composite.jl; geometry_collision_callback(::CompositeGeometry), bootstrap.jl:76-110):
     // a VectorContinuousCallback whose k-th condition is component k's distance_to_disc and whose every affect terminates with
@@ -3615,7 +3739,13 @@ struct Ray {
             const Cold& cd = cold_of(p);
             hdat = (cd.src_mode == 2 && cd.height) ? (real)cd.height[jl] : (real)p.cfg.disc_params[0];
         }
-        cprev = kContinuous ? disc_cond4(p, x[1], s, c, x[3]) : 1.0;
+#ifdef GR_RADTRANS
+        // u_init = vcat(pos, vel, I₀); within_geometry = !is_finite_disc: false for both thick discs (radiative-transfer-problem.jl:45,155)
+        I = (real)cold_of(p).transfer->I0;
+        within = 0; ncross = 0;
+        dI[0] = 0.0;
+#endif
+        cprev = kContinuous ? trace_cond4(p, x[1], s, c, x[3]) : 1.0;
         ev_mask = 0;
 #if GR_HAS_MESH
         if constexpr (DISC == GR_DISC_MESH) {
@@ -3645,7 +3775,16 @@ struct Ray {
             d1s = GR_FMA(a1, a1, d1s);
             d1s = GR_FMA(b1, b1, d1s);
         }
+#ifdef GR_RADTRANS
+        // the ninth component: its scale like the others'; dI/dλ = 0 at the start (outside the geometry).  The mean is over 9.
+        {
+            const real a0 = I * rcp_full(abstol + GR_FABS(I) * reltol);
+            d0s = GR_FMA(a0, a0, d0s);
+        }
+        const real d0 = sqrt_fast(d0s * (real)(1.0 / 9.0)), d1 = sqrt_fast(d1s * (real)(1.0 / 9.0));
+#else
         const real d0 = sqrt_fast(d0s * 0.125), d1 = sqrt_fast(d1s * 0.125);
+#endif
         real dt0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * (d0 * rcp_full(d1));
         dt0 = GR_FMIN(dt0, dtmax);
         if (dt0 < 10.0 * GR_EPS) {
@@ -3663,7 +3802,11 @@ struct Ray {
                 d2s = GR_FMA(ex, ex, d2s);
                 d2s = GR_FMA(ev, ev, d2s);
             }
+#ifdef GR_RADTRANS
+            const real d2 = sqrt_fast(d2s * (real)(1.0 / 9.0)) * rcp_full(dt0);
+#else
             const real d2 = sqrt_fast(d2s * 0.125) * rcp_full(dt0);
+#endif
             const real dm = GR_FMAX(d1, d2);
             // 10^(-(2 + log10 dm)/5) = 10^-0.4 dm^-0.2 ; single-precision hardware log2/exp2 is ample
             // for a starting step size
@@ -3733,6 +3876,18 @@ struct Ray {
             vs[i] = GR_FMA(ha, acc, v[i]);                                                     \
         }
 #endif
+#ifdef GR_RADTRANS
+        // the ninth component's stage derivative, at the stage's position and momentum with I_s = I + h Σ_q a_Sq dI_q
+#define GR_RT_STAGE(S)                                                                                \
+        dI[S] = 0.0;                                                                                  \
+        if (within) {                                                                                 \
+            real is = dI[0];                                                                          \
+            _Pragma("unroll") for (int q = 1; q < S; ++q) is = GR_FMA(TsD::X.AR[S][q], dI[q], is);    \
+            dI[S] = rt_rhs(m, p, rs, ts, s, c, vs[0], vs[1], vs[3], GR_FMA(ha, is, I));               \
+        }
+#else
+#define GR_RT_STAGE(S)
+#endif
 #define GR_STAGE(S)                                                                                   \
     {                                                                                                 \
         real vs[4];                                                                                 \
@@ -3759,6 +3914,7 @@ struct Ray {
         else                                                                                          \
         geodesic_rhs_sc(m, rs, s, c, vs[0], vs[1], vs[2], vs[3], A[S][0], A[S][1], A[S][2], A[S][3]); \
         GR_PIN4(A[S]);                                                                                \
+        GR_RT_STAGE(S)                                                                                \
     }
         GR_STAGE(1)
         GR_STAGE(2)
@@ -3766,6 +3922,7 @@ struct Ray {
         GR_STAGE(4)
         GR_STAGE(5)
 #undef GR_STAGE
+#undef GR_RT_STAGE
 #undef GR_STAGE_VSUM
         // stage 7 argument = the new state.  Its right-hand side reads r, θ and the velocities; t and ϕ of the new state are
         // formed behind it
@@ -3816,6 +3973,18 @@ struct Ray {
         GR_NEW_POSITION(0)
         GR_NEW_POSITION(3)
 #undef GR_NEW_POSITION
+#ifdef GR_RADTRANS
+        // I at the new state (b_q = a_6q) and the seventh stage there
+        real In = I;
+        dI[6] = 0.0;
+        if (within) {
+            real is = dI[0];
+#pragma unroll
+            for (int q = 1; q < 6; ++q) is = GR_FMA(TsD::X.AR[6][q], dI[q], is);
+            In = GR_FMA(ha6, is, I);
+            dI[6] = rt_rhs(m, p, xn[1], xn[2], sn, cn, vn[0], vn[1], vn[3], In);
+        }
+#endif
 
         // error estimate, squared RMS norm over all eight components: ũ_v = h Σ b̃_q A_q, ũ_x = h (Σb̃ · v + h Σ b̄_i A_i);
         // the common factor h² and the 1/8 of the mean are applied once to the sum.
@@ -3920,6 +4089,22 @@ struct Ray {
 #endif
         }
 #endif
+#if defined(GR_RADTRANS)
+        // the ninth component's residual ũ_I = h Σ b̃_q dI_q over abstol + reltol max(|I₀|, |I₁|), beside the velocities' (the same
+        // common factors); zero outside the geometry.  The reference integrates SVector{9}: the mean is over 9.
+        if (within) {
+            real ei = dI[0];
+#pragma unroll
+            for (int q = 1; q < 7; ++q) ei = GR_FMA(TsD::X.BTR[q], dI[q], ei);
+#if GR_NORM_F32_ON
+            const float aif = (float)ei * GR_RCPF(__builtin_fmaf((float)absmax(I, In), (float)reltol, (float)abstol));
+            e2vf = __builtin_fmaf(aif, aif, e2vf);
+#else
+            const real ai = ei * rcp_raw(GR_FMA(absmax(I, In), reltol, abstol));
+            e2v = GR_FMA(ai, ai, e2v);
+#endif
+        }
+#endif
 #if GR_NORM_F32_ON
         real e2 = (real)__builtin_fmaf((float)(Ts::BT[0] * Ts::BT[0]), e2vf, e2xf);
 #else
@@ -3928,7 +4113,11 @@ struct Ray {
 #ifdef GR_REAL_IS_TAN2
         if (p.tangent_norm) e2 = real(e2n * (1.0 / 3.0));
 #endif
+#ifdef GR_RADTRANS
+        e2 *= (real)(1.0 / 9.0) * h2;   // EEst² over nine components
+#else
         e2 *= 0.125 * h2;   // EEst² ; accept iff EEst <= 1
+#endif
 #ifdef GR_HOST_HARNESS
         dbg_e2 = e2;
 #endif
@@ -3976,7 +4165,7 @@ struct Ray {
                 for (int k = 0; k < GR_COMP_MAX; ++k)
                     if (k < K) comp_prev(k) = cnx[k];
             } else if (kContinuous) {
-                const real cnext = disc_cond4(p, xn[1], sn, cn, xn[3]);
+                const real cnext = trace_cond4(p, xn[1], sn, cn, xn[3]);
                 // prev = sign(c(u_prev)), event at the step's end iff prev != 0 and prev * sign(c(u_new)) <= 0 (a NaN
                 // condition has sign 0 and counts as a crossing): four comparisons, no integer sign arithmetic
                 const bool pos = cprev > 0.0, neg = cprev < 0.0;
@@ -4014,6 +4203,13 @@ struct Ray {
                         }
                     }
                 }
+#ifdef GR_RADTRANS
+                if (top) {
+                    // a surface crossing does not end the ray: to the root, flip, go on (rt_cross)
+                    ev_top = top;
+                    return rt_cross(m, p, dtnew);
+                }
+#endif
                 if (top) {
                     // leave (x, v, A, h) in place; finalize() root-finds on the dense output
                     flags |= RAY_EVENT;
@@ -4046,6 +4242,9 @@ struct Ray {
             if constexpr (kEscapeCull) same_side = cn > 0.0 ? cth > 0.0 : cth < 0.0;
 #pragma unroll
             for (int i = 0; i < 4; ++i) { x[i] = xn[i]; v[i] = vn[i]; A[0][i] = A[6][i]; }
+#ifdef GR_RADTRANS
+            I = In; dI[0] = dI[6];
+#endif
             sth = sn; cth = cn;
             t = tnew;
             dt = GR_FMIN(dtmax, dtnew);
@@ -4173,6 +4372,10 @@ struct Ray {
                 bool state_nan = false;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) state_nan |= !(xn[i] == xn[i]) || !(vn[i] == vn[i]) || !(A[6][i] == A[6][i]);
+#ifdef GR_RADTRANS
+                state_nan |= !(In == In) || !(dI[6] == dI[6]);      // (no real fluid velocity there: I carries the NaN out)
+                if (state_nan) I = In;
+#endif
                 if (state_nan) { flags |= GR_FLAG_NAN; return true; }
 #elif defined(GR_REAL_IS_FLOAT)
                 // Single precision: the NaN norm is, as a rule, a trial step that OVERFLOWED.  At tolerance 1e-3 .. 1e-4 the
@@ -4303,7 +4506,11 @@ struct Ray {
         GR_DBG_BIT(1 << 8);
         real Ct[4], Cr[4];
         dense_coeffs(2, hh, Ct);
+#ifdef GR_RADTRANS
+        bool any = (ps < 0) || within;      // inside the geometry the samples to find are the ones OUTSIDE it: no pre-filter
+#else
         bool any = (ps < 0);
+#endif
         if (thin) {
 #pragma unroll
             for (int jj = 0; jj < 6; ++jj) {
@@ -4342,8 +4549,8 @@ struct Ray {
             const real th = (real)jj / 7.0;
             real s, c;
             sincos_fast(dense_eval(x[2], hh, Ct, th), s, c);
-            const real cj = disc_cond4(p, dense_eval(x[1], hh, Cr, th), s, c,
-                                       DISC == GR_DISC_PRECESSING_THIN ? dense_eval(x[3], hh, Cp, th) : (real)0.0);
+            const real cj = trace_cond4(p, dense_eval(x[1], hh, Cr, th), s, c,
+                                        DISC == GR_DISC_PRECESSING_THIN ? dense_eval(x[3], hh, Cp, th) : (real)0.0);
             if ((real)ps * cj < 0.0) return jj;
         }
         return 0;
@@ -4384,7 +4591,7 @@ struct Ray {
         {
             real s, c;
             sincos_fast(dense_eval(x[2], h, Ct, hi), s, c);
-            fhi = disc_cond4(p, dense_eval(x[1], h, Cr, hi), s, c, DISC == GR_DISC_PRECESSING_THIN ? dense_eval(x[3], h, Cp, hi) : (real)0.0);
+            fhi = trace_cond4(p, dense_eval(x[1], h, Cr, hi), s, c, DISC == GR_DISC_PRECESSING_THIN ? dense_eval(x[3], h, Cp, hi) : (real)0.0);
         }
         if (fhi != 0.0) {
             // Illinois regula falsi: brackets [lo, hi] with sign(f(lo)) == ps throughout, superlinear on
@@ -4398,15 +4605,19 @@ struct Ray {
                 real mid = lo - flo * w / (fhi - flo);
                 // on the plateau c = 1 outside the disc's radial range the condition is a step
                 // function: bisection is the optimal bracketing method there
+#ifdef GR_RADTRANS
+                const bool plateau = (GR_FABS(flo) == 1.0) || (GR_FABS(fhi) == 1.0);      // (-1 seen from inside)
+#else
                 const bool plateau = (flo == 1.0) || (fhi == 1.0);
+#endif
                 if (plateau || !(mid > lo && mid < hi)) {
                     mid = lo + 0.5 * w;
                     if (!(mid > lo && mid < hi)) break;
                 }
                 real s, c;
                 sincos_fast(dense_eval(x[2], h, Ct, mid), s, c);
-                const real fm = disc_cond4(p, dense_eval(x[1], h, Cr, mid), s, c,
-                                           DISC == GR_DISC_PRECESSING_THIN ? dense_eval(x[3], h, Cp, mid) : (real)0.0);
+                const real fm = trace_cond4(p, dense_eval(x[1], h, Cr, mid), s, c,
+                                            DISC == GR_DISC_PRECESSING_THIN ? dense_eval(x[3], h, Cp, mid) : (real)0.0);
                 if (sgn(fm) == ps) {
                     lo = mid; flo = fm;
                     if (side < 0) fhi *= 0.5;
@@ -4466,6 +4677,9 @@ struct Ray {
             }
         }
 #endif
+#ifdef GR_RADTRANS
+        I = rt_dense_I(h, theta);      // the ninth component from its interpolant (dI and I are still the step's)
+#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i) { x[i] = xe[i]; v[i] = ve[i]; }
         t = t + theta * h;
@@ -4516,6 +4730,9 @@ struct Ray {
                 o->x[q] = (double)x[q];
                 o->v[q] = (double)v[q];
             }
+#ifdef GR_RADTRANS
+            if (cd.intensity) cd.intensity[oj] = (double)I;      // gp.aux[1], beside the record
+#endif
         } else if (cd.out_mode >= 2) {
             // lineprofile(bins, ε, m, u, d, BinningMethod()), line-profiles.jl:186-197
             real s, c;
@@ -4649,6 +4866,9 @@ struct Ray {
                 if (cd.pf.pf_id == GR_PF_AFFINE_TIME) val = t;
                 else if (cd.pf.pf_id == GR_PF_STATUS) val = (real)status;
                 else if (cd.pf.pf_id == GR_PF_WINDING) val = (real)((uint32_t)flags >> 16);
+#ifdef GR_RADTRANS
+                else if (cd.pf.pf_id == GR_PF_INTENSITY) val = I;      // gp.aux[1]
+#endif
                 else if (cd.pf.pf_id == GR_PF_RADIUS) {
                     real s, c;
                     sincos_fast(x[2], s, c);

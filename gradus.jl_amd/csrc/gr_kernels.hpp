@@ -607,6 +607,18 @@ hipError_t launch_tmpl(const LaunchKnobs& k, Params& p, hipStream_t stream)
 }
 
 // DISC is the geometry id itself (GR_DISC_*): compile-time in the kernels
+#ifdef GR_RADTRANS
+// TraceRadiativeTransfer: the two optically thick discs only (the host unit refuses every other id before it gets here)
+template <class Metric>
+hipError_t launch_metric(const LaunchKnobs& k, Params& p, hipStream_t stream)
+{
+    switch (p.cfg.disc_id) {
+    case GR_DISC_SHAKURA_SUNYAEV: return launch_tmpl<Metric, GR_DISC_SHAKURA_SUNYAEV>(k, p, stream);
+    case GR_DISC_TABULATED: return launch_tmpl<Metric, GR_DISC_TABULATED>(k, p, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+#else
 template <class Metric>
 hipError_t launch_metric(const LaunchKnobs& k, Params& p, hipStream_t stream)
 {
@@ -624,6 +636,7 @@ hipError_t launch_metric(const LaunchKnobs& k, Params& p, hipStream_t stream)
     default: return launch_tmpl<Metric, GR_DISC_NONE>(k, p, stream);
     }
 }
+#endif
 
 template <class Metric>
 hipError_t launch_path_metric(const Params& p, double* d_path, int64_t cap, unsigned long long* d_n, hipStream_t stream)

@@ -26,6 +26,7 @@
 #include <vector>
 
 #define GR_NS gr
+#define GR_RADTRANS_LAYOUT 1      // Cold with the two pointers of the TraceRadiativeTransfer kernels behind everything else (gr_device.hpp)
 #include "gr_device.hpp"
 #include "gr_stats_fold.hpp"
 #include "gr_tile_order.hpp"
@@ -68,6 +69,14 @@ hipError_t gr64_launch_apply_m11(const void*, const gr_point*, double, double*, 
 hipError_t gr64_launch_classify_m11(const void*, uint8_t*, int64_t, hipStream_t);
 hipError_t gr64_launch_areafactor_m11(const void*, const double*, double*, hipStream_t);
 hipError_t grv1_launch_offset_m11(const void*, const void*, int, hipStream_t);
+// TraceRadiativeTransfer (kernels_tu.hip -DGR_TU_RT -> kernelsrt_m<id>.o): the catalogue metrics that have an ISCO
+hipError_t grrt_launch_trace_m0(int, int, int, int, unsigned long long*, const void*, hipStream_t);
+hipError_t grrt_launch_trace_m1(int, int, int, int, unsigned long long*, const void*, hipStream_t);
+hipError_t grrt_launch_trace_m3(int, int, int, int, unsigned long long*, const void*, hipStream_t);
+hipError_t grrt_launch_trace_m4(int, int, int, int, unsigned long long*, const void*, hipStream_t);
+hipError_t grrt_launch_trace_m5(int, int, int, int, unsigned long long*, const void*, hipStream_t);
+hipError_t grrt_launch_trace_m6(int, int, int, int, unsigned long long*, const void*, hipStream_t);
+hipError_t grrt_launch_trace_m9(int, int, int, int, unsigned long long*, const void*, hipStream_t);
 static_assert(GR_METRIC_NOZ == 10 && GR_METRIC_TABULATED == 11, "one kernel object per metric id 0..11: extend the tables below with the catalogue");
 
 namespace {
@@ -97,6 +106,9 @@ const classify_fn kClassify64[12] = GR_ROW(gr64_launch_classify_m, gr64_launch_c
 const areafactor_fn kAreaFactor64[12] = GR_ROW(gr64_launch_areafactor_m, gr64_launch_areafactor_m11);      // γ(r) A(r) of the disc (kernelsarea_m<id>.o)
 const offset_fn kOffsetSolve1[12] = GR_ROW(grv1_launch_offset_m, grv1_launch_offset_m11);      // k_offset_solve / k_offset_search (kernelssolve1_m<id>.o)
 #undef GR_ROW
+// the radiative-transfer kernels, null where the metric has no ISCO (Morris-Thorne, flat space, Kerr with dark matter, no-Z) and for a table
+const trace_fn kTraceRT[12] = { grrt_launch_trace_m0, grrt_launch_trace_m1, nullptr, grrt_launch_trace_m3, grrt_launch_trace_m4, grrt_launch_trace_m5,
+                                grrt_launch_trace_m6, nullptr, nullptr, grrt_launch_trace_m9, nullptr, nullptr };
 // Metric::kEscapeRadiusM per metric id, in units of params[0] (escape_cull_radius)
 #define GR_ESC(ID) MetricOf<ID>::type::kEscapeRadiusM
 const double kEscapeRadiusM[12] = { GR_ESC(0), GR_ESC(1), GR_ESC(2), GR_ESC(3), GR_ESC(4), GR_ESC(5), GR_ESC(6), GR_ESC(7),
@@ -241,6 +253,8 @@ struct gr_ctx {
     double* d_chart_table = nullptr;       // device copy of a PoloidalShapeChart table
     size_t chart_table_bytes = 0;
     Cold* d_cold = nullptr;                // ring of per-launch cold blocks
+    gr_transfer* d_transfer = nullptr;     // ring of per-launch medium blocks of the gr_transfer_* calls (made at the first of them)
+    int transfer_next = 0;
     int cold_next = 0;
     double* d_plunge = nullptr;            // 4 x n_plunge
     int64_t plunge_cap = 0;
@@ -1012,7 +1026,8 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
     // kernel's refill would mix again -- one ray per lane, four waves to a workgroup (10⁶ lamp-post samples: 5.9 ms against 7.6
     // persistent, 6.6 with one-wave workgroups, 8.4 in sample order; profiles/r6_corona_cost_ab.log)
     const bool dealt = sky && sky_dealt(ctx, p.n) && !tangent;
-    const int kern_sel = tangent ? 0 : (dealt && ctx->kernel == 2) ? 0 : resolve_kernel(ctx, p.n, cold, p.cfg.metric_id);
+    const bool transfer = cold.transfer != nullptr;      // the gr_transfer_* calls: the one-ray-per-lane kernel of kernelsrt_m<id>.o
+    const int kern_sel = (tangent || transfer) ? 0 : (dealt && ctx->kernel == 2) ? 0 : resolve_kernel(ctx, p.n, cold, p.cfg.metric_id);
     const int block_sel = tangent ? (ctx->block ? (int)ctx->block : 64) : (dealt && ctx->kernel == 2 && !ctx->block) ? 256 : resolve_block(ctx, kern_sel);
     // LDS staging: the plunging table (<= 2048 rows = 64 KB) and the line-profile histogram (<= 4096 bins).
     // A table is staged per workgroup: with one-wave workgroups a CU holds 8 copies, so it is staged
@@ -1093,8 +1108,9 @@ int32_t launch_trace(gr_ctx* ctx, Params& p, const Cold& cold_in, hipStream_t st
     // on 4 SIMDs per CU -- cannot keep the SIMDs busy either way and is as long as its longest ray: it takes the pairs.
     const bool pairs = tangent && (ctx->tangent_pairs == 1 || (ctx->tangent_pairs == 2 && 2 * p.n <= (int64_t)ctx->n_cu * 4 * 64));
     const bool skycell = cold.out_mode == 6;
-    const trace_fn fn = skycell ? (pairs ? mk.sky1 : mk.sky) : tangent ? (pairs ? mk.tan1 : mk.tan) : ctx->precision == 32 ? mk.trace32 : mk.trace64;
-    GR_NEED_KERNEL(fn, skycell ? "sky-cell" : tangent ? "tangent" : ctx->precision == 32 ? "fp32" : "fp64 trace");
+    const trace_fn fn = transfer ? ((p.cfg.metric_id >= 0 && p.cfg.metric_id < 12) ? kTraceRT[p.cfg.metric_id] : nullptr)
+                        : skycell ? (pairs ? mk.sky1 : mk.sky) : tangent ? (pairs ? mk.tan1 : mk.tan) : ctx->precision == 32 ? mk.trace32 : mk.trace64;
+    GR_NEED_KERNEL(fn, transfer ? "radiative-transfer" : skycell ? "sky-cell" : tangent ? "tangent" : ctx->precision == 32 ? "fp32" : "fp64 trace");
     p.tangent_norm = (tangent && ctx->tangent_norm) ? 1 : 0;
 #ifdef GR_WAVE_TIMELINE
     p.queue = g_debug_timeline;      // debug builds: 4 x u64 per wave of a one-ray-per-lane launch (gr_kernels.hpp)
@@ -1412,6 +1428,7 @@ int32_t gr_ctx_destroy(gr_ctx* c)
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_stat_part) (void)hipFree(c->d_stat_part);
     if (c->d_cold) (void)hipFree(c->d_cold);
+    if (c->d_transfer) (void)hipFree(c->d_transfer);
     if (c->d_disc_table) (void)hipFree(c->d_disc_table);
     if (c->d_mesh) (void)hipFree(c->d_mesh);
     if (c->d_chart_table) (void)hipFree(c->d_chart_table);
@@ -4487,6 +4504,164 @@ int32_t gr_trace_endpoints(gr_ctx* ctx, const gr_config* cfg, const double* x, i
                            int64_t n, gr_point* points, gr_stats* stats)
 {
     return one_context(gr_trace_endpoints_multi(&ctx, 1, cfg, x, x_stride, v, n, points, stats), stats);
+}
+
+// ---- covariant radiative transfer (include/gradus_mi355x.h, gr_transfer): TraceRadiativeTransfer through a thick disc ----
+extern "C++" {
+namespace {
+// what the radiative-transfer kernels are not built for, refused before anything touches the device
+int32_t transfer_check(const gr_ctx* ctx, const gr_config* cfg, const gr_transfer* transfer)
+{
+    if (!cfg) return fail(GR_ERR_INVALID_ARGUMENT, "config is null");
+    if (!transfer) return fail(GR_ERR_INVALID_ARGUMENT, "transfer is null");
+    if (cfg->metric_id == GR_METRIC_TABULATED || cfg->metric_id >= GR_METRIC_COMPILED)
+        return fail(GR_ERR_UNSUPPORTED, "radiative transfer is traced through the catalogue's metrics only (not GR_METRIC_TABULATED, not a compiled metric)");
+    if (cfg->metric_id < 0 || cfg->metric_id >= 12 || !kTraceRT[cfg->metric_id])
+        return fail(GR_ERR_UNSUPPORTED, "radiative transfer needs a metric with an ISCO (fluid_velocity): metric_id " + std::to_string(cfg->metric_id) + " has none");
+    if (cfg->disc_id != GR_DISC_SHAKURA_SUNYAEV && cfg->disc_id != GR_DISC_TABULATED)
+        return fail(GR_ERR_UNSUPPORTED, "radiative transfer is traced through GR_DISC_SHAKURA_SUNYAEV and GR_DISC_TABULATED only (disc_id "
+                                        + std::to_string(cfg->disc_id) + ")");
+    if (cfg->disc_id == GR_DISC_TABULATED && cfg->disc_params[3] != 0.0)
+        return fail(GR_ERR_UNSUPPORTED, "radiative transfer: a warped thin disc's table (disc_params[3] != 0) is an optically thin sheet, not a medium");
+    if (ctx->precision == 32) return fail(GR_ERR_UNSUPPORTED, "radiative transfer has fp64 kernels only (\"precision\" 32)");
+    if (cfg->q != 0.0) return fail(GR_ERR_UNSUPPORTED, "radiative transfer along charged test particles (q != 0) is not built");
+    if (cfg->count_windings) return fail(GR_ERR_UNSUPPORTED, "radiative transfer does not count windings (count_windings)");
+    if (!(transfer->r_isco > 0.0)) return fail(GR_ERR_INVALID_ARGUMENT, "transfer->r_isco must be positive");
+    return GR_OK;
+}
+
+// the caller's medium block into the next slot of the context's ring, ordered on `stream` before the kernel that reads it
+int32_t stage_transfer(gr_ctx* ctx, const gr_transfer* transfer, hipStream_t stream, const gr_transfer** d_out)
+{
+    if (!ctx->d_transfer) GR_HIP(hipMalloc((void**)&ctx->d_transfer, sizeof(gr_transfer) * (size_t)ctx->queue_slots));
+    gr_transfer* slot = ctx->d_transfer + ctx->transfer_next;
+    ctx->transfer_next = (ctx->transfer_next + 1) % ctx->queue_slots;
+    GR_HIP(hipMemcpyAsync(slot, transfer, sizeof(gr_transfer), hipMemcpyHostToDevice, stream));
+    *d_out = slot;
+    return GR_OK;
+}
+
+// rays given by (x, v) on the device: records to d_points, intensities to d_intensity
+int32_t transfer_endpoints_device(gr_ctx* ctx, const gr_config* cfg, const gr_transfer* transfer, const double* d_x, int64_t x_stride,
+                                  const double* d_v, int64_t n, gr_point* d_points, double* d_intensity, gr_stats* d_stats, hipStream_t stream)
+{
+    int32_t rc;
+    Params p;
+    Cold cd;
+    std::memset(&p, 0, sizeof p);
+    std::memset(&cd, 0, sizeof cd);
+    p.cfg = *cfg;
+    p.n = n;
+    p.stats = (unsigned long long*)d_stats;
+    cd.src_mode = 1;
+    cd.out_mode = 1;
+    cd.x = d_x;
+    cd.x_stride = x_stride;
+    cd.v = d_v;
+    cd.points = d_points;
+    cd.intensity = d_intensity;
+    cd.range = gr_range{ 0, n, n > 0 ? n : 1, 1 };
+    cd.swizzle = 0;
+    if (n == 0) return GR_OK;
+    if ((rc = stage_transfer(ctx, transfer, stream, &cd.transfer)) != GR_OK) return rc;
+    return launch_trace(ctx, p, cd, stream);
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t gr_transfer_render_device(gr_ctx* ctx, const gr_config* cfg, const gr_transfer* transfer, const gr_plane* plane,
+                                  const gr_pointfunction* pf, const gr_range* range, double* d_image, gr_stats* d_stats, void* hip_stream)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc;
+    if ((rc = transfer_check(ctx, cfg, transfer)) != GR_OK) return rc;      // (first: what it refuses, it refuses as unsupported)
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if ((rc = validate_plane(plane, range)) != GR_OK) return rc;
+    if (!pf) return fail(GR_ERR_INVALID_ARGUMENT, "point function is null");
+    if (pf->pf_id != GR_PF_INTENSITY) return fail(GR_ERR_UNSUPPORTED, "a radiative-transfer render gives GR_PF_INTENSITY (pf_id " + std::to_string(pf->pf_id) + ")");
+    if (pf->filter_id < GR_FILTER_NONE || pf->filter_id > GR_FILTER_INTERSECTED) return fail(GR_ERR_UNSUPPORTED, "unknown filter_id " + std::to_string(pf->filter_id));
+    if (!d_image && range->count > 0) return fail(GR_ERR_INVALID_ARGUMENT, "image is null");
+    GR_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    Params p;
+    Cold cd;
+    plane_params(ctx, p, cd, cfg, plane, range);
+    cd.pf.pf_id = pf->pf_id;
+    cd.pf.filter_id = pf->filter_id;
+    cd.pf.fill = pf->fill;
+    cd.pf.r_isco = transfer->r_isco;
+    cd.out_mode = 0;
+    cd.image = d_image;
+    p.stats = (unsigned long long*)d_stats;
+    if (range->count == 0) return GR_OK;
+    if ((rc = stage_transfer(ctx, transfer, stream, &cd.transfer)) != GR_OK) return rc;
+    return launch_trace(ctx, p, cd, stream);
+}
+
+int32_t gr_transfer_render(gr_ctx* ctx, const gr_config* cfg, const gr_transfer* transfer, const gr_plane* plane, const gr_pointfunction* pf,
+                           const gr_range* range, double* image, gr_stats* stats)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!range) return fail(GR_ERR_INVALID_ARGUMENT, "range is null");
+    if (!image && range->count > 0) return fail(GR_ERR_INVALID_ARGUMENT, "image is null");
+    int32_t rc;
+    // refusals come before the call's first device work (begin_host_call)
+    if ((rc = transfer_check(ctx, cfg, transfer)) != GR_OK) return rc;      // (first: what it refuses, it refuses as unsupported)
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if ((rc = validate_plane(plane, range)) != GR_OK) return rc;
+    if (!pf || pf->pf_id != GR_PF_INTENSITY) return fail(GR_ERR_UNSUPPORTED, "a radiative-transfer render gives GR_PF_INTENSITY");
+    const size_t bytes = sizeof(double) * (size_t)(range->count > 0 ? range->count : 0);
+    auto enq = [&](int) -> int32_t {
+        int32_t r;
+        GR_HIP(hipSetDevice(ctx->device));
+        if ((r = ensure(&ctx->d_scratch, &ctx->scratch_bytes, bytes ? bytes : 8)) != GR_OK) return r;
+        if ((r = begin_host_call(ctx, stats)) != GR_OK) return r;
+        return gr_transfer_render_device(ctx, cfg, transfer, plane, pf, range, (double*)ctx->d_scratch, stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream);
+    };
+    auto copy = [&](int) -> int32_t {
+        if (bytes == 0) return GR_OK;
+        GR_HIP(hipSetDevice(ctx->device));
+        GR_HIP(hipMemcpyAsync(image, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GR_OK;
+    };
+    return one_context(multi_drive(&ctx, 1, stats, enq, copy), stats);
+}
+
+int32_t gr_transfer_endpoints(gr_ctx* ctx, const gr_config* cfg, const gr_transfer* transfer, const double* x, int64_t x_stride,
+                              const double* v, int64_t n, gr_point* points, double* intensity, gr_stats* stats)
+{
+    if (!ctx) return fail(GR_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc;
+    if ((rc = transfer_check(ctx, cfg, transfer)) != GR_OK) return rc;      // (first: what it refuses, it refuses as unsupported)
+    if ((rc = validate_cfg(cfg)) != GR_OK) return rc;
+    if (n < 0) return fail(GR_ERR_INVALID_ARGUMENT, "n must be non-negative");
+    if (x_stride != 0 && x_stride != 4) return fail(GR_ERR_INVALID_ARGUMENT, "x_stride must be 0 or 4");
+    if (n > 0 && (!x || !v || !points || !intensity)) return fail(GR_ERR_INVALID_ARGUMENT, "x/v/points/intensity is null");
+    const size_t nx = (size_t)(x_stride == 0 ? 4 : 4 * n), nv = (size_t)(4 * n);
+    const size_t rec_bytes = sizeof(gr_point) * (size_t)n, int_bytes = sizeof(double) * (size_t)n;
+    auto enq = [&](int) -> int32_t {
+        int32_t r;
+        GR_HIP(hipSetDevice(ctx->device));
+        // the records, then the intensities (152 n is a multiple of 8: the doubles behind them are aligned)
+        if ((r = ensure(&ctx->d_scratch, &ctx->scratch_bytes, rec_bytes + int_bytes + 8)) != GR_OK) return r;
+        if ((r = ensure(&ctx->d_in, &ctx->in_bytes, sizeof(double) * (nx + nv) + 8)) != GR_OK) return r;
+        if ((r = begin_host_call(ctx, stats)) != GR_OK) return r;
+        if (n == 0) return GR_OK;
+        double* d_x = (double*)ctx->d_in;
+        double* d_v = d_x + nx;
+        GR_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * nx, hipMemcpyHostToDevice, ctx->stream));
+        GR_HIP(hipMemcpyAsync(d_v, v, sizeof(double) * nv, hipMemcpyHostToDevice, ctx->stream));
+        return transfer_endpoints_device(ctx, cfg, transfer, d_x, x_stride, d_v, n, (gr_point*)ctx->d_scratch,
+                                         (double*)((char*)ctx->d_scratch + rec_bytes), stats ? (gr_stats*)ctx->d_stats : nullptr, ctx->stream);
+    };
+    auto copy = [&](int) -> int32_t {
+        if (n == 0) return GR_OK;
+        GR_HIP(hipSetDevice(ctx->device));
+        GR_HIP(hipMemcpyAsync(points, ctx->d_scratch, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        GR_HIP(hipMemcpyAsync(intensity, (char*)ctx->d_scratch + rec_bytes, int_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GR_OK;
+    };
+    return one_context(multi_drive(&ctx, 1, stats, enq, copy), stats);
 }
 
 extern "C++" {

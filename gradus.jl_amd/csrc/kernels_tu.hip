@@ -7,6 +7,7 @@
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN[1] -DGR_TU_SKY -c kernels_tu.hip -o kernelssky[1]_m<id>.o    (the two tangent shapes for sky cells)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_AREA -c kernels_tu.hip -o kernelsarea_m<id>.o                   (fp64, k_disc_area_factor alone)
 //     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_TAN1 -DGR_TU_SOLVE -c kernels_tu.hip -o kernelssolve1_m<id>.o    (pairs; k_offset_solve, k_offset_search alone)
+//     hipcc ... -DGR_TU_METRIC=<id> -DGR_TU_RT -c kernels_tu.hip -o kernelsrt_m<id>.o                       (fp64, TraceRadiativeTransfer; metrics with an ISCO)
 //     hipcc ... -DGR_TU_METRIC=12 -DGR_TU_USER -DGR_USER_COMPONENTS_FILE=\"<body>\" [one of the flag sets above but fp32] ...  (a user's metric:
 //               gr_usermetric.hpp; the seven objects are linked into a module of their own, not into the library -- metrics.CompiledMetric)
 //
@@ -18,7 +19,7 @@
 //
 // Exports (plain signatures: the host unit, gradus_mi355x.hip, passes its gr::Params by address -- gr32::Params has the
 // same layout, its fields are double / integer / pointers only):
-//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>, gr64_launch_areafactor_m<ID> (-DGR_TU_AREA)      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>      grts_launch_trace_m<ID>      grts1_launch_trace_m<ID>      grv1_launch_offset_m<ID> (-DGR_TU_SOLVE)
+//     gr64_launch_trace_m<ID>, gr64_launch_path_m<ID>, gr64_launch_apply_m<ID>, gr64_launch_classify_m<ID>, gr64_launch_areafactor_m<ID> (-DGR_TU_AREA)      gr32_launch_trace_m<ID>      grt_launch_trace_m<ID>      grt1_launch_trace_m<ID>      grts_launch_trace_m<ID>      grts1_launch_trace_m<ID>      grv1_launch_offset_m<ID> (-DGR_TU_SOLVE)      grrt_launch_trace_m<ID> (-DGR_TU_RT)
 #ifndef GR_TU_METRIC
 #error "compile with -DGR_TU_METRIC=<metric id>"
 #endif
@@ -69,6 +70,17 @@
 #endif
 #define GR_LANE_ONLY 1
 #define GR_LANE_MIN_WAVES 1  // waves per SIMD the tangent kernels are compiled for
+#elif defined(GR_TU_RT)
+// TraceRadiativeTransfer (namespace grrt; gr_device.hpp, GR_RADTRANS): fp64, the one-ray-per-lane kernel only, for the two
+// optically thick discs.  The ray carries a ninth component I with its seven stage derivatives and goes THROUGH the surface.
+// An object of its own (the GR_TU_SKY precedent): everything the flavour adds to the headers sits behind GR_RADTRANS, and the
+// other objects compile to what they did without it (scripts/isa_compare.py; DESIGN_measurements.md).  Two waves per SIMD: the
+// ray's sixteen doubles more do not fit the 168 registers of three (registers, scratch: DESIGN_measurements.md).
+#define GR_RADTRANS 1
+#define GR_NS grrt
+#define GR_TU_PREFIX grrt
+#define GR_LANE_ONLY 1
+#define GR_LANE_MIN_WAVES 2
 #elif defined(GR_TU_F32)
 #define GR_REAL_IS_FLOAT 1
 #define GR_NS gr32
@@ -130,7 +142,7 @@ GR_TU_EXPORT hipError_t GR_TU_NAME(_launch_trace_m)(int kernel, int block, int n
 }
 #endif
 
-#if !defined(GR_TU_F32) && !defined(GR_TU_TAN) && !defined(GR_TU_TAN1) && !defined(GR_TU_AREA)
+#if !defined(GR_TU_F32) && !defined(GR_TU_TAN) && !defined(GR_TU_TAN1) && !defined(GR_TU_AREA) && !defined(GR_TU_RT)
 GR_TU_EXPORT hipError_t GR_TU_NAME(_launch_path_m)(const void* params, double* d_path, int64_t cap, unsigned long long* d_n, hipStream_t stream)
 {
     return GR_NS::launch_path_metric<TuMetric>(*reinterpret_cast<const GR_NS::Params*>(params), d_path, cap, d_n, stream);

@@ -12,7 +12,7 @@ from typing import Callable, Optional
 from .metrics import AbstractMetric, KerrMetric
 from .status import StatusCodes
 
-GR_PF_AFFINE_TIME, GR_PF_REDSHIFT, GR_PF_STATUS, GR_PF_RADIUS, GR_PF_WINDING = 0, 1, 2, 3, 4
+GR_PF_AFFINE_TIME, GR_PF_REDSHIFT, GR_PF_STATUS, GR_PF_RADIUS, GR_PF_WINDING, GR_PF_INTENSITY = 0, 1, 2, 3, 4, 5
 GR_FILTER_NONE, GR_FILTER_EARLY_TERM, GR_FILTER_INTERSECTED = 0, 1, 2
 
 
@@ -104,6 +104,16 @@ class ConstPointFunctions:
     def winding():
         """PointFunction((m, gp, t) -> gp.aux.winding) for a TraceWindings render (photon-ring order)."""
         return PointFunction(lambda m, gp, max_time, **kw: float((int(gp["flags"]) & 0xFFFFFFFF) >> 16), device_pf=GR_PF_WINDING)
+
+    @staticmethod
+    def intensity():
+        """PointFunction((m, gp, t) -> gp.aux[1]) for a TraceRadiativeTransfer render: the intensity the ray ends with.  The
+        end-point record has no place for it: it is formed by the trace (rendergeodesics(..., trace=TraceRadiativeTransfer(...)))
+        and cannot be applied to stored points."""
+        def _host(_m, gp, max_time, **_kw):
+            raise NotImplementedError("the intensity is carried by the trace itself: render with trace=TraceRadiativeTransfer(...)")
+
+        return PointFunction(_host, device_pf=GR_PF_INTENSITY)
 
     @staticmethod
     def shadow():

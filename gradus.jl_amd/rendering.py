@@ -84,6 +84,8 @@ def apply_pointfunction(ensemble: EnsembleMI355X, config_or_cache, pf, points, m
 
 def render_into_image(config: TracingConfiguration, pf=None, stats=False):
     """render_into_image! (rendering.jl:89-101).  Fused on the device when `pf` is a built-in."""
+    if config.transfer is not None:
+        return _render_transfer(config, pf, stats)
     if pf is None:
         pf = ConstPointFunctions.shadow()   # default pf of rendering.jl:93-94
     ens = config.ensemble
@@ -104,6 +106,30 @@ def render_into_image(config: TracingConfiguration, pf=None, stats=False):
         pts = ensemble_solve_tracing_problem(ens, config)
         img = _apply_host(pf, config.metric, pts, config.λ_domain[1])
     # Julia image is (H, W) column-major with linear index i = x*H + y
+    image = img.reshape(rv.image_width, rv.image_height).T
+    return (image, st.asdict()) if stats else image
+
+
+def _render_transfer(config: TracingConfiguration, pf, stats):
+    """rendergeodesics(..., trace = TraceRadiativeTransfer(...)): the image of the intensity (the example's pf,
+    `PointFunction((m, gp, t) -> gp.aux[1])`, is the default and the only value the trace itself can give)."""
+    from .pointfunctions import GR_PF_INTENSITY
+
+    if pf is None:
+        pf = ConstPointFunctions.intensity()
+    if pf.device_pf != GR_PF_INTENSITY:
+        raise NotImplementedError("a TraceRadiativeTransfer render gives the intensity: pf = ConstPointFunctions.intensity() "
+                                  "(optionally behind filter_early_term())")
+    ens = config.ensemble
+    if ens.multi:
+        raise NotImplementedError("TraceRadiativeTransfer runs on one device")
+    rv = config.velocity
+    n = rv.image_width * rv.image_height
+    cfg, pl, tr = config.abi_config(), config.abi_plane(), config.abi_transfer()
+    s, keep = abi_pointfunction(pf)
+    img = np.zeros(n)
+    rg = _lib.gr_range(0, n, max(n, 1), 1)
+    st = ens.call("gr_transfer_render", C.byref(cfg), C.byref(tr), C.byref(pl), C.byref(s), C.byref(rg), img.ctypes.data)
     image = img.reshape(rv.image_width, rv.image_height).T
     return (image, st.asdict()) if stats else image
 

@@ -126,6 +126,48 @@ class TraceWindings:
     plane_inc: float = math.pi / 2
 
 
+@dataclass(frozen=True)
+class PowerLawMedium:
+    """Absorption and emissivity coefficients of the medium inside an optically thick geometry, as power laws of the
+    cylindrical radius ρ = r sin θ and of the frequency in the fluid's frame, ν = ν₀ ds/dλ:
+
+        a_ν = a0 ρ^-pa ν^-sa,    j_ν = j0 ρ^-pj ν^-sj.
+
+    Zero exponents give constant coefficients -- what the reference's doughnut example defines
+    (absorption_coefficient / emissivity_coefficient of a geometry, radiative-transfer-problem.jl:22-27); the default is the
+    reference's default of zero coefficients.  User-written coefficient functions do not run on the device."""
+
+    a0: float = 0.0
+    j0: float = 0.0
+    pa: float = 0.0
+    pj: float = 0.0
+    sa: float = 0.0
+    sj: float = 0.0
+
+
+@dataclass(frozen=True)
+class TraceRadiativeTransfer:
+    """TraceRadiativeTransfer(μ = 0, q = 0, ν = 1, I₀ = 1.0) -- src/tracing/tracing.jl:9-17,
+    src/tracing/radiative-transfer-problem.jl.  The ray carries the intensity I as a ninth state component,
+    dI/dλ = s (-a_ν I + j_ν / ν³) with s = -g(k, u) while it is inside the geometry, and passes THROUGH the geometry's surface
+    instead of ending on it.  `medium`: a PowerLawMedium (None: zero coefficients).  On the device: ShakuraSunyaev, ThickDisc(f)
+    and PolishDoughnut around a metric with an ISCO, μ = 0 rays, q = 0."""
+
+    μ: float = 0.0
+    q: float = 0.0
+    ν: float = 1.0
+    I0: float = 1.0
+    medium: Optional[PowerLawMedium] = None
+
+    def abi_transfer(self, r_isco: float) -> "_lib.gr_transfer":
+        md = self.medium if self.medium is not None else PowerLawMedium()
+        t = _lib.gr_transfer()
+        t.nu0, t.I0 = float(self.ν), float(self.I0)
+        t.a0, t.j0, t.pa, t.pj, t.sa, t.sj = (float(getattr(md, k)) for k in ("a0", "j0", "pa", "pj", "sa", "sj"))
+        t.r_isco, t.reserved = float(r_isco), 0.0
+        return t
+
+
 def winding_number(points):
     """gp.aux.winding of TraceWindings end points (carried in bits 16..31 of the records' flags)."""
     return (np.asarray(points["flags"]).astype(np.uint32) >> 16).astype(np.int64)
@@ -316,6 +358,13 @@ class TracingConfiguration:
     maxiters: int = 1_000_000
     q: float = 0.0
     winding_plane: Optional[float] = None      # TraceWindings.plane_inc (photon-rings.jl:17-24); None = plain TraceGeodesic
+    transfer: Optional[TraceRadiativeTransfer] = None      # the trace carries an intensity through the geometry (gr_transfer_*)
+
+    def abi_transfer(self) -> "_lib.gr_transfer":
+        """gr_transfer of a TraceRadiativeTransfer configuration (the ISCO of the metric: fluid_velocity's switch)"""
+        if not hasattr(self.metric, "isco"):
+            raise NotImplementedError(f"TraceRadiativeTransfer needs a metric with an ISCO; {type(self.metric).__name__} has none")
+        return self.transfer.abi_transfer(self.metric.isco())
 
     def abi_config(self) -> _lib.gr_config:
         c = _lib.gr_config()
@@ -459,12 +508,17 @@ def tracing_configuration(
     trace=None,
 ):
     winding_plane = None
+    transfer = None
     if trace is not None:
         # TraceGeodesic(μ, q) / TraceWindings(μ, plane_inc): the `trace` keyword of tracegeodesics (tracing.jl:66-80)
         if isinstance(trace, TraceWindings):
             μ, winding_plane = trace.μ, trace.plane_inc
         elif isinstance(trace, TraceGeodesic):
             μ, q = trace.μ, trace.q
+        elif isinstance(trace, TraceRadiativeTransfer):
+            μ, q, transfer = trace.μ, trace.q, trace
+            if geometry is None:
+                raise ValueError("Cannot calculate radiative transfer without geometry (geometry is `nothing`).")
         else:
             raise NotImplementedError(f"trace {type(trace).__name__} has no device implementation")
     if solver != "Tsit5":
@@ -486,7 +540,7 @@ def tracing_configuration(
     position = np.asarray(position, dtype=np.float64)
     from .planes import PolarPlane
 
-    if isinstance(velocity, PolarPlane) and os.environ.get("GRADUS_MI355X_SEPARABLE_RAYS", "1") != "0":
+    if isinstance(velocity, PolarPlane) and transfer is None and os.environ.get("GRADUS_MI355X_SEPARABLE_RAYS", "1") != "0":
         trajectories = velocity.Nr * velocity.Nθ
         velocity = PlaneVelocity(velocity)
     elif isinstance(velocity, PlaneVelocity):
@@ -516,7 +570,7 @@ def tracing_configuration(
         geometry = geometry.thick_disc()         # PolishDoughnut: its isobar, sampled like any ThickDisc(f)
     return TracingConfiguration(
         m, position, velocity, geometry, chart, callback, ensemble, trajectories, _as_lambda_domain(λs),
-        abstol, reltol, gtol, μ, maxiters, q, winding_plane,
+        abstol, reltol, gtol, μ, maxiters, q, winding_plane, transfer,
     )
 
 
@@ -524,6 +578,25 @@ def ensemble_solve_tracing_problem(ensemble: EnsembleMI355X, config: TracingConf
     """THE DROP-IN BOUNDARY (src/tracing/tracing.jl:151-196): returns the GeodesicPoint records
     (numpy structured array, 152-byte layout of src/solution-processing.jl:15-32)."""
     cfg = config.abi_config()
+    if config.transfer is not None:
+        # TraceRadiativeTransfer: (points, intensities) -- the record is fixed, gp.aux[1] comes beside it as a float64 array of
+        # shape (n,), ray i's intensity at index i
+        if isinstance(config.velocity, (RenderVelocity, PlaneVelocity)):
+            raise NotImplementedError("TraceRadiativeTransfer end points are traced from (x, v) arrays or an image plane's impact parameters")
+        if ensemble.multi:
+            raise NotImplementedError("TraceRadiativeTransfer runs on one device")
+        tr = config.abi_transfer()
+        v = np.ascontiguousarray(config.velocity, dtype=np.float64)
+        x = np.ascontiguousarray(config.position, dtype=np.float64)
+        n = v.shape[0]
+        stride = 0 if x.ndim == 1 else 4
+        if stride == 4 and x.shape[0] != n:
+            raise ValueError("positions and velocities must have the same length")
+        out = np.zeros(n, dtype=_lib.POINT_DTYPE)
+        inten = np.zeros(n, dtype=np.float64)
+        st = ensemble.call("gr_transfer_endpoints", C.byref(cfg), C.byref(tr), x.ctypes.data, stride, v.ctypes.data, n, out.ctypes.data,
+                           inten.ctypes.data)
+        return ((out, inten), st.asdict()) if stats else (out, inten)
     if isinstance(config.velocity, RenderVelocity):
         pl = config.abi_plane()
         n = pl.width * pl.height
@@ -558,6 +631,8 @@ def tracegeodesics(m, x, v, *args, stats=False, **kwargs):
     `v` may be an (n, 4) array of unconstrained velocities (with `x` one position or an (n, 4)
     array), an `AbstractImagePlane`, or a function `i -> velocity` with `trajectories=`.
     Returns an array of GeodesicPoint records (the reference's `EnsembleEndpointThreads` result).
+    With `trace=TraceRadiativeTransfer(...)`: the pair `(points, intensities)` -- the usual records and, beside them, a
+    float64 array of shape `(n,)` with the intensity each ray ends with (the reference's `gp.aux[1]`).
     """
     if len(args) == 2:
         geometry, λs = args

@@ -221,7 +221,8 @@ enum {
     GR_PF_REDSHIFT = 1,       /* ConstPointFunctions.redshift(m, x)                      */
     GR_PF_STATUS = 2,         /* Float64(gp.status)                                      */
     GR_PF_RADIUS = 3,         /* _equatorial_project(gp.x)                               */
-    GR_PF_WINDING = 4         /* gp.aux.winding of a TraceWindings trace (photon-ring order) */
+    GR_PF_WINDING = 4,        /* gp.aux.winding of a TraceWindings trace (photon-ring order) */
+    GR_PF_INTENSITY = 5       /* gp.aux[1] of a TraceRadiativeTransfer trace: the gr_transfer_* entry points only */
 };
 enum {
     GR_FILTER_NONE = 0,
@@ -407,6 +408,41 @@ int32_t gr_trace_endpoints_device(gr_ctx* ctx, const gr_config* cfg, const doubl
                                   gr_point* d_points, gr_stats* d_stats, void* hip_stream);
 int32_t gr_trace_endpoints(gr_ctx* ctx, const gr_config* cfg, const double* x, int64_t x_stride,
                            const double* v, int64_t n, gr_point* points, gr_stats* stats);
+
+/* ---- covariant radiative transfer (additive within ABI 8): TraceRadiativeTransfer through an optically thick disc ----
+ * src/tracing/radiative-transfer-problem.jl.  The ray carries a ninth state component I, integrated with the geodesic:
+ *     dI/dλ = s (-a_ν I + j_ν / ν³),   s = -g_μν(x) k^μ u^ν,   ν = nu0 s,
+ * with u the fluid velocity at ρ = r sin θ (CircularOrbits.fourvelocity outside the ISCO, CircularOrbits.plunging_fourvelocity
+ * inside) while the ray is inside the geometry, and dI/dλ = 0 outside.  The ray does not end on the surface: every crossing
+ * is located on the dense output, the state (I included) moved there, and the trace goes on -- to the chart, to lambda1, to
+ * maxiters, or to the 65th crossing (GR_FLAG_MAXITERS).  Coefficients are power laws,
+ *     a_ν = a0 ρ^-pa ν^-sa,   j_ν = j0 ρ^-pj ν^-sj
+ * (all exponents zero: the constant coefficients of the reference's doughnut example).  transfer->r_isco separates the two
+ * velocity laws (pf->r_isco is not read).
+ * Refused with GR_ERR_UNSUPPORTED: cfg->disc_id other than GR_DISC_SHAKURA_SUNYAEV / GR_DISC_TABULATED (a warped table,
+ * disc_params[3] != 0, included), GR_METRIC_TABULATED and compiled metrics, metrics without an ISCO (kernels exist for Kerr,
+ * Johannsen, Bumblebee, Kerr-Newman, Johannsen-Psaltis, dilaton-axion and Kerr-refractive), "precision" 32, cfg->q != 0,
+ * cfg->count_windings, and in the render a pf_id other than GR_PF_INTENSITY. */
+typedef struct gr_transfer {
+    double nu0;               /* TraceRadiativeTransfer.ν                                  */
+    double I0;                /* TraceRadiativeTransfer.I₀: the intensity every ray starts with */
+    double a0, j0;            /* absorption / emissivity amplitudes                        */
+    double pa, pj;            /* ... their exponents in ρ                                  */
+    double sa, sj;            /* ... and in ν                                              */
+    double r_isco;            /* isco(m), host-computed: fluid_velocity's switch between the two laws */
+    double reserved;          /* zero                                                      */
+} gr_transfer;
+/* the image of I over `range` of the plane (pf->pf_id = GR_PF_INTENSITY; filter and fill as in gr_render) */
+int32_t gr_transfer_render_device(gr_ctx* ctx, const gr_config* cfg, const gr_transfer* transfer, const gr_plane* plane,
+                                  const gr_pointfunction* pf, const gr_range* range, double* d_image /* device */,
+                                  gr_stats* d_stats /* device, may be NULL */, void* hip_stream);
+int32_t gr_transfer_render(gr_ctx* ctx, const gr_config* cfg, const gr_transfer* transfer, const gr_plane* plane,
+                           const gr_pointfunction* pf, const gr_range* range, double* image /* host, range->count doubles */,
+                           gr_stats* stats /* host, may be NULL */);
+/* the end-point records of n rays given by (x, v) as in gr_trace_endpoints, and their intensities beside them */
+int32_t gr_transfer_endpoints(gr_ctx* ctx, const gr_config* cfg, const gr_transfer* transfer, const double* x,
+                              int64_t x_stride, const double* v, int64_t n, gr_point* points,
+                              double* intensity /* host, n doubles */, gr_stats* stats);
 
 /* ---- tracegeodesics(m, x::SVector, v::SVector, ...): ONE geodesic with every accepted step
  * saved (the reference's single-problem solve with save_on = true, src/tracing/tracing.jl:88-110).
